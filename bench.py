@@ -2,7 +2,7 @@
 """bench.py — images/s of PaDT_Pro_3B REC inference on MI355X (BASELINE.json metric), one process per GPU.
 
   python bench.py [--gpus N --steps K --warmup W]         (N>1: one rank per GPU under torch.distributed.run — given as typed, the script
-                                                           re-launches itself under it; rank 0's JSON line is the only stdout line)
+                                                           launches itself under it as a child process; rank 0's JSON line is the only stdout line)
 
 A "step" = one batch of `--batch` (default 8) synthetic 640x640-equivalent images (grid [1,46,46], 2116 patches,
 529 VRTs, prompt L=577) through the whole hot path with inputs already resident in HBM:
@@ -28,12 +28,6 @@ import sys
 import time
 
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # multi-process GPU work: the host driver only supports dmabuf IPC (RCCL needs it)
-# HIP maps streams onto HSA hardware queues, 4 by default: the runner's streams (caller's, prefill, two decode lanes) fill them, and a fifth
-# stream — the post-processing stream of the to_rle leg, RCCL's and the exchange's side stream with world > 1 — shares a queue with a busy one:
-# its first submission after an idle phase then waits for that queue's backlog (measured: 90 ms once per run, tools/diag/to_rle_timing.py;
-# gone with 8 queues).  Read by the ROCm runtime when it initialises; padt_amd/__init__.py sets the same default for other callers.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -106,6 +100,8 @@ def parse_args():
     ap.add_argument("--no-steady", dest="steady", action="store_false", help="skip the 64-step steady-state run of the same runner")
     ap.add_argument("--no-bf16-twin", dest="bf16_twin", action="store_false", help="skip the leg that times the bf16-operand instantiation of the same workload")
     ap.add_argument("--dump-exchange", default="", help="directory: every rank saves its local results and what the all-gathers delivered (tests)")
+    ap.add_argument("--dump-outputs", default="", help="directory: rank 0 saves what the last timed step returned (boxes, scores, mask logits, ...) as "
+                    "<name>.npy in float32 (float64 for integer fields), at most 64 MB in all, so that two builds can be compared output for output")
     a = ap.parse_args()
     if a.model != "3b" or a.task != "rec" or a.weights != "bf16":
         a.extras = False                                               # the extra keys belong to the headline line only
@@ -675,6 +671,35 @@ def to_rle_leg(model, inp, args, steps):
                     "(padt_mask_upsample_binarize + padt_mask_rle: only the COCO counts strings cross PCIe)"}
 
 
+DUMP_LIMIT_BYTES = 60 << 20      # 62.9 MB of array data: with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(decoded, out_dir, limit=DUMP_LIMIT_BYTES):
+    """What a caller of the timed path receives for one batch (vl_decode's dict) → out_dir/<name>.npy: floating fields as float32, integer
+    and bool fields as float64 (exact).  Tuples of per-object tensors become <name>_<i>.npy.  Should the files exceed `limit` bytes, every
+    array is cut to the same fixed, seeded sample of its flattened elements (sorted indices, numpy seed 0) so that they fit."""
+    import numpy as np
+    arrays = {}
+    for k, v in decoded.items():
+        items = [(k, v)] if not isinstance(v, (tuple, list)) or not v or not isinstance(v[0], torch.Tensor) else [(f"{k}_{i}", t) for i, t in enumerate(v)]
+        for name, t in items:
+            t = t.detach().cpu() if isinstance(t, torch.Tensor) else torch.as_tensor(t)
+            fp = t.is_floating_point()
+            arrays[name] = t.to(torch.float32 if fp else torch.float64).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        keep = limit / total
+        for name, a in arrays.items():
+            n = max(1, int(a.size * keep))
+            if n < a.size:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+                arrays[name] = a.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def csrc_sha16():
     """sha256 (first 16 hex digits) over the kernel sources: what a committed PMC measurement was taken on."""
     import hashlib
@@ -692,7 +717,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` as typed: become `python -m torch.distributed.run --nproc-per-node N bench.py ...` (one rank per GPU;
+        # `python bench.py --gpus N` as typed: run `python -m torch.distributed.run --nproc-per-node N bench.py ...` (one rank per GPU;
         # 127.0.0.1 rendezvous — the container hostname may not resolve; torchrun's own chatter goes to stderr, rank 0's line to stdout)
         import socket
         s = socket.socket()
@@ -702,7 +727,13 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        import ctypes
+        import signal
+        import subprocess
+
+        def die_with_parent():                                         # the launcher (and through it every rank) ends when this process is killed
+            ctypes.CDLL(None, use_errno=True).prctl(1, signal.SIGTERM)    # PR_SET_PDEATHSIG
+        sys.exit(subprocess.call(cmd, preexec_fn=die_with_parent))     # a child process, not exec: this one stays the launcher's parent
     if args.gpus != world:
         print(f"bench.py --gpus {args.gpus} under a launcher with WORLD_SIZE={world}: the two must agree", file=sys.stderr)
         sys.exit(2)
@@ -810,6 +841,9 @@ def main():
         torch.save({"local": dump, "gathered": [g.records.cpu() for g in gathered], "cap": args.cap, "batch": args.batch,      # plain tensors: torch.load(weights_only)
                     "continuation": [None if g.continuation is None else g.continuation.cpu() for g in gathered]},
                    os.path.join(args.dump_exchange, f"rank{rank}.pt"))
+
+    if args.dump_outputs and rank == 0:                                # the timed path's last step, before any side leg runs
+        dump_outputs(decoded, args.dump_outputs)
 
     side = not dist_on and rank == 0 and not args.no_alt
     # the same runner over 64 steps (8 decode groups): what the pipeline does once the fill / drain of the driver's 20-step window

@@ -361,14 +361,30 @@ def test_generate_argument_policy_defaults_unknowns_and_max_length():
         m.generate(input_ids=torch.zeros((1, 4), dtype=torch.long), max_new_tokens=2, pad_token_id=151643, output_logits=True)
 
 
-def test_import_sets_hardware_queue_default_but_never_overrides_the_user():
-    """padt_amd/__init__.py: GPU_MAX_HW_QUEUES defaults to 8 (a fifth HIP stream must not share an HSA queue with the prefill stream:
-    profiles/r05_to_rle_hw_queue_stall.log); an explicit setting wins."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = "import os, sys; sys.path.insert(0, %r); import padt_amd; print(os.environ['GPU_MAX_HW_QUEUES'])" % root
-    env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
-    assert subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env).stdout.strip() == "8"
-    env["GPU_MAX_HW_QUEUES"] = "2"
-    assert subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env).stdout.strip() == "2"
+def test_bench_dump_outputs_writes_every_field_as_float_and_samples_to_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every field of vl_decode's dict → <name>.npy (floating → float32, integer → float64, tuples of per-object
+    tensors → <name>_<i>.npy); above the byte limit every array becomes the same seeded sample, identical from call to call."""
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))   # bench's import-time default stays
+    import bench                                                                                          # out of this process
+    g = torch.Generator().manual_seed(3)
+    decoded = {"pred_boxes": torch.rand(3, 4, generator=g, dtype=torch.float64), "pred_score": torch.rand(3, 1, generator=g).half(),
+               "pred_mask": torch.randn(3, 16, 16, generator=g), "pred_mask_valid_hw": (torch.tensor([16, 12, 9]), torch.tensor([16, 10, 8])),
+               "sample_idx": [0, 0, 2], "sample_idx_t": torch.tensor([0, 0, 2], dtype=torch.int32)}
+    names = bench.dump_outputs(decoded, str(tmp_path / "full"))
+    assert names == sorted(["pred_boxes", "pred_score", "pred_mask", "pred_mask_valid_hw_0", "pred_mask_valid_hw_1", "sample_idx", "sample_idx_t"])
+    for n in names:
+        a = np.load(tmp_path / "full" / f"{n}.npy")
+        assert a.dtype in (np.float32, np.float64)
+    assert np.load(tmp_path / "full" / "pred_boxes.npy").dtype == np.float32
+    assert np.array_equal(np.load(tmp_path / "full" / "pred_mask.npy"), decoded["pred_mask"].numpy())
+    assert np.load(tmp_path / "full" / "sample_idx.npy").dtype == np.float64 and np.load(tmp_path / "full" / "sample_idx.npy").tolist() == [0, 0, 2]
+    assert np.load(tmp_path / "full" / "pred_mask_valid_hw_1.npy").tolist() == [16, 10, 8]
+    limit = 1024
+    for d in ("a", "b"):
+        bench.dump_outputs(decoded, str(tmp_path / d), limit=limit)
+    assert sum(np.load(tmp_path / "a" / f"{n}.npy").nbytes for n in names) <= limit
+    for n in names:
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert np.array_equal(a, b)
+    m = np.load(tmp_path / "a" / "pred_mask.npy")
+    assert 0 < m.size < decoded["pred_mask"].numel() and np.isin(m, decoded["pred_mask"].numpy().reshape(-1)).all()
