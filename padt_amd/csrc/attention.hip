@@ -367,6 +367,18 @@ struct DecodeArgs {
 // at D = 128: the fused kernel's scalar rotation was compiled to v_fma_mixlo_f16 — one rounding — where llm_qkv_post's vector path rounds
 // twice; see rounded32() in common.h.)  Only the fused kernel runs in a decode step, so no product invariant (merged == un-merged decode,
 // graph == eager) ever depended on it.
+// Keys >= len of the split that contains len: their probabilities are exactly 0, but 0 x inf is NaN, and a reused cache holds whatever an earlier
+// (possibly overflowed) batch wrote there.  The V^T fragment of such keys is zeroed: element e of the 16-bit pair word w sits at key offset off(w) + e.
+PADT_DEV unsigned keep_keys2(unsigned w, int off, int n) {
+    return w & ((off + 1 < n) ? 0xffffffffu : (off < n ? 0x0000ffffu : 0u));
+}
+// 8 consecutive keys (row-major V^T fragment): keep the first n
+PADT_DEV u32x4 keep_keys8(u32x4 v, int n) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w) v[w] = keep_keys2(v[w], 2 * w, n);
+    return v;
+}
+
 template <int D>
 __global__ __launch_bounds__(64) void decode_attn_kernel(DecodeArgs p) {
 #pragma clang fp contract(off)
@@ -448,8 +460,13 @@ __global__ __launch_bounds__(64) void decode_attn_kernel(DecodeArgs p) {
         const x16x8 pf = ld_frag(Pw + frow * 72 + ks * 32 + fq * 8);
         int kk0 = k0 + ks * 32 + fq * 8;                          // 8 keys, 16-byte aligned in the V^T row
         kk0 = (kk0 + 8 <= p.S_max) ? kk0 : p.S_max - 8;           // (S_max % 64 == 0, so this never actually clamps)
+        const bool tail = len - k0 < 64;                          // the split that contains len: keys >= len must not reach P·V
 #pragma unroll
-        for (int i = 0; i < NB; ++i) o[i] = mfma16(pf, ld_frag(vbase + (long)(i * 16 + frow) * p.S_max + kk0), o[i]);
+        for (int i = 0; i < NB; ++i) {
+            u32x4 vv = *reinterpret_cast<const u32x4*>(vbase + (long)(i * 16 + frow) * p.S_max + kk0);
+            if (tail) vv = keep_keys8(vv, len - kk0);
+            o[i] = mfma16(pf, __builtin_bit_cast(x16x8, vv), o[i]);
+        }
     }
     // partials: lane holds O[head = fq*4 + r][d = i*16 + frow]
 #pragma unroll
@@ -488,12 +505,14 @@ __global__ void decode_combine_kernel(DecodeArgs p) {
             const bool ok = s0 + i < p.nsplit;
             const long base = base0 + (long)(ok ? s0 + i : 0) * 16;
             mv[i] = ok ? p.part_ml[base * 2] : -INFINITY;
-            lv[i] = p.part_ml[base * 2 + 1];
-            ov[i] = (mv[i] == -INFINITY) ? 0.f : p.part_o[base * D + d];      // empty splits never wrote their O partial
+            lv[i] = ok ? p.part_ml[base * 2 + 1] : 0.f;
+            ov[i] = (lv[i] == 0.f) ? 0.f : p.part_o[base * D + d];            // empty splits never wrote their O partial
         }
+        // An empty split is marked by l == 0 (a split with a key has l >= 1), NOT by m == -inf: a NaN query (rope_fin's overflow marker) makes every
+        // score NaN, which fmaxf skips — m = -inf, l = NaN —, and that partial must reach the output as NaN rather than be dropped as empty.
 #pragma unroll
         for (int i = 0; i < CH; ++i) {
-            if (mv[i] == -INFINITY) continue;
+            if (lv[i] == 0.f) continue;
             const float w = exp2f(mv[i] - M);
             L += w * lv[i];
             acc += w * ov[i];
@@ -502,7 +521,7 @@ __global__ void decode_combine_kernel(DecodeArgs p) {
     const long ld = (long)p.Hq * D;
     const int n = hq * D + d;
     const long o = p.out_packed ? (long)(b >> 4) * 16 * ld + ((long)(n >> 3) * 16 + (b & 15)) * 8 + (n & 7) : (long)b * ld + n;
-    p.out[o] = f2x(L > 0.f ? acc / L : 0.f);
+    p.out[o] = f2x(L == 0.f ? 0.f : acc / L);                     // no key at all: a zero row; NaN stays NaN
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -684,6 +703,7 @@ __global__ __launch_bounds__(64) void decode_attn_rope_kernel(DecodeRopeArgs p) 
         for (int i = 0; i < NB; ++i) {
             const int d = i * 16 + frow;
             u32x4 vv = vraw[ks][i];
+            if (owner) vv = keep_keys8(vv, len - kk0);             // stale keys past len (keep_keys2)
             if (j >= 0 && j < 8) {
                 const unsigned nv = Vnew[d];
                 const int wsel = j >> 1;
@@ -841,6 +861,16 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_rope_packed_kernel(Decode
                         const u32x2 v0 = *reinterpret_cast<const u32x2*>(vr), v1 = *reinterpret_cast<const u32x2*>(vr + 16);
                         vfr[ks][i] = u32x4{v0[0], v0[1], v1[0], v1[1]};
                     }
+            }
+            if (owner) {                                          // stale keys past len (keep_keys2); words 0-1: keys base + 0..3, 2-3: base + 16..19
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    const int n = len - (k0 + ks * 32 + fq * 4);
+#pragma unroll
+                    for (int i = 0; i < NB; ++i)
+#pragma unroll
+                        for (int w = 0; w < 4; ++w) vfr[ks][i][w] = keep_keys2(vfr[ks][i][w], (w >> 1) * 16 + (w & 1) * 2, n);
+                }
             }
             unsigned vnew[NB];
             if (owner) {

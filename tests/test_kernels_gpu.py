@@ -353,10 +353,10 @@ def test_gemm_strided_views_and_argument_errors(ops):
 
 
 # ------------------------------------------------------------------------------------------------------------ attention
-def ref_attn(q, k, v, cu_q, cu_k, H, Hkv, D, causal):
+def ref_attn(q, k, v, cu_q, cu_k, H, Hkv, D, causal, dtype=torch.float32):
     Tq = q.shape[0]
-    out = torch.zeros(Tq, H * D, device=q.device)
-    qf, kf, vf = q.float().view(Tq, H, D), k.float().view(-1, Hkv, D), v.float().view(-1, Hkv, D)
+    out = torch.zeros(Tq, H * D, device=q.device, dtype=dtype)
+    qf, kf, vf = q.to(dtype).view(Tq, H, D), k.to(dtype).view(-1, Hkv, D), v.to(dtype).view(-1, Hkv, D)
     rep = H // Hkv
     for s in range(len(cu_q) - 1):
         q0, q1, k0, k1 = cu_q[s], cu_q[s + 1], cu_k[s], cu_k[s + 1]
