@@ -308,10 +308,12 @@ int  padt_greedy_step(void* stream, const void* part_val, const void* part_idx, 
 /* Sampling branch (padt.py:740-743 multinomial over softmax of the warped scores): one token per row drawn from the fp32 logits
  * padt_vrt_head wrote (logits_f32), after HF's Temperature → TopK → TopP warpers (generation/logits_process.py) with the
  * parameters in gen_cfg (DEVICE: {float penalty; int eos[4]; int do_sample; unsigned seed; float temperature; int top_k;
- * float top_p; int pad[2]}); exact top-k by radix select, nucleus over the sorted survivors (top_p < 1 needs 0 < top_k <= 1024),
- * Gumbel-max draw keyed by (seed, *step, row, index) so a captured decode graph draws fresh numbers every replay.  Writes one
- * (value, index) pair per row in padt_greedy_step's partial layout (nblk = 1). */
-int  padt_sample_token(void* stream, const void* logits_f32, long ld_logits, long n_rows_table, const void* gen_cfg, const int* step,
+ * float top_p; int write_back; int pad}); exact top-k by radix select, nucleus over the sorted survivors (top_p < 1 needs
+ * 0 < top_k <= 1024; entries tied at the k-th value: the lowest indices stay), Gumbel-max draw keyed by (seed, *step, row, index) so a
+ * captured decode graph draws fresh numbers every replay.  Writes one (value, index) pair per row in padt_greedy_step's partial layout
+ * (nblk = 1).  write_back != 0: logits_f32[b][0..n_rows_table) is then overwritten with the warped scores (l / T on the kept entries,
+ * -inf elsewhere: HF's `scores` under sampling, padt.py:717-720). */
+int  padt_sample_token(void* stream, void* logits_f32, long ld_logits, long n_rows_table, const void* gen_cfg, const int* step,
                        void* part_val, void* part_idx, long batch);
 /* Arg-max of fp32 score rows → one (value, index) pair per row in padt_greedy_step's partial layout (nblk = 1), ties → lowest index
  * (torch.argmax, padt.py:745): the selection of the HOOKED decode loop, where caller-supplied logits processors (padt.py:717) have rewritten

@@ -30,7 +30,8 @@ struct GenCfg {
     float temperature;                 // TemperatureLogitsWarper
     int top_k;                         // TopKLogitsWarper (0 = off)
     float top_p;                       // TopPLogitsWarper (1 = off)
-    int pad[2];
+    int write_back;                    // sample_token_kernel overwrites its input rows with the warped scores (l / T, -inf outside the kept set)
+    int pad;
 };
 
 struct HeadArgs {
@@ -303,11 +304,17 @@ extern "C" int padt_greedy_step(void* stream, const void* part_val, const void* 
 // logits warpers (generation/logits_process.py: Temperature → TopK → TopP, the order _get_logits_processor builds at padt.py:570-580).
 // One block per row over the fp32 logits the head kernel wrote (mask / repetition penalty / scripted mode already applied):
 //   top-k: exact k-th largest by a 4-pass radix select on order-preserving keys; everything >= it stays (HF keeps ties);
-//   top-p: the survivors (<= 1024: top_p needs top_k) are sorted in LDS; rank r stays iff the probability mass of the ranks
-//          before it is < top_p (= HF's "remove ascending-cumulative <= 1 - top_p", at least one token kept);
+//   top-p: the survivors STRICTLY above the k-th largest value (<= k - 1 <= 1023: top_p needs top_k) are sorted in LDS; rank r stays
+//          iff the probability mass of the ranks before it is < top_p (= HF's "remove ascending-cumulative <= 1 - top_p", at least one
+//          token kept).  The entries EQUAL to the k-th value (any number of them: one exact tie already makes k + 1 survivors) all carry
+//          the same probability and come after every sorted rank: they are one block with a count, of which the lowest-index j stay,
+//          j = the number of tied ranks whose mass-before is < top_p — the order (value descending, index ascending) of a full sort;
 //   draw:  Gumbel-max — argmax((l - max)/T + g), g = -log(-log u), u from a counter-based hash of (seed, step, row, index) —
 //          an exact multinomial draw from softmax(l/T) over the survivors without normalising or building a CDF.
 // The draws cannot match torch.multinomial's (different generator); the DISTRIBUTION is what the tests check.
+// gen->write_back: the row is then overwritten with the warped scores HF's samplers see (padt.py:717-720: the warpers are part of
+// logits_processor, so `scores` and the stopping criteria get them): l / T (a true fp32 division, HF's TemperatureLogitsWarper) on the
+// kept entries, -inf everywhere else in [0, n).
 PADT_DEV unsigned hash32(unsigned x) {
     x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
     return x;
@@ -324,19 +331,22 @@ PADT_DEV unsigned float_key(float f) {                                    // ord
     const unsigned u = __builtin_bit_cast(unsigned, f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+PADT_DEV float key_float(unsigned k) {                                    // inverse of float_key
+    return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
 
-__global__ __launch_bounds__(1024) void sample_token_kernel(const float* __restrict__ logits, long ld, int n, const GenCfg* __restrict__ g,
+__global__ __launch_bounds__(1024) void sample_token_kernel(float* logits, long ld, int n, const GenCfg* __restrict__ g,
                                                             const int* __restrict__ step, float* __restrict__ out_val,
                                                             int* __restrict__ out_idx) {
-    __shared__ unsigned hist[256];
+    __shared__ unsigned hist[256];                                        // radix histogram; then the per-wave tie counts of the cut search
     __shared__ unsigned sel[2];                                           // chosen bin, remaining rank
     __shared__ float sval[1024];
     __shared__ int sidx[1024];
     __shared__ float red_v[1024];
     __shared__ int red_i[1024];
-    __shared__ int cnt;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* row = logits + (long)b * ld;
+    __shared__ int cnt, n_tie, tie_keep, tie_last;                        // sorted ranks; tied entries, how many stay, index of the last kept
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float* row = logits + (long)b * ld;
     const float T = g->temperature > 0.f ? g->temperature : 1.f;
     const int k = g->top_k;
     const float top_p = g->top_p;
@@ -388,17 +398,23 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(const float* __restr
     __syncthreads();
     float best = -INFINITY;
     int bidx = 0x7fffffff;
-    if (top_p < 1.0f && k > 0 && k <= 1024) {
-        // ---- nucleus over the (<= 1024) top-k survivors: gather, sort descending, prefix mass, Gumbel over the kept ranks
-        if (tid == 0) cnt = 0;
+    const bool nucleus = top_p < 1.0f && k > 0 && k <= 1024;
+    int n_keep = 0;                                                       // nucleus: kept sorted ranks (a prefix of the sort)
+    if (nucleus) {
+        // ---- nucleus over the top-k survivors: gather the entries above the threshold (< k <= 1024 of them; k >= n: n <= 1024), sort
+        //      descending, prefix mass, Gumbel over the kept ranks; the entries at the threshold are one block (see above)
+        if (tid == 0) { cnt = 0; n_tie = 0; }
         sval[tid] = -INFINITY;
         sidx[tid] = 0x7fffffff;
         __syncthreads();
         for (int i = tid; i < n; i += 1024) {
             const float v = row[i];
-            if (float_key(v) >= thresh) {
+            const unsigned key = float_key(v);
+            if (key > thresh) {
                 const int slot = atomicAdd(&cnt, 1);
                 if (slot < 1024) { sval[slot] = v; sidx[slot] = i; }
+            } else if (key == thresh) {
+                atomicAdd(&n_tie, 1);
             }
         }
         __syncthreads();
@@ -423,12 +439,59 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(const float* __restr
             red_v[tid] += add;
             __syncthreads();
         }
-        const float total = red_v[1023];
+        const float S = red_v[1023];                                      // mass above the threshold (no tie: the total, bit for bit as before)
+        const float tv = key_float(thresh);                               // the tied value (finite: thresh > key(-inf))
+        const float et = n_tie > 0 ? expf((tv - mx) / T) : 0.f;           // mass of ONE tied entry
+        const float total = S + (float)n_tie * et;
         const float before = (red_v[tid] - pv) / total;                   // probability mass of the ranks before this one
         const bool keep = sval[tid] > -INFINITY && (tid == 0 || before < top_p);
+        n_keep = __syncthreads_count(keep);
+        if (tid == 0) {
+            // tied rank j (0-based, ascending index) has mass-before (S + j et) / total, non-decreasing in j: the kept ones are those below the
+            // first j whose mass-before is >= top_p; none when a sorted rank was already cut, at least one when nothing lies above the threshold
+            int lo = 0, hi = n_tie;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if ((S + (float)mid * et) / total < top_p) lo = mid + 1;
+                else hi = mid;
+            }
+            if (n_keep < cnt) lo = 0;
+            if (cnt == 0 && n_tie > 0 && lo == 0) lo = 1;
+            tie_keep = lo;
+            tie_last = lo == n_tie ? 0x7fffffff : -1;
+        }
+        __syncthreads();
+        const int jk = tie_keep;
+        if (jk > 0 && jk < n_tie) {
+            // index of the jk-th tied entry: count the tied entries of consecutive 1024-column chunks (ballot per wave, 16 wave counts)
+            int seen = 0;
+            for (int c0 = 0; c0 < n && seen < jk; c0 += 1024) {
+                const int i = c0 + tid;
+                const bool t = i < n && float_key(row[i]) == thresh;
+                const unsigned long long bal = __ballot(t);
+                if (lane == 0) hist[wave] = (unsigned)__popcll(bal);
+                __syncthreads();
+                int pre = 0, tot = 0;
+#pragma unroll
+                for (int w = 0; w < 16; ++w) { pre += w < wave ? (int)hist[w] : 0; tot += (int)hist[w]; }
+                if (t && seen + pre + __popcll(bal & ((1ull << lane) - 1ull)) == jk - 1) tie_last = i;
+                seen += tot;
+                __syncthreads();
+            }
+            __syncthreads();
+        }
         if (keep) {
             best = (sval[tid] - mx) / T + gumbel_noise(seed, st, (unsigned)b, (unsigned)sidx[tid]);
             bidx = sidx[tid];
+        }
+        if (jk > 0) {
+            const int last = tie_last;
+            for (int i = tid; i < n && i <= last; i += 1024) {
+                if (float_key(row[i]) == thresh) {
+                    const float sc = (tv - mx) / T + gumbel_noise(seed, st, (unsigned)b, (unsigned)i);
+                    if (sc > best || (sc == best && i < bidx)) { best = sc; bidx = i; }
+                }
+            }
         }
     } else {
         for (int i = tid; i < n; i += 1024) {
@@ -452,15 +515,35 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(const float* __restr
         __syncthreads();
     }
     if (tid == 0) { out_val[b] = red_v[0]; out_idx[b] = red_i[0]; }
+    if (g->write_back) {                                                  // every read of the row is behind the barriers above
+        const float lv = n_keep > 0 ? sval[n_keep - 1] : INFINITY;       // nucleus: last kept sorted rank (value, index)
+        const int li = n_keep > 0 ? sidx[n_keep - 1] : -1;
+        const int last = nucleus ? tie_last : 0x7fffffff;
+        constexpr int WU = 8;                                             // loads in flight per thread before the stores
+        for (int i0 = tid; i0 < n; i0 += WU * 1024) {
+            float v[WU];
+#pragma unroll
+            for (int u = 0; u < WU; ++u) v[u] = i0 + u * 1024 < n ? row[i0 + u * 1024] : 0.f;
+#pragma unroll
+            for (int u = 0; u < WU; ++u) {
+                const int i = i0 + u * 1024;
+                const unsigned key = float_key(v[u]);
+                const bool kept = !nucleus ? key >= thresh
+                                : key > thresh ? (v[u] > lv || (v[u] == lv && i <= li)) : (key == thresh && i <= last);
+                if (i < n) row[i] = kept ? v[u] / T : -INFINITY;
+            }
+        }
+    }
 }
 
 // next token per row by multinomial sampling from the warped logits; writes one (value, index) "partial" per row in the layout
-// padt_greedy_step reads with nblk = 1, so the bookkeeping kernel is shared with the greedy path.
-extern "C" int padt_sample_token(void* stream, const void* logits_f32, long ld_logits, long n_rows_table, const void* gen_cfg,
+// padt_greedy_step reads with nblk = 1, so the bookkeeping kernel is shared with the greedy path.  With gen_cfg's write_back set the rows
+// are overwritten with the warped scores (see sample_token_kernel).
+extern "C" int padt_sample_token(void* stream, void* logits_f32, long ld_logits, long n_rows_table, const void* gen_cfg,
                                  const int* step, void* part_val, void* part_idx, long batch) {
     if (batch <= 0) return 0;
     if (gen_cfg == nullptr || n_rows_table <= 0 || n_rows_table > 0x7fffffffL) { padt_set_error("padt_sample_token: gen_cfg and a table size are required"); return -1; }
-    hipLaunchKernelGGL(sample_token_kernel, dim3((unsigned)batch), dim3(1024), 0, (hipStream_t)stream, (const float*)logits_f32, ld_logits,
+    hipLaunchKernelGGL(sample_token_kernel, dim3((unsigned)batch), dim3(1024), 0, (hipStream_t)stream, (float*)logits_f32, ld_logits,
                        (int)n_rows_table, (const GenCfg*)gen_cfg, step, (float*)part_val, (int*)part_idx);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }

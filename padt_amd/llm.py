@@ -10,6 +10,7 @@ libpadt_hip.so.  Differences from the reference's control flow that do not chang
   * a decode step is ONE captured hipGraph replayed per token; argmax, EOS/pad bookkeeping, token append and the
     per-step hidden-state stash all happen on device, the host syncs once per `sync_every` steps.
 """
+import gc
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -200,6 +201,8 @@ class DecodeSession:
         self.summary_host = torch.zeros(2 + 3 * B, dtype=I32).pin_memory() if torch.device(device).type == "cuda" else torch.zeros(2 + 3 * B, dtype=I32)
         self.keep_scores = False         # output_scores=True: every step's masked fp32 logit rows are filed in `scores` [t_max][B][W]
         self.scores = None
+        self.keep_logits = False         # output_logits=True under sampling: the rows before the warpers, in `raw_scores` [t_max][B][W]
+        self.raw_scores = None
         self.rope_cs = z(B, hd // 2, 2, dt=torch.float32)
         self.n_qkv = (cfg.num_attention_heads + 2 * Hkv) * hd
         self.graphs = {}                 # captured decode-step graph per mode (greedy / sampling: different kernel sequences)
@@ -296,13 +299,21 @@ class DecodeSession:
             new = _call_hooks(hk["processors"], hk["sequences"](), view, chain=True)
             if new is not view:
                 view.copy_(new.to(torch.float32))
-        if self.keep_scores:                                 # padt.py:719-720: scores += (next_token_scores,) — filed under the device step counter
-            if self.scores is None:
-                self.scores = torch.zeros((self.t_max,) + tuple(self.logits.shape), device=hn.device, dtype=torch.float32)
+        if self.keep_scores and self.scores is None:
+            self.scores = torch.zeros((self.t_max,) + tuple(self.logits.shape), device=hn.device, dtype=torch.float32)
+        if self.keep_logits:                                 # padt.py:721-722: raw_logits += (next_token_logits,) — differ from the scores under sampling
+            if self.raw_scores is None:
+                self.raw_scores = torch.zeros((self.t_max,) + tuple(self.logits.shape), device=hn.device, dtype=torch.float32)
+            ops.stash_step_f32(lg, self.step, self.raw_scores)
+        if self.keep_scores and not self.do_sample:          # padt.py:719-720: scores += (next_token_scores,) — filed under the device step counter
             ops.stash_step_f32(lg, self.step, self.scores)
         nblk = self.nblk
         if self.do_sample:                                   # padt.py:740-743: multinomial over softmax of the warped scores
+            # with keep_scores the session's gen_cfg has write_back set: lg then holds the warped rows (l / T, -inf outside top-k / top-p),
+            # HF's next_token_scores — the warpers are part of its logits_processor (padt.py:717)
             ops.sample_token(lg, cfg.vocab_size + self.np_max, self.gen_cfg, self.step, self.part_val, self.part_idx, self.B)
+            if self.keep_scores:
+                ops.stash_step_f32(lg, self.step, self.scores)
             nblk = 1
         elif hk is not None and hk["processors"]:            # the head's fused arg-max partials describe the rows BEFORE the caller's processors
             ops.argmax_rows(lg, cfg.vocab_size + self.np_max, self.part_val, self.part_idx, self.B)
@@ -329,16 +340,24 @@ class DecodeSession:
             for _ in range(n):
                 one_step()
             return
-        gkey = (self.do_sample, self.keep_scores, self.step_fn is not None)   # different kernel sequences → one captured graph per mode
+        gkey = (self.do_sample, self.keep_scores, self.keep_logits, self.step_fn is not None)   # different kernel sequences → one captured graph per mode
         if gkey not in self.graphs:
             one_step()                                       # real step; also pays every one-time kernel attribute call
             n -= 1
             g = torch.cuda.CUDAGraph()
-            # thread_local: only THIS thread's calls are checked during capture.  With world > 1 the process group's watchdog thread polls
-            # the events of an in-flight result gather (pipeline.ResultExchange) while a later lane captures its graph; under the default
-            # global mode such a query from another thread invalidates the capture.
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                one_step()
+            # No garbage collection inside the capture: a dead reference cycle that still owns GPU objects (a released model's sessions with
+            # their graphs, events and cached blocks) would be finalised on this thread in the middle of the capture, which aborts the process.
+            gc_on = gc.isenabled()
+            gc.disable()
+            try:
+                # thread_local: only THIS thread's calls are checked during capture.  With world > 1 the process group's watchdog thread polls
+                # the events of an in-flight result gather (pipeline.ResultExchange) while a later lane captures its graph; under the default
+                # global mode such a query from another thread invalidates the capture.
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    one_step()
+            finally:
+                if gc_on:
+                    gc.enable()
             self.graphs[gkey] = g
         t = ops.STEP_TIMER
         ev = t.begin() if t is not None else None

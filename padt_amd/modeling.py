@@ -294,9 +294,11 @@ class PaDTForConditionalGeneration:
         generation_config.json (self.generation_config), exactly the entries HF's generate turns into a logits processor /
         stopping criterion / sampling switch (padt.py:436,570-580,740-743); explicit arguments override.
         ``output_scores=True`` (padt.py:719-720): ``.scores`` = T-tuple of (B, table rows) fp32 tensors — the step's logits after the logit mask
-        (padt.py:292-301) and the logits processors (repetition penalty, the synthetic ``schedule``), i.e. what the arg-max / the sampler saw.
-        ``output_logits=True`` (padt.py:721-724, the rows BEFORE the processors): served when no processor is active (repetition_penalty == 1,
-        no schedule — then they ARE the scores), rejected otherwise.  ``pad_token_id``: must be the config's (the greedy kernel pads finished
+        (padt.py:292-301) and the logits processors (repetition penalty, the synthetic ``schedule``), i.e. what the arg-max saw; under
+        ``do_sample=True`` also after HF's warpers, which are part of ``logits_processor`` there (padt.py:717-720): ``logits / temperature`` on
+        the tokens top-k / top-p keep, ``-inf`` on every other one.  Stopping criteria that take scores get the same rows.
+        ``output_logits=True`` (padt.py:721-724, the rows BEFORE the processors and warpers): served when no processor is active
+        (repetition_penalty == 1, no schedule — then, under greedy decoding, they ARE the scores), rejected otherwise.  ``pad_token_id``: must be the config's (the greedy kernel pads finished
         rows with it, padt.py:749).
         ``do_sample=True``: multinomial sampling after HF's Temperature → TopK → TopP warpers (``temperature`` / ``top_k`` /
         ``top_p``, defaults from generation_config, HF's own defaults 1.0 / 50 / 1.0) on a device counter-based generator keyed
@@ -324,7 +326,8 @@ class PaDTForConditionalGeneration:
         ctx = self.generate_launch(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, do_sample,
                                    schedule, sync_every, use_graph, lane, repetition_penalty=repetition_penalty,
                                    eos_token_id=eos_token_id, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
-                                   keep_scores=bool(output_scores or output_logits or hooks is not None), hooks=hooks)
+                                   keep_scores=bool(output_scores or output_logits or hooks is not None), hooks=hooks,
+                                   keep_logits=bool(output_logits))
         return self.generate_collect(ctx, output_hidden_states, return_dict_in_generate, output_scores=bool(output_scores),
                                      output_logits=bool(output_logits))
 
@@ -332,7 +335,7 @@ class PaDTForConditionalGeneration:
     def generate_launch(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens=1024, do_sample=None,
                         schedule=None, sync_every=16, use_graph=True, lane=0, decode_stream=None, group=None, n_slots=1,
                         repetition_penalty=None, eos_token_id=None, temperature=None, top_k=None, top_p=None, seed=None,
-                        vit_stream=None, inputs_ready=None, keep_scores=False, hooks=None):
+                        vit_stream=None, inputs_ready=None, keep_scores=False, hooks=None, keep_logits=False):
         """Asynchronous half of generate(): host integer prep + every kernel up to the first host sync point, enqueued on
         the current stream (the decode steps on ``decode_stream`` if given, ordered after the prefill by an event).
         Returns a group context for generate_collect().
@@ -349,7 +352,7 @@ class PaDTForConditionalGeneration:
         if owner is not self:
             return owner.generate_launch(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, do_sample, schedule, sync_every,
                                          use_graph, lane, decode_stream, group, n_slots, repetition_penalty, eos_token_id, temperature, top_k, top_p,
-                                         seed, vit_stream, inputs_ready, keep_scores, hooks)
+                                         seed, vit_stream, inputs_ready, keep_scores, hooks, keep_logits)
         self._batches_seen += 1
         gc = self.generation_config
         do_sample = gc.do_sample if do_sample is None else do_sample
@@ -374,7 +377,8 @@ class PaDTForConditionalGeneration:
         if cfg.eos_token_id not in eos_list or len(eos_list) > 4:
             raise NotImplementedError("eos_token_id must contain config.eos_token_id and hold at most 4 ids")
         samp = (float(temperature), int(top_k), float(top_p), int(seed)) if do_sample else None
-        gen_key = (float(repetition_penalty), tuple(eos_list), samp, bool(keep_scores))
+        # under sampling the scores are the warped rows (sample_token writes them back), so output_logits needs a stash of its own
+        gen_key = (float(repetition_penalty), tuple(eos_list), samp, bool(keep_scores), bool(keep_logits) and samp is not None)
         grid = image_grid_thw.detach().cpu().long()
         B = input_ids.shape[0]
         T_max = int(max_new_tokens)
@@ -393,9 +397,11 @@ class PaDTForConditionalGeneration:
                          gen_key=gen_key, eos_list=eos_list, lane=lane, owner=self)
             sess.gen_cfg.copy_(ops.gen_cfg_tensor(gen_key[0], gen_key[1], "cpu", do_sample=samp is not None, seed=samp[3] if samp else 0,
                                                   temperature=samp[0] if samp else 1.0, top_k=samp[1] if samp else 0,
-                                                  top_p=samp[2] if samp else 1.0).to(dev, non_blocking=True))
+                                                  top_p=samp[2] if samp else 1.0,
+                                                  write_back=samp is not None and bool(keep_scores)).to(dev, non_blocking=True))
             sess.do_sample = samp is not None
             sess.keep_scores = bool(keep_scores)
+            sess.keep_logits = gen_key[4]
             sess.hooks = None
             if hooks is not None:
                 ids_dev = input_ids.detach().to(dev).long().contiguous()
@@ -575,17 +581,17 @@ class PaDTForConditionalGeneration:
             hidden = StepHiddenStates(hbuf[:n_steps, row0: row0 + B].clone(), n_steps, sub["hn_all"],
                                       plan.lens, plan.L_pad)
             table_rows = cfg.vocab_size + sub["n_proto"]
-            scores = None
-            if output_scores or output_logits:
+            def per_step(stash):
                 # per step (B, table rows): text columns + this batch's own prototype columns of the session-wide rows (padt.py:719-724)
                 V, p0 = cfg.vocab_size, sub["proto_row0"]
-                rows_t = sess.scores[:n_steps, row0: row0 + B]
+                rows_t = stash[:n_steps, row0: row0 + B]
                 if p0 == 0:
-                    scores = tuple(rows_t[t, :, :table_rows].clone() for t in range(n_steps))
-                else:
-                    scores = tuple(torch.cat([rows_t[t, :, :V], rows_t[t, :, V + p0: V + p0 + sub["n_proto"]]], dim=1) for t in range(n_steps))
+                    return tuple(rows_t[t, :, :table_rows].clone() for t in range(n_steps))
+                return tuple(torch.cat([rows_t[t, :, :V], rows_t[t, :, V + p0: V + p0 + sub["n_proto"]]], dim=1) for t in range(n_steps))
+            scores = per_step(sess.scores) if output_scores or output_logits else None
+            logits = (per_step(sess.raw_scores) if sess.keep_logits else scores) if output_logits else None
             out = CustomGenerateDecoderOnlyOutput(
-                sequences=sequences, scores=scores if output_scores else None, logits=scores if output_logits else None, attentions=None,
+                sequences=sequences, scores=scores if output_scores else None, logits=logits, attentions=None,
                 hidden_states=hidden if output_hidden_states else None, past_key_values=sess,
                 past_image_embeds=sub["proto"].clone(),
                 past_logit_mask=ops.logit_mask(sess.vrt_off[row0: row0 + B + 1], cfg.vocab_size, table_rows, sub["proto_row0"], B),

@@ -984,6 +984,55 @@ def test_output_scores_are_the_oracles_processed_logits(setup):
     assert torch.equal(outs[1].past_logit_mask, alone.past_logit_mask)
 
 
+def test_output_scores_under_sampling_are_the_warped_rows(setup):
+    """do_sample=True (padt.py:717-720: HF's Temperature / TopK / TopP warpers are part of logits_processor, so `scores` are the warped rows): each
+    step's row has at most top_k finite entries, the drawn token is finite in its row, the finite values are the teacher-forced oracle's rows / T
+    within the operand type's logit noise and exactly the output_logits rows / T (one correctly rounded fp32 division); a stopping criterion that
+    takes scores receives the same rows; output_logits keeps the rows before the warpers."""
+    cfg, w, model, U, oc = setup
+    grids = [[1, 10, 12], [1, 8, 8]]
+    grid, pix, ids, am = U.synthetic_batch(cfg, grids, n_pre=6, n_post=9, ragged=True, seed=77)
+    T, temp, K, P = 9, 0.7, 20, 0.9
+    kw = dict(input_ids=ids.cuda(), attention_mask=am.cuda(), pixel_values=pix.cuda(), image_grid_thw=grid, max_new_tokens=T,
+              do_sample=True, temperature=temp, top_k=K, top_p=P, seed=4321, repetition_penalty=1.0, eos_token_id=cfg.eos_token_id)
+    out = model.generate(output_scores=True, output_logits=True, **kw)
+    L, V, N = ids.shape[1], cfg.vocab_size, sum(g[1] * g[2] // 4 for g in grids)
+    n = len(out.scores)
+    assert n >= 1 and len(out.logits) == n
+    toks = out.sequences.cpu()[:, L:]
+    ores = U.O.generate(w, oc, ids, am, pix, grid, n, collect_logits=True, force_tokens=toks, repetition_penalty=1.0)
+    t32 = torch.tensor(temp, dtype=torch.float32).double()
+    live = torch.ones(2, dtype=torch.bool)
+    worst = 0.0
+    for t in range(n):
+        s, raw, o = out.scores[t].cpu(), out.logits[t].cpu(), ores["logits"][t]
+        assert s.shape == (2, V + N) and raw.shape == (2, V + N)
+        fin = torch.isfinite(s)
+        assert (fin.sum(dim=1) >= 1).all() and (fin.sum(dim=1) <= K).all(), f"step {t}: {fin.sum(dim=1).tolist()} finite entries"
+        assert torch.equal(torch.isfinite(raw), torch.isfinite(o)), f"step {t}: output_logits are not the rows before the warpers"
+        assert bool((fin <= torch.isfinite(o)).all())
+        assert torch.equal(s[fin], (raw[fin].double() / t32).float()), f"step {t}: scores are not output_logits / T"
+        for b in range(2):
+            if live[b]:
+                assert bool(fin[b, toks[b, t]]), f"step {t} row {b}: the drawn token is not in the warped row"
+                if int(toks[b, t]) == cfg.eos_token_id:
+                    live[b] = False
+        ref = o[fin].double() / temp
+        worst = max(worst, ((s[fin].double() - ref).abs().max() / ref.abs().max()).item())
+    print(f"\n[sampling scores, {model.dtype}] worst |score - oracle / T| / max|oracle / T| over {n} steps: {worst:.3e}")
+    assert worst < tol(model, 2e-2, 3e-3)                           # the logit noise bound of test_output_scores_are_the_oracles_processed_logits
+    # a stopping criterion that takes scores: the same rows (the hooked, eager loop draws what the captured graph drew)
+    got = []
+
+    def crit(input_ids, scores, **kwargs):
+        got.append(scores[-1].clone())
+        return torch.zeros(input_ids.shape[0], dtype=torch.bool, device=input_ids.device)
+    out2 = model.generate(output_scores=True, stopping_criteria=[crit], **kw)
+    assert torch.equal(out2.sequences, out.sequences) and len(got) == n
+    for t in range(n):
+        assert torch.equal(got[t], out.scores[t].to(got[t].device)) and torch.equal(out2.scores[t], out.scores[t])
+
+
 def test_generate_with_caller_logits_processors_and_stopping_criteria(setup):
     """padt.py:422-423,570-580,717,752 (round 6): caller-supplied `logits_processor` / `stopping_criteria` on the hooked decode loop.  (1) no-op hooks
     reproduce the captured-graph run bit for bit (sequences, scores, per-step hidden rows); (2) a processor's rows are what is selected from and what
