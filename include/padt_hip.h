@@ -68,8 +68,8 @@ int padt_gemm_resid32(void* stream, const void* A, long lda, const void* W, long
                       long ldxb, long M, long N, long K);
 /* Dispatch knobs of the 256-row tile kernel (tests force every tile variant; tools A/B them): mode256 0 off / 1 auto / 2 forced,
  * mf 0 auto / 2..4 tile height in 64-row units, peel 0 never / 1 cost model / 2 always, colsplit 0 never / 1 cost model / n columns,
- * group_m rasterisation patch height.  -1 keeps a field.  The defaults are read once from PADT_GEMM256 / PADT_GEMM_MF / PADT_GEMM_PEEL /
- * PADT_GEMM_COLSPLIT / PADT_GEMM_GROUP_M when the library loads.  Process-wide, not thread-safe (a test / tuning surface). */
+ * group_m rasterisation patch height.  -1 keeps a field.  Defaults: 1, 0, 1, 1, 8.  Process-wide, not thread-safe (a test / tuning
+ * surface). */
 int padt_gemm_knobs(int mode256, int mf, int peel, int colsplit, int group_m);
 /* Measurement surface (bench.py's in-situ roofline): while a slot array (capacity pairs of uint64, initialised to {~0, 0} by the caller) is
  * registered, every tile-GEMM call (M > 64) takes the next slot and its kernels record {first block start, last block end} in 100 MHz

@@ -1137,10 +1137,8 @@ extern "C" int PADT_TWIN(padt_decode_attn_rope)(void* stream, const void* qkv, l
         DecodePackedArgs pa{(const x16_t*)qkv, ld_qkv, (const float*)rope_cs, slot, (x16_t*)k_cache, (x16_t*)vt_cache, (x16_t*)out,
                             batch, n_heads, n_kv_heads, s_max, scale * 1.4426950408889634f, out_packed};
         // two blocks per (kv head, sample) while one block each would leave half of the chip without a KV stream (decode_attn_rope_packed_kernel, DS);
-        // cache_packed = 2 / 3 or PADT_DECODE_ATTN_DSPLIT = 0 / 1 force the choice (tests, A/B)
-        static const int env = getenv("PADT_DECODE_ATTN_DSPLIT") ? atoi(getenv("PADT_DECODE_ATTN_DSPLIT")) : -1;
-        const int force = cache_packed == 2 ? 0 : (cache_packed == 3 ? 1 : env);
-        const bool dsplit = force >= 0 ? force != 0 : (long)n_kv_heads * batch <= 128;
+        // cache_packed = 2 / 3 force one / two blocks (tests, tools/bench_kernels.py)
+        const bool dsplit = cache_packed == 2 ? false : (cache_packed == 3 ? true : (long)n_kv_heads * batch <= 128);
         if (dsplit) hipLaunchKernelGGL((decode_attn_rope_packed_kernel<128, NW, true, 2>), dim3(n_kv_heads, batch, 2), dim3(NW * 64), lds, (hipStream_t)stream, pa);
         else hipLaunchKernelGGL((decode_attn_rope_packed_kernel<128, NW, true, 1>), dim3(n_kv_heads, batch), dim3(NW * 64), lds, (hipStream_t)stream, pa);
         hipError_t e = hipGetLastError();

@@ -617,13 +617,12 @@ static void launch_skinny_nt(const GemmArgs& a, float eps, hipStream_t s) {
 // K-step → wave map nor the cross-wave summation order, so every output bit is the narrow launch's (NW comes from the narrow block count).
 // Taken only where the halved grid still covers the chip (>= 256 blocks); measured and NOT taken: 128 rows (NT x MT = 32 accumulator
 // fragments: one wave per SIMD, 42.5 → 47.7 us), qkv / o (80 / 64 blocks left: 8.9 → 10.5, 7.6 → 10.9 us), 4 K-step pairs in flight (24.9 us);
-// down with twice the split: 20.3 → 19.7 us, not worth a different split at 8 rows.  PADT_SKINNY_WIDE=0 is the A/B switch.
+// down with twice the split: 20.3 → 19.7 us, not worth a different split at 8 rows.
 template <int MT, int NW, int EPI, bool F32, bool NORM, bool PACKED = false, int WQ = 0>
 static void launch_skinny_nw(const GemmArgs& a, float eps, hipStream_t s) {
     constexpr int NT = (EPI == EPI_SWIGLU) ? 2 : 1;
     if constexpr (PACKED && MT == 4 && EPI == EPI_SWIGLU && NW == 4) {
-        static const int wide = getenv("PADT_SKINNY_WIDE") ? atoi(getenv("PADT_SKINNY_WIDE")) : 1;
-        if (wide && a.N % (32 * NT) == 0 && a.N / (32 * NT) >= 256) {
+        if (a.N % (32 * NT) == 0 && a.N / (32 * NT) >= 256) {
             launch_skinny_nt<MT, 2 * NT, NW, EPI, F32, NORM, PACKED, WQ>(a, eps, s);
             return;
         }

@@ -19,13 +19,11 @@
 #include <stdlib.h>
 #include <type_traits>
 
-// Dispatch knobs (tests force every tile variant): read from the environment ONCE when the library is loaded; tests and tools that A/B a
-// variant inside one process call padt_gemm_knobs() instead.  -1 keeps a field.  ONE object for both operand-type instantiations.
+// Dispatch knobs: constant defaults; tests and tools that force a tile variant inside one process call padt_gemm_knobs().  -1 keeps a
+// field.  ONE object for both operand-type instantiations.
 struct Knobs256 { int mode, mf, peel, colsplit, group_m; };
 #if !PADT_OP16_F16
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-Knobs256 padt_g_knobs256 = {env_int("PADT_GEMM256", 1), env_int("PADT_GEMM_MF", 0), env_int("PADT_GEMM_PEEL", 1), env_int("PADT_GEMM_COLSPLIT", 1),
-                            env_int("PADT_GEMM_GROUP_M", 8)};
+Knobs256 padt_g_knobs256 = {1, 0, 1, 1, 8};
 extern "C" int padt_gemm_knobs(int mode256, int mf, int peel, int colsplit, int group_m) {
     if (mode256 >= 0) padt_g_knobs256.mode = mode256;
     if (mf >= 0) padt_g_knobs256.mf = mf;

@@ -148,9 +148,8 @@ class DecodeSession:
         # KV caches, one pair per layer.  head_dim 128 (PaDT_Pro_3B / 7B): the FRAGMENT-PACKED images of padt_decode_attn_rope (K
         # [S/16][D/32][64 lanes][8], V^T [D/16][S/32][64 lanes][8]: 1 KiB contiguous per wave-wide load) read by the one-launch decode
         # attention and written in place by the prompt pass (llm_qkv_post) and the decode step's append; otherwise row-major K / transposed V
-        # with the two-launch split attention.  PADT_KV_PACKED=0 keeps the row-major form for A/B runs.
-        import os
-        self.cache_packed = hd == 128 and cfg.num_attention_heads // Hkv <= 16 and os.environ.get("PADT_KV_PACKED", "1") != "0"
+        # with the two-launch split attention.
+        self.cache_packed = hd == 128 and cfg.num_attention_heads // Hkv <= 16
         self.kc = [z(B, Hkv, s_max, hd) for _ in range(nl)]
         self.vtc = [z(B, Hkv, hd, s_max) for _ in range(nl)]
         self.proto = z(np_max, D)
@@ -176,12 +175,12 @@ class DecodeSession:
         assert self.inv_freq.numel() == half
         # decode-step activations (static addresses → graph-replayable)
         # x / att / h are in the 16-row fragment-packed activation layout (include/padt_hip.h): every projection reads its
-        # input fragments as 1 KiB contiguous wave loads; x_rm is the row-major copy at the two ends of the layer loop
+        # input fragments as 1 KiB contiguous wave loads; x_rm is the row-major copy the step's token embeddings land in
         I = W.llm_ipad
         B16 = (B + 15) // 16 * 16
         self.x = z(B16, D)
         self.x_rm = z(B, D)
-        self.x32 = z(B, D, dt=torch.float32) if W.resid_f32 else None     # fp32 residual stream of the decode step (x is its packed bf16 mirror)
+        self.x32 = z(B, D, dt=torch.float32)     # fp32 residual stream of the decode step (x is its packed 16-bit mirror)
         self.n = z(B, D)
         self.qkv = z(B, (cfg.num_attention_heads + 2 * Hkv) * hd)
         self.q = z(B, cfg.num_attention_heads * hd)
@@ -219,59 +218,30 @@ class DecodeSession:
         Hq, Hkv, hd, D = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim, cfg.hidden_size
         B = self.B
         ops.embed_tokens(self.cur_tok, None, W["llm.embed"], self.proto, None, out=self.x_rm, err_flag=self.err)
-        f32 = self.x32 is not None
-        sc = ops.stream_scale(W.op16) if f32 else 1.0
-        eps_n = W.eps_m(cfg.rms_norm_eps) if f32 else cfg.rms_norm_eps       # the fused norms read the (scaled) stream mirror
-        if f32:
-            ops.cast_x16_f32(self.x_rm, out=self.x32)
-            if sc != 1.0:                                                     # first mirror of the step's stream: X(scale * x32)
-                ops.cast_f32_x16(self.x32, out=self.x_rm, scale=sc)
+        sc = ops.stream_scale(W.op16)
+        eps_n = W.eps_m(cfg.rms_norm_eps)                                    # the fused norms read the (scaled) stream mirror
+        ops.cast_x16_f32(self.x_rm, out=self.x32)
+        if sc != 1.0:                                                         # first mirror of the step's stream: X(scale * x32)
+            ops.cast_f32_x16(self.x32, out=self.x_rm, scale=sc)
         ops.pack_rows(self.x_rm, self.x, B, to_packed=True)
         ops.rope_table(self.pos3, self.inv_freq, self.rope_cs, hd, cfg.mrope_section)
+        fp8 = W.llm_weights == "fp8"                              # fp8 weight images (+ per-row scales): half the bytes per step
+        wk = ".wq" if fp8 else ".wp"
+        ws = (lambda m: W[m + ".ws"]) if fp8 else (lambda m: None)
         for i in range(cfg.num_hidden_layers):
             p = f"llm.{i}."
             # 6 launches per layer: [norm+qkv] [rope+append+split attention] [merge] [o+resid] [norm+gate/up+SwiGLU] [down+resid]
-            if W.llm_weights == "fp8":                            # fp8 weight images (+ per-row scales): half the bytes per step
-                ops.gemm_packed_fp8(self.x, W[p + "qkv.wq"], W[p + "qkv.ws"], self.n_qkv, W[p + "qkv.b"], out=self.qkv,
-                                    norm_eps=eps_n, a_packed=True, rows=B)
-                ops.decode_attn_rope(self.qkv, self.rope_cs, self.slot, self.kc[i], self.vtc[i], self.att, self.attn_ws, Hq, Hkv,
-                                     hd, self.s_max, self.s_max, out_packed=True, cache_packed=self.cache_packed)
-                if f32:
-                    ops.gemm_packed_resid32(self.att, W[p + "o.wq"], D, self.x32, self.x, scales=W[p + "o.ws"], split_k=self.o_split,
-                                            workspace=self.splitk_ws, rows=B)
-                else:
-                    ops.gemm_packed_fp8(self.att, W[p + "o.wq"], W[p + "o.ws"], D, out=self.x, epilogue=ops.EPI_RESID, residual=self.x,
-                                        split_k=self.o_split, workspace=self.splitk_ws, a_packed=True, c_packed=True, rows=B)
-                ops.gemm_packed_fp8(self.x, W[p + "gu.wq"], W[p + "gu.ws"], 2 * W.llm_ipad, out=self.h, epilogue=ops.EPI_SWIGLU,
-                                    norm_eps=eps_n, a_packed=True, c_packed=True, rows=B)
-                if f32:
-                    ops.gemm_packed_resid32(self.h, W[p + "down.wq"], D, self.x32, self.x, scales=W[p + "down.ws"], split_k=self.down_split,
-                                            workspace=self.splitk_ws, rows=B)
-                else:
-                    ops.gemm_packed_fp8(self.h, W[p + "down.wq"], W[p + "down.ws"], D, out=self.x, epilogue=ops.EPI_RESID, residual=self.x,
-                                        split_k=self.down_split, workspace=self.splitk_ws, a_packed=True, c_packed=True, rows=B)
-                continue
-            ops.gemm_packed(self.x, W[p + "qkv.wp"], self.n_qkv, W[p + "qkv.b"], out=self.qkv, norm_eps=eps_n,
-                            a_packed=True, rows=B)
+            ops.gemm_packed(self.x, W[p + "qkv" + wk], self.n_qkv, W[p + "qkv.b"], out=self.qkv, norm_eps=eps_n, a_packed=True, rows=B,
+                            scales=ws(p + "qkv"))
             ops.decode_attn_rope(self.qkv, self.rope_cs, self.slot, self.kc[i], self.vtc[i], self.att, self.attn_ws, Hq, Hkv,
                                  hd, self.s_max, self.s_max, out_packed=True, cache_packed=self.cache_packed)
-            if f32:
-                ops.gemm_packed_resid32(self.att, W[p + "o.wp"], D, self.x32, self.x, split_k=self.o_split, workspace=self.splitk_ws, rows=B)
-            else:
-                ops.gemm_packed(self.att, W[p + "o.wp"], D, out=self.x, epilogue=ops.EPI_RESID, residual=self.x,
-                                split_k=self.o_split, workspace=self.splitk_ws, a_packed=True, c_packed=True, rows=B)
-            ops.gemm_packed(self.x, W[p + "gu.wp"], 2 * W.llm_ipad, out=self.h, epilogue=ops.EPI_SWIGLU, norm_eps=eps_n,
-                            a_packed=True, c_packed=True, rows=B)
-            if f32:
-                ops.gemm_packed_resid32(self.h, W[p + "down.wp"], D, self.x32, self.x, split_k=self.down_split, workspace=self.splitk_ws, rows=B)
-            else:
-                ops.gemm_packed(self.h, W[p + "down.wp"], D, out=self.x, epilogue=ops.EPI_RESID, residual=self.x,
-                                split_k=self.down_split, workspace=self.splitk_ws, a_packed=True, c_packed=True, rows=B)
-        if f32:
-            ops.rmsnorm_f32(self.x32, W["llm.norm"], out=self.hn, eps=cfg.rms_norm_eps)
-        else:
-            ops.pack_rows(self.x, self.x_rm, B, to_packed=False)
-            ops.rmsnorm(self.x_rm, W["llm.norm"], out=self.hn, eps=cfg.rms_norm_eps)
+            ops.gemm_packed_resid32(self.att, W[p + "o" + wk], D, self.x32, self.x, scales=ws(p + "o"), split_k=self.o_split,
+                                    workspace=self.splitk_ws, rows=B)
+            ops.gemm_packed(self.x, W[p + "gu" + wk], 2 * W.llm_ipad, out=self.h, epilogue=ops.EPI_SWIGLU, norm_eps=eps_n,
+                            a_packed=True, c_packed=True, rows=B, scales=ws(p + "gu"))
+            ops.gemm_packed_resid32(self.h, W[p + "down" + wk], D, self.x32, self.x, scales=ws(p + "down"), split_k=self.down_split,
+                                    workspace=self.splitk_ws, rows=B)
+        ops.rmsnorm_f32(self.x32, W["llm.norm"], out=self.hn, eps=cfg.rms_norm_eps)
         ops.check_finite(self.hn, self.nf, rows_per_flag=1, rows=B)      # sticky per-row flag, read once per generate (modeling.generate_collect)
         self.head_and_select(self.hn, advance=True)
 
@@ -411,9 +381,9 @@ class LanguageModel:
         dev = image_embeds.device
         bf = W.op16
         x = ops.embed_tokens(plan.ids, plan.img_index, W["llm.embed"], sess.proto, image_embeds, err_flag=sess.err)
-        x32 = ops.cast_x16_f32(x) if W.resid_f32 else None       # fp32 residual stream; x stays its 16-bit mirror
-        eps_n = W.eps_m(cfg.rms_norm_eps) if x32 is not None else cfg.rms_norm_eps
-        if x32 is not None and ops.stream_scale(bf) != 1.0:
+        x32 = ops.cast_x16_f32(x)                                # fp32 residual stream; x stays its 16-bit mirror
+        eps_n = W.eps_m(cfg.rms_norm_eps)
+        if ops.stream_scale(bf) != 1.0:
             ops.cast_f32_x16(x32, out=x, scale=ops.stream_scale(bf))           # mirrors hold X(scale * x32) (fp16: 2^-4, see ops.stream_scale)
         n = torch.empty_like(x)
         rstd = torch.empty((T,), device=dev, dtype=torch.float32)
@@ -423,7 +393,7 @@ class LanguageModel:
         att = torch.empty((T, Hq * hd), device=dev, dtype=bf)
         h = torch.empty((T, W.llm_ipad), device=dev, dtype=bf)
         mx = max(plan.lens)
-        f8 = W.fp8_prefill and x32 is not None
+        f8 = W.fp8_prefill
         if f8:                                                       # e4m3 images of the three GEMM inputs of a layer + their row scales
             x8 = torch.empty((T, cfg.hidden_size), device=dev, dtype=torch.uint8)
             a8 = torch.empty((T, Hq * hd), device=dev, dtype=torch.uint8)
@@ -445,10 +415,8 @@ class LanguageModel:
             if f8 and (p + "o.w8") in W:
                 ops.quant_rows_fp8(att, out=a8, rs=rs8)
                 ops.gemm_fp8(a8, W[p + "o.w8"], W[p + "o.ws"], rs8, epilogue=ops.EPI_RESID, x32=x32, xb=x)
-            elif x32 is not None:
-                ops.gemm_resid32(att, W[p + "o.w"], None, x32, x)
             else:
-                ops.gemm(att, W[p + "o.w"], out=x, epilogue=ops.EPI_RESID, residual=x)
+                ops.gemm_resid32(att, W[p + "o.w"], None, x32, x)
             if f8 and (p + "gu.w8") in W:
                 ops.quant_rows_fp8(x, norm_eps=eps_n, out=x8, rs=rs8)
                 ops.gemm_fp8(x8, W[p + "gu.w8"], W[p + "gu.ws"], rs8, out=h, epilogue=ops.EPI_SWIGLU)
@@ -458,14 +426,9 @@ class LanguageModel:
             if f8 and (p + "down.w8") in W:
                 ops.quant_rows_fp8(h, out=h8, rs=rs8)
                 ops.gemm_fp8(h8, W[p + "down.w8"], W[p + "down.ws"], rs8, epilogue=ops.EPI_RESID, x32=x32, xb=x)
-            elif x32 is not None:
-                ops.gemm_resid32(h, W[p + "down.w"], None, x32, x)
             else:
-                ops.gemm(h, W[p + "down.w"], out=x, epilogue=ops.EPI_RESID, residual=x)
-        if x32 is not None:
-            ops.rmsnorm_f32(x32, W["llm.norm"], out=n, eps=cfg.rms_norm_eps)
-        else:
-            ops.rmsnorm(x, W["llm.norm"], out=n, eps=cfg.rms_norm_eps)
+                ops.gemm_resid32(h, W[p + "down.w"], None, x32, x)
+        ops.rmsnorm_f32(x32, W["llm.norm"], out=n, eps=cfg.rms_norm_eps)
         if nf is not None:
             ops.check_finite(n, nf)
         return n

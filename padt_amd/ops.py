@@ -301,24 +301,6 @@ def pack_weight_fp8(wq):
     return wq.view(Np // 16, 16, Kp // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5).contiguous().view(Np, Kp)
 
 
-def gemm_packed_fp8(a, wq_packed, scales, n, bias=None, out=None, epilogue=EPI_NONE, residual=None, norm_eps=None, split_k=1, workspace=None,
-                    a_packed=False, c_packed=False, rows=None):
-    """gemm_packed over fp8 weights: out = epi(rstd?(a) * scales[n] * (a @ wq^T) + bias)."""
-    dt = _x16(a, bias, residual, out)
-    assert wq_packed.dtype == torch.uint8 and scales.dtype == torch.float32 and scales.is_contiguous()
-    M, K = a.shape
-    if rows is not None:
-        M = rows
-    n_out = n // 2 if epilogue == EPI_SWIGLU else n
-    if out is None:
-        out = torch.empty((M, n_out), device=a.device, dtype=dt)
-    _lib.check(_fn("padt_gemm_packed_fp8", dt)(_stream(), _p(a), a.stride(0), _p(wq_packed), wq_packed.shape[1], _p(scales), _p(bias), _p(out),
-                                        out.stride(0), _p(residual), residual.stride(0) if residual is not None else 0, M, n, K, epilogue,
-                                        -1.0 if norm_eps is None else float(norm_eps), int(split_k), _p(workspace),
-                                        (1 if a_packed else 0) | (2 if c_packed else 0)), "padt_gemm_packed_fp8")
-    return out
-
-
 def new_splitk_workspace(n, split_k, device):
     """Zero-initialised split-K workspace (ticket header must start at zero), one per concurrently decoding stream."""
     return torch.zeros(_lib.load().padt_gemm_splitk_workspace(n, split_k), dtype=torch.uint8, device=device)
@@ -333,21 +315,32 @@ def pack_rows(src, dst, M, to_packed=True):
 
 
 def gemm_packed(a, wp, n, bias=None, out=None, epilogue=EPI_NONE, residual=None, norm_eps=None, split_k=1, workspace=None,
-                a_packed=False, c_packed=False, rows=None):
+                a_packed=False, c_packed=False, rows=None, scales=None):
     """Decode-step projection over a pack_weight() image (rows <= 128): out = epi(rstd?(a) * (a @ w^T) + bias).
-    a_packed / c_packed: a / (out and residual) are fragment-packed activation buffers holding `rows` valid rows."""
-    dt = _x16(a, wp, bias, residual, out)
+    a_packed / c_packed: a / (out and residual) are fragment-packed activation buffers holding `rows` valid rows.
+    scales given: wp is the fp8 image (pack_weight_fp8) and out = epi(rstd?(a) * scales[n] * (a @ wq^T) + bias)."""
+    if scales is None:
+        dt, name = _x16(a, wp, bias, residual, out), "padt_gemm_packed_bf16"
+    else:
+        assert wp.dtype == torch.uint8 and scales.dtype == torch.float32 and scales.is_contiguous()
+        dt, name = _x16(a, bias, residual, out), "padt_gemm_packed_fp8"
     M, K = a.shape
     if rows is not None:
         M = rows
     n_out = n // 2 if epilogue == EPI_SWIGLU else n
     if out is None:
         out = torch.empty((M, n_out), device=a.device, dtype=dt)
-    _lib.check(_fn("padt_gemm_packed_bf16", dt)(_stream(), _p(a), a.stride(0), _p(wp), wp.shape[1], _p(bias), _p(out), out.stride(0),
-                                         _p(residual), residual.stride(0) if residual is not None else 0, M, n, K, epilogue,
-                                         -1.0 if norm_eps is None else float(norm_eps), int(split_k), _p(workspace),
-                                         (1 if a_packed else 0) | (2 if c_packed else 0)), "padt_gemm_packed_bf16")
+    sc = () if scales is None else (_p(scales),)
+    _lib.check(_fn(name, dt)(_stream(), _p(a), a.stride(0), _p(wp), wp.shape[1], *sc, _p(bias), _p(out), out.stride(0),
+                             _p(residual), residual.stride(0) if residual is not None else 0, M, n, K, epilogue,
+                             -1.0 if norm_eps is None else float(norm_eps), int(split_k), _p(workspace),
+                             (1 if a_packed else 0) | (2 if c_packed else 0)), name)
     return out
+
+
+def gemm_packed_fp8(a, wq_packed, scales, n, *args, **kw):
+    """gemm_packed over an fp8 image (pack_weight_fp8) and its per-row scales."""
+    return gemm_packed(a, wq_packed, n, *args, scales=scales, **kw)
 
 
 def gemm_packed_resid32(a, wp, n, x32, xb_packed, scales=None, split_k=1, workspace=None, a_packed=True, rows=None):

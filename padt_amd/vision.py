@@ -92,11 +92,10 @@ class VisionEncoder:
             torch.cuda.current_stream().synchronize()        # tables are shared by every stream that runs this grid later
         return self._plans[key]
 
-    def block(self, i: int, x, plan: VisionPlan, rstd, qkv, att, hbuf, force_full=None, x32=None):
-        """One ViT block in place on x (P, vh): x += proj(attn(rope(qkv(RMSNorm(x))))); x += down(SwiGLU(RMSNorm(x)))
-        (HF:297-321).  Window segments except for the full-attention layers (padt.py:89-93).
-        x32 given: the residual stream is the fp32 tensor x32, updated in place by the residual GEMMs' epilogues, and x is its bf16
-        mirror (the A operand of the qkv / gate-up GEMMs), rewritten by the same epilogues."""
+    def block(self, i: int, x, plan: VisionPlan, rstd, qkv, att, hbuf, x32, force_full=None):
+        """One ViT block in place on the fp32 residual stream x32 (P, vh): x32 += proj(attn(rope(qkv(RMSNorm(x32)))));
+        x32 += down(SwiGLU(RMSNorm(x32))) (HF:297-321).  Window segments except for the full-attention layers (padt.py:89-93).
+        x is the stream's 16-bit mirror (the A operand of the qkv / gate-up GEMMs), rewritten by the residual GEMMs' epilogues."""
         cfg, W = self.cfg, self.W
         v = cfg.vision_config
         vh, H = v.hidden_size, v.num_heads
@@ -104,7 +103,7 @@ class VisionEncoder:
         p = f"vit.{i}."
         full = (i in v.fullatt_block_indexes) if force_full is None else force_full
         cu, mx = (plan.cu_full, plan.max_full) if full else (plan.cu_win, plan.max_win)
-        eps = W.eps_m(1e-6) if x32 is not None else 1e-6                   # x is the (scaled) mirror of x32: rstd comes out as rstd / scale
+        eps = W.eps_m(1e-6)                                                # x is the (scaled) mirror of x32: rstd comes out as rstd / scale
         ops.row_rstd(x, eps=eps, out=rstd)                                 # RMSNorm = rstd x (weight folded into qkv.w)
         # qkv projection with the rotary embedding applied in its epilogue (q / k columns are pair-interleaved per head by
         # prepare_weights): no separate pass over q and k
@@ -114,16 +113,10 @@ class VisionEncoder:
             ops.gemm(x, W[p + "qkv.w"], W[p + "qkv.b"], out=qkv, row_scale=rstd)
             ops.rope_half_(qkv, plan.cos, plan.sin, 2 * H, hd)
         ops.attn_varlen(qkv[:, :vh], qkv[:, vh:2 * vh], qkv[:, 2 * vh:], att, cu, cu, mx, H, H, hd)
-        if x32 is not None:
-            ops.gemm_resid32(att, W[p + "proj.w"], W[p + "proj.b"], x32, x)
-        else:
-            ops.gemm(att, W[p + "proj.w"], W[p + "proj.b"], out=x, epilogue=ops.EPI_RESID, residual=x)
+        ops.gemm_resid32(att, W[p + "proj.w"], W[p + "proj.b"], x32, x)
         ops.row_rstd(x, eps=eps, out=rstd)
         ops.gemm(x, W[p + "gu.w"], W[p + "gu.b"], out=hbuf, epilogue=ops.EPI_SWIGLU, row_scale=rstd)
-        if x32 is not None:
-            ops.gemm_resid32(hbuf, W[p + "down.w"], W[p + "down.b"], x32, x)
-        else:
-            ops.gemm(hbuf, W[p + "down.w"], W[p + "down.b"], out=x, epilogue=ops.EPI_RESID, residual=x)
+        ops.gemm_resid32(hbuf, W[p + "down.w"], W[p + "down.b"], x32, x)
 
     def __call__(self, pixel_values: torch.Tensor, grid_thw: torch.Tensor, proto_out=None, nf=None):
         """pixel_values (P, C*T*p*p) fp32 / bf16 / fp16 on device → (image_embeds (N,D), high_res (P,vh), (cos,sin) (P,hd)).
@@ -142,29 +135,20 @@ class VisionEncoder:
             pix = ops.cast_f32_x16(pixel_values.contiguous(), dtype=op16)
         else:                                                                  # the other 16-bit type: through fp32 (exact), one rounding
             pix = ops.cast_f32_x16(ops.cast_x16_f32(pixel_values.contiguous()), dtype=op16)
-        f32 = W.resid_f32
-        x0 = ops.gemm(pix, W["vit.patch_embed"], out_f32=f32)                  # conv3d-as-GEMM (HF:116-122)
-        x32 = None
-        if f32:                                                                # fp32 residual stream + its bf16 mirror
-            x32 = ops.gather_rows(x0, plan.patch_perm)                         # window order
-            x = ops.cast_f32_x16(x32, dtype=op16, scale=ops.stream_scale(op16))   # the stream's first mirror
-        else:
-            x = ops.gather_rows(x0, plan.patch_perm)
+        x0 = ops.gemm(pix, W["vit.patch_embed"], out_f32=True)                 # conv3d-as-GEMM (HF:116-122)
+        x32 = ops.gather_rows(x0, plan.patch_perm)                             # the fp32 residual stream, window order
+        x = ops.cast_f32_x16(x32, dtype=op16, scale=ops.stream_scale(op16))    # its first 16-bit mirror
         n = torch.empty_like(x)
         rstd = torch.empty((P,), device=x.device, dtype=torch.float32)
         qkv = torch.empty((P, 3 * vh), device=x.device, dtype=x.dtype)
         att = torch.empty_like(x)
         hbuf = torch.empty((P, W.vit_ipad), device=x.device, dtype=x.dtype)
         for i in range(v.depth):
-            self.block(i, x, plan, rstd, qkv, att, hbuf, x32=x32)
-        high = x32 if f32 else x                                               # the PaDT decoder reads fp32 or bf16 rows
+            self.block(i, x, plan, rstd, qkv, att, hbuf, x32)
         if nf is not None:                                                     # inf / NaN of any block is absorbing in the residual stream
-            ops.check_finite(high, nf)
-        if f32:
-            ops.rmsnorm_f32(x32, W["vit.merger.ln_q"], out=n)
-        else:
-            ops.rmsnorm(x, W["vit.merger.ln_q"], out=n)
+            ops.check_finite(x32, nf)
+        ops.rmsnorm_f32(x32, W["vit.merger.ln_q"], out=n)
         m = ops.gemm(n.view(plan.N, vh * cfg.merge_unit), W["vit.merger.0.w"], W["vit.merger.0.b"], epilogue=ops.EPI_GELU)
         low_win = ops.gemm(m, W["vit.merger.2.w"], W["vit.merger.2.b"])
         low = ops.gather_rows(low_win, plan.reverse)                           # raster order (padt.py:103-104)
-        return low, high, (plan.cos.clone(), plan.sin.clone())     # the caller owns past_visual_pe (plan tables are cached)
+        return low, x32, (plan.cos.clone(), plan.sin.clone())     # the caller owns past_visual_pe (plan tables are cached)

@@ -212,7 +212,6 @@ class PreparedWeights(dict):
     dec_ipad: int
     dec_hp: bool = False
     llm_weights: str = "bf16"
-    resid_f32: bool = True
     fp8_prefill: bool = False
     op16: torch.dtype = torch.bfloat16
 
@@ -241,18 +240,12 @@ def prepare_weights(sd: Dict[str, torch.Tensor], cfg: PaDTConfig, device="cuda",
         raise ValueError("operands must be 'fp16' or 'bf16'")
     dev = torch.device(device)
     W = PreparedWeights()
-    fp8_act = llm_weights == "fp8+act" or (llm_weights == "fp8" and os.environ.get("PADT_FP8_PREFILL", "0") == "1")
+    # "fp8+act": at prompt length the LLM projections run as fp8 x fp8 MFMA GEMMs (activation rows quantised to e4m3 on the fly,
+    # v_mfma_f32_16x16x128_f8f6f4) wherever the shape allows
+    W.fp8_prefill = llm_weights == "fp8+act"
     llm_weights = "fp8" if llm_weights == "fp8+act" else llm_weights
     W.llm_weights = llm_weights
-    # fp32 residual streams in the ViT and the LLM (default; PADT_RESID_F32=0 keeps the round-2 bf16 streams for A/B runs): the
-    # residual GEMMs' epilogues update an fp32 stream in place and emit its bf16 mirror for the next projection
-    W.resid_f32 = os.environ.get("PADT_RESID_F32", "1") != "0"
-    if operands == "fp16" and not W.resid_f32:
-        raise ValueError("fp16 operands need the fp32 residual streams (PADT_RESID_F32=0 is a bf16-only A/B switch)")
     W.op16 = torch.float16 if operands == "fp16" else BF16
-    # "fp8+act": at prompt length the LLM projections run as fp8 x fp8 MFMA GEMMs (activation rows quantised to e4m3 on the fly,
-    # v_mfma_f32_16x16x128_f8f6f4) wherever the shape allows.  Needs the fp32 residual streams.
-    W.fp8_prefill = llm_weights == "fp8" and W.resid_f32 and fp8_act
     op16 = W.op16
 
     out_of_range = []                                       # (name, device bool): fp16 images holding inf / NaN, read back once at the end

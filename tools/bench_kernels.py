@@ -74,11 +74,11 @@ def main():
                     ops.gemm_rmsnorm(a, w, out=out, epilogue=epi)
             elif fp8:
                 if epi == 2:
-                    ops.gemm_packed_fp8(a_pk, w, sc, N, out=out_pk, epilogue=2, residual=out_pk, split_k=split, workspace=ws_split,
-                                        a_packed=True, c_packed=True, rows=B)
+                    ops.gemm_packed(a_pk, w, N, out=out_pk, epilogue=2, residual=out_pk, split_k=split, workspace=ws_split,
+                                    a_packed=True, c_packed=True, rows=B, scales=sc)
                 else:
-                    ops.gemm_packed_fp8(a_pk, w, sc, N, out=out_pk if epi == 3 else out, epilogue=epi, norm_eps=1e-6, a_packed=True,
-                                        c_packed=(epi == 3), rows=B)
+                    ops.gemm_packed(a_pk, w, N, out=out_pk if epi == 3 else out, epilogue=epi, norm_eps=1e-6, a_packed=True,
+                                    c_packed=(epi == 3), rows=B, scales=sc)
             elif os.environ.get("PACK"):                          # fragment-packed activations, as the decode step runs them
                 if epi == 2:
                     ops.gemm_packed(a_pk, w, N, out=out_pk, epilogue=2, residual=out_pk, split_k=split, workspace=ws_split,
@@ -99,7 +99,7 @@ def main():
     Hq, Hkv, D, S_max = 16, 2, 128, 640
     qkv = torch.randn(B, (Hq + 2 * Hkv) * D, device="cuda").to(BF)
     nkv = int(os.environ.get("ROTKV", 8))                         # rotating cache sets: > the 256 MB Infinity Cache at 64 rows
-    kvp = bool(os.environ.get("KVP"))                              # KVP=1: fragment-packed caches → the one-launch kernel (what the decode step runs)
+    kvp = int(os.environ.get("KVP", 0))        # KVP=1: fragment-packed caches → the one-launch kernel (what the decode step runs); 2 / 3 force 1 / 2 blocks
     kcs = [torch.randn(B, Hkv, S_max, D, device="cuda").to(BF) for _ in range(nkv)]
     vts = [torch.randn(B, Hkv, D, S_max, device="cuda").to(BF) for _ in range(nkv)]
     if kvp:
