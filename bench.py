@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — images/s of PaDT_Pro_3B REC inference on MI355X (BASELINE.json metric), one process per GPU.
 
-  python bench.py [--gpus N --steps K --warmup W]         (N>1: one rank per GPU under torch.distributed.run — given as typed, the script
+  python bench.py [--gpus N --steps K --warmup W] [--full] (N>1: one rank per GPU under torch.distributed.run — given as typed, the script
                                                            launches itself under it as a child process; rank 0's JSON line is the only stdout line)
 
 A "step" = one batch of `--batch` (default 8) synthetic 640x640-equivalent images (grid [1,46,46], 2116 patches,
@@ -11,12 +11,15 @@ A "step" = one batch of `--batch` (default 8) synthetic 640x640-equivalent image
 Weights: random-init PaDT_Pro_3B architecture (3.85 B parameters, bf16 values; ViT / LLM multiply them as fp16 MFMA operands —
 `v_mfma_f32_16x16x32_f16`, the bf16 rate with 3 more mantissa bits; `--operands bf16` is the A/B variant).  Rank 0 prints ONE JSON line.
 The timed loops rotate 4 distinct input batches (a repeated batch would sit in the 256 MB Infinity Cache).
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line, nothing else; the side legs run with --full only
+(one GPU; a --no-* flag skips a single leg).
 Extra objects on that line (N=1): "roofline" (bf16 MFMA tile-GEMM family: in-kernel start / end stamps of every tile-GEMM call INSIDE the
 running pipeline — HIP-event pairs around 290 launches per step cost 10 % throughput and count the dispatch gaps; frac_replay = the same
 launches replayed alone between one event pair), "roofline_decode" (HBM bytes of a decode step / its in-situ and stand-alone
 duration), "from_images" (the same pipeline fed from uint8 host images), "cpu_baseline" (the fp32 CPU oracle timed on this host, with the
 parity read-out), "extra_workloads" (BASELINE configs[3] OVD and configs[4] 7B RIC fp8 per-GPU shapes, short runs), "steady_state" (64 steps of the
-same runner), "operands_bf16" (the bf16 instantiation, same steps), "reference_precision" (precision="reference": every float output within 1e-3).
+same runner), "unmerged_decode" (decode groups of one batch), "single_batch_latency", "to_rle" (the loop ending at COCO RLE records),
+"operands_bf16" (the bf16 instantiation, same steps), "reference_precision" (precision="reference": every float output within 1e-3).
 The synthetic workload (prompts, pixel rows, scripted schedules, tokenizer stand-in) ships with the package (padt_amd/synthetic.py), so every
 leg except `cpu_baseline` runs from an installed package; the CPU baseline needs the source checkout (oracle/ + tests/parity_util.py are test
 infrastructure, deliberately not shipped): without them that leg reports itself as skipped.
@@ -82,6 +85,9 @@ def parse_args():
                     "residual streams either way): auto (the product default: fp16 operands — 8x closer to the fp32 reference at the same rate — under "
                     "the device-side range guard, a flagged batch is re-run on bf16), fp16 (same guard, a flagged batch raises) or bf16")
     ap.add_argument("--cap", type=int, default=0, help="object capacity of the per-batch result record (default: 2 x the scheduled objects)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run every side leg (one GPU): steady state, unmerged decode, "
+                    "single-batch latency, rooflines, host-image and RLE legs, bf16 and reference-precision twins, CPU baseline with the parity "
+                    "read-out, OVD / 7B RIC workloads; the --no-* flags below skip single legs.  Without it the line carries the headline only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--merge", type=int, default=0, help="consecutive batches of 8 whose decode steps share one session (in-flight batching; "
@@ -845,11 +851,12 @@ def main():
     if args.dump_outputs and rank == 0:                                # the timed path's last step, before any side leg runs
         dump_outputs(decoded, args.dump_outputs)
 
-    side = not dist_on and rank == 0 and not args.no_alt
+    full = args.full and not dist_on and rank == 0                     # side legs: --full, one GPU
+    side = full and not args.no_alt
     # the same runner over 64 steps (8 decode groups): what the pipeline does once the fill / drain of the driver's 20-step window
-    # (2.5 groups: the last group's decode runs with nothing to overlap) is amortised — printed next to `value` so that the driver's clock covers it
+    # (2.5 groups: the last group's decode runs with nothing to overlap) is amortised
     steady = None
-    if not dist_on and rank == 0 and runner is not None and args.steady:
+    if full and runner is not None and args.steady:
         if args.steps >= 64:
             steady = {"value": round(args.batch * args.steps / elapsed, 3), "unit": "images/s", "steps": args.steps, "note": "the timed region itself"}
         else:
@@ -959,25 +966,25 @@ def main():
                 traceback.print_exc(file=sys.stderr)
                 line[key] = {"error": f"{type(e).__name__}: {e}"[:300]}
 
-        if not dist_on and not args.no_roofline and runner is not None:
+        if full and not args.no_roofline and runner is not None:
             def roofs():
                 roof, dec = insitu_leg(model, inp, args, cfg, run_steps, min(args.steps, 16))
                 roof.update(replay_leg(model, inp, args, cfg))
                 line["roofline_decode"] = decode_alone_leg(model, inp, args, cfg, dec)
                 return roof
             leg("roofline", roofs)
-        if not dist_on and args.bf16_twin and runner is not None and args.operands == "fp16" and args.extras:
+        if full and args.bf16_twin and runner is not None and args.operands == "fp16" and args.extras:
             leg("operands_bf16", lambda: bf16_twin_leg(cfg, args, grid_hw, device))
-        if not dist_on and args.extras and runner is not None and args.operands == "fp16":
+        if full and args.extras and runner is not None and args.operands == "fp16":
             leg("reference_precision", lambda: reference_precision_leg(cfg, args, grid_hw, device))
-        if not dist_on and args.from_images and runner is not None:
+        if full and args.from_images and runner is not None:
             leg("from_images", lambda: from_images_leg(model, inp, args, grid_hw, min(args.steps, 24)))
             leg("to_rle", lambda: to_rle_leg(model, inp, args, min(args.steps, 24)))
-        if not dist_on and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             leg("cpu_baseline", lambda: cpu_baseline_leg(cfg, args, inp, model))
         if isinstance(line.get("cpu_baseline"), dict) and "parity" in line["cpu_baseline"]:
             line["parity_vs_oracle"] = line["cpu_baseline"]["parity"]      # top level too: the metric's "box IoU vs ref" read-out of this run
-        if not dist_on and args.extras:
+        if full and args.extras:
             del runner
             m3, model = model, None
             leg("extra_workloads", lambda: extra_workloads(args, device, m3, cfg, grid_hw))

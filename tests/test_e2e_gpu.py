@@ -761,20 +761,32 @@ def test_fp8_llm_weights_against_oracle_on_dequantised_weights(llm_weights):
 
 
 def test_bench_contract_small_config():
-    """`python bench.py` prints ONE JSON line with the driver's contract fields, the roofline and cpu_baseline objects and the parity
-    read-out — exercised on the small plumbing config so that it runs in seconds (the numbers mean nothing at this size)."""
+    """`python bench.py` prints ONE JSON line with the result contract's fields and nothing measured beyond the timed region; with `--full`
+    the line also carries the roofline and cpu_baseline objects and the parity read-out — exercised on the small plumbing config so that
+    it runs in seconds (the numbers mean nothing at this size)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model", "small", "--steps", "3", "--warmup", "1"],
-                       capture_output=True, text=True, timeout=600, cwd=root)
-    assert r.returncode == 0, r.stderr[-2000:]
-    lines = [l for l in r.stdout.splitlines() if l.strip()]
-    assert len(lines) == 1, lines
-    d = json.loads(lines[0])
-    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
-              "data", "config", "roofline", "roofline_decode", "from_images", "to_rle", "cpu_baseline", "parity_vs_oracle", "steady_state", "range_guard"):
+    contract = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                "data", "config", "range_guard")
+    legs = ("roofline", "roofline_decode", "from_images", "to_rle", "cpu_baseline", "parity_vs_oracle", "steady_state", "unmerged_decode",
+            "single_batch_latency", "operands_bf16", "reference_precision", "extra_workloads")
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model", "small", "--steps", "3", "--warmup", "1", *extra],
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0])
+    d = run()
+    for k in contract:
+        assert k in d, k
+    assert not [k for k in legs if k in d], d.keys()
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and abs(d["ms_per_step"] * d["value"] / 1e3 - 8) < 0.05
+    d = run("--full")
+    for k in contract + ("roofline", "roofline_decode", "from_images", "to_rle", "cpu_baseline", "parity_vs_oracle", "steady_state"):
         assert k in d, k
     assert d["range_guard"]["operands_policy"] == "auto" and d["range_guard"]["batches_rerun_on_bf16"] == 0 and d["steady_state"]["value"] > 0
     assert d["cpu_baseline"]["cores"] == min(32, os.cpu_count() or 1)

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 LIGHT="--no-alt --no-cpu-baseline --no-extras --no-from-images"
 SEQ="python $REPO/bench.py --steps 1 --warmup 0 --depth 1 --merge 1 $LIGHT --no-roofline --no-graph"
 # (1) kernel trace of the pipelined bench; the bench line printed INSIDE this run carries roofline.frac measured under the profiler
-timeout 900 rocprofv3 --kernel-trace -d $OUT/prof_trace -o trace -- python $REPO/bench.py --steps 20 --warmup 5 $LIGHT > $OUT/prof_trace_line.json 2> $OUT/prof_trace.err
+timeout 900 rocprofv3 --kernel-trace -d $OUT/prof_trace -o trace -- python $REPO/bench.py --full --steps 20 --warmup 5 $LIGHT > $OUT/prof_trace_line.json 2> $OUT/prof_trace.err
 timeout 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/prof_fetch -o fetch -- $SEQ > $OUT/prof_fetch.log 2>&1
 timeout 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/prof_write -o write -- $SEQ > $OUT/prof_write.log 2>&1
 timeout 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $OUT/prof_mfma -o mfma -- $SEQ > $OUT/prof_mfma.log 2>&1
@@ -37,7 +37,7 @@ cd $REPO
 for rows in 64 128; do
   for k in fetch l2 tcp; do python tools/pmc_sum.py $OUT/prof_dec${rows}_$k gemm_skinny decode_attn decode_combine vrt_head greedy > $OUT/pmc_dec${rows}_$k.md 2>&1; done
 done
-timeout 1200 python bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err
+timeout 1200 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_line.err
 tail -c 600 $OUT/prof_trace_line.json; head -14 $OUT/kernel_stats.md; cat $OUT/pmc_mfma.md $OUT/pmc_lds.md | head -40
 # keep the merged-back payload small
 # keep the merged-back payload small (gpurun copies back at most 64 MiB, and refuses when the LOCAL gpurun_out/ already exceeds it)
