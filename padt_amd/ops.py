@@ -778,12 +778,13 @@ F32 = torch.float32
 OUT_NONE, OUT_F32, OUT_SPLIT = 0, 1, 2
 
 
-def gemm_hp(a_split, w2, bias=None, out=None, epilogue=EPI_NONE, residual=None, out_mode=OUT_F32, M=None, w_packed=None):
+def gemm_hp(a_split, w2, bias=None, out=None, epilogue=EPI_NONE, residual=None, out_mode=OUT_F32, M=None, w_packed=None, lo_off=None):
     """Split-precision GEMM (include/padt_hip.h "hp decoder"): a_split (M, 2K) bf16 rows [hi | lo], w2 (N, 2K) = [W | W].
     out_mode OUT_F32 → fp32 (M, N) [+ fp32 residual, in place allowed]; OUT_SPLIT → bf16 (M, 2N) rows [hi | lo]; epilogue EPI_SWIGLU (OUT_SPLIT only,
     weight rows [gate16 | up16]-interleaved) → bf16 (M, 2 * N/2) split rows of silu(gate) * up.
     w_packed (few rows only): the pack_weight() image of W — the rows are then packed too (one padt_pack_rows launch) so that every wave load of
-    either operand is 1 KiB contiguous (padt_gemm_split_rows, layout 3)."""
+    either operand is 1 KiB contiguous (padt_gemm_split_rows, layout 3).
+    lo_off (OUT_SPLIT only): column of `out` at which the lo half starts (default: right after the hi half; a multiple of 4, >= the hi width)."""
     lib = _lib.load()
     _chk_bf16(a_split, w2, bias)
     M = a_split.shape[0] if M is None else M
@@ -802,8 +803,8 @@ def gemm_hp(a_split, w2, bias=None, out=None, epilogue=EPI_NONE, residual=None, 
         assert residual is None and n_out % 4 == 0
         if out is None:
             out = torch.empty((M, 2 * n_out), device=a_split.device, dtype=BF16)
-        assert out.dtype == BF16 and out.shape[1] >= 2 * n_out
-        lo_off = n_out
+        lo_off = n_out if lo_off is None else int(lo_off)
+        assert out.dtype == BF16 and lo_off >= n_out and out.shape[1] >= lo_off + n_out
     if M <= 64 and K2 % 16 == 0 and ((out_mode == OUT_F32 and epilogue in (EPI_NONE, EPI_RESID)) or epilogue == EPI_SWIGLU):
         # few rows (a decode step): bound by the weight stream — read W once and multiply it with the hi and the lo fragments (padt_gemm_split_rows)
         K = K2 // 2

@@ -24,6 +24,7 @@ import math
 import pytest
 import torch
 
+from edge_util import same_bits
 from test_decoder_hp_gpu import join, split_close
 from test_kernels_f16_gpu import close_f16
 from test_kernels_gpu import close_bf16, ref_attn
@@ -59,13 +60,6 @@ def cum(lens):
 
 def i32(xs):
     return torch.tensor(xs, dtype=torch.int32, device="cuda")
-
-
-def same_bits(a, b):
-    a, b = a.contiguous(), b.contiguous()
-    if a.dtype == F32:
-        return torch.equal(a.view(torch.int32), b.view(torch.int32))
-    return torch.equal(a.view(torch.int16), b.view(torch.int16))
 
 
 def randn(g, *shape):
