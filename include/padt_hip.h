@@ -132,6 +132,19 @@ int padt_quant_rows_fp8(void* stream, const void* x, long ldx, void* x8, long ld
  * in the fragment-packed activation layout.  split_k / workspace as padt_gemm_packed_bf16. */
 int padt_gemm_packed_resid32(void* stream, const void* A, long lda, const void* Wp, long Kp, const void* scales, void* X32, long ldx,
                              void* Xb, long ldxb, long M, long N, long K, int split_k, void* workspace, int a_packed);
+/* padt_gemm_packed_bf16 / padt_gemm_packed_resid32 over MXFP4 weights (OCP microscaling: e2m1 codes {0, .5, 1, 1.5, 2, 3, 4, 6} with a sign
+ * bit, one E8M0 exponent per block of 32 consecutive K-elements of a weight row; 4.25 bits per weight).  Wq = the nibble image
+ * [N/16][Kp/64][64 lanes][8 B]: lane fq*16 + frow holds, for weight row n16*16 + frow, its 8 elements k = t*64 + fq*8 + j (j = 0..7, element
+ * j in nibble j of the first dword, low nibble first) of K-step 2t and then its 8 elements of K-step 2t + 1 — one wave load is 512 B.
+ * exps = E8M0 bytes [N/16][Kp/64][16 rows][2 K-steps], values in [1, 254] (scale 2^(byte - 127)).  Codes times 2^e are rebuilt in registers as
+ * 16-bit fragments (exact: v_cvt_scalef32_pk_{bf16,f16}_fp4), fp32 accumulation; the result equals, bit for bit, what the bf16 entry point
+ * computes on the fragment-packed 16-bit image of the dequantised matrix.  Kp % 64 == 0, N % 16 == 0, K % 32 == 0, exps 16-byte aligned;
+ * every other argument as in the entry point named first.  HF:727-757 at T = 1 with W ≈ code * 2^e. */
+int padt_gemm_packed_fp4(void* stream, const void* A, long lda, const void* Wq, long Kp, const void* exps, const void* bias, void* C,
+                         long ldc, const void* R, long ldr, long M, long N, long K, int epilogue, float norm_eps, int split_k,
+                         void* workspace, int act_packed);
+int padt_gemm_packed_resid32_fp4(void* stream, const void* A, long lda, const void* Wq, long Kp, const void* exps, void* X32, long ldx,
+                                 void* Xb, long ldxb, long M, long N, long K, int split_k, void* workspace, int a_packed);
 
 /* ---- attention ------------------------------------------------------------------------------------------------------
  * Varlen flash attention, fp32 online softmax, non-causal or causal (bottom-right aligned), GQA by head index.

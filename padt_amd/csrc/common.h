@@ -125,6 +125,24 @@ PADT_DEV x16x8 fp8x8_to_x16x8(unsigned lo, unsigned hi) {
     return __builtin_bit_cast(x16x8, r);
 }
 
+// 8 OCP e2m1 codes (one dword, element j = nibble j, low nibble first) times the block scale 2^(e8m0 - 127) → one MFMA fragment:
+// v_cvt_scalef32_pk_{f16,bf16}_fp4, one instruction per two elements.  {0, .5, 1, 1.5, 2, 3, 4, 6} x 2^e is exactly representable in
+// either operand type for the exponents ops.quantize_mxfp4_rows emits (fp16: e >= -23, subnormal results included), and the conversion
+// returns exactly that number (tests/test_mxfp4_gpu.py compares against the 16-bit image of the same matrix, bit for bit).
+// e8m0 in [1, 254]: the scale is the normal fp32 number with that exponent field.
+PADT_DEV float e8m0_scale(unsigned e8m0) { return __builtin_bit_cast(float, e8m0 << 23); }
+PADT_DEV x16x8 fp4x8_to_x16x8(unsigned w, float scale) {
+#if PADT_OP16_F16
+    const x16x2 a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, scale, 0), b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, scale, 1);
+    const x16x2 c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, scale, 2), d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, scale, 3);
+#else
+    const x16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1);
+    const x16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3);
+#endif
+    const u32x4 r = {__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, c), __builtin_bit_cast(unsigned, d)};
+    return __builtin_bit_cast(x16x8, r);
+}
+
 #if PADT_OP16_F16
 PADT_DEV f32x4 mfma16(x16x8 a, x16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 #else

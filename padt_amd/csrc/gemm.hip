@@ -69,6 +69,7 @@ struct GemmArgs {
     x16_t* C2 = nullptr;        // fp32 output: optional bf16 mirror of C (fp32 residual stream → the next projection's A operand), row-major
     long ldc2 = 0;               //   or, with c_pack, in the fragment-packed activation layout (decode steps)
     long a_lo_off = 0;           // skinny kernel, WQ = 2: A rows are (hi | lo) pairs, the lo half starts a_lo_off elements into the row (padt_gemm_split_rows)
+    const unsigned char* we = nullptr;   // skinny kernel, WQ = 3: E8M0 block exponents [N/16][Kp/64][16 rows][2 K-steps] of the MXFP4 image in W
 };
 
 // bf16 split pair of 4 fp32 values: hi = bf16(x), lo = bf16(x - hi)  (hi + lo carries 16 mantissa bits)
@@ -364,6 +365,10 @@ __global__ __launch_bounds__(256) void gemm_tile_kernel(GemmArgs p) {
 // WQ = 1: fp8 weights (OCP e4m3, per-output-row scale in p.cs) in the fp8 fragment-packed image [N/16][Kp/64][64 lanes][16 B]: a lane's
 //   16 bytes hold its 8 elements of K-step 2t and its 8 elements of K-step 2t + 1 — one 1-KiB wave load feeds two MFMA K-steps, the
 //   weight stream is half the bf16 bytes; bytes are converted to bf16 fragments in registers (exact), accumulation stays fp32.
+// WQ = 3: MXFP4 weights (OCP e2m1 codes, one E8M0 exponent per 32 K-elements of a row) in the image [N/16][Kp/64][64 lanes][8 B]: a lane's
+//   8 bytes hold its 8 elements of K-step 2t, then its 8 of K-step 2t + 1 (512 B per wave load), the two exponents of (row, K-step pair)
+//   come from p.we.  Each dword becomes one 16-bit fragment ALREADY multiplied by its block's 2^e (exact) — the fragments, the K-step pair →
+//   wave map and the summation order are those of the 16-bit packed kernel on the dequantised matrix, so every output bit is too.
 template <int MT, int NT, int NW, int EPI, bool OUT_F32, bool NORM, bool PACKED, int WQ = 0>
 __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmArgs p, float norm_eps) {
     // LDS (dynamic: 64 rows x 2 weight-row blocks x 8 waves do not fit the 64 KiB static limit): every wave's partial fragments
@@ -438,6 +443,20 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmArgs p, float 
                         if (ks < nks) q = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wq));
                         wf[u][i] = fp8x8_to_x16x8(q[0], q[1]);
                         wf[u + (U > 1 ? 1 : 0)][i] = fp8x8_to_x16x8(q[2], q[3]);
+                    }
+                    continue;
+                }
+                if (WQ == 3) {
+                    if ((u & 1) == 0) {
+                        const long tile = (long)(n0 / 16 + i) * (p.ldw / 64) + (ks >> 1);
+                        u32x2 q = u32x2{0u, 0u};
+                        unsigned ex = 0x7f7fu;                    // past the last K-step: zero codes (any valid exponent)
+                        if (ks < nks) {
+                            q = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned char*>(p.W) + (tile * 64 + lane) * 8));
+                            ex = __builtin_nontemporal_load(reinterpret_cast<const unsigned short*>(p.we) + tile * 16 + frow);
+                        }
+                        wf[u][i] = fp4x8_to_x16x8(q[0], e8m0_scale(ex & 0xffu));
+                        wf[u + (U > 1 ? 1 : 0)][i] = fp4x8_to_x16x8(q[1], e8m0_scale(ex >> 8));
                     }
                     continue;
                 }
@@ -865,7 +884,8 @@ static long splitk_ticket_bytes(long N) { return (((N + 15) / 16 * 4 + 255) / 25
 
 static int gemm_packed_impl(void* stream, const void* A, long lda, const void* Wp, long Kp, const void* bias, void* C,
                             long ldc, const void* R, long ldr, long M, long N, long K, int epilogue, float norm_eps,
-                            int split_k, void* workspace, int act_packed, const float* wscale, void* Xb = nullptr, long ldxb = 0) {
+                            int split_k, void* workspace, int act_packed, const float* wscale, void* Xb = nullptr, long ldxb = 0,
+                            const void* wexp = nullptr) {
     if (M <= 0 || N <= 0) return 0;
     const bool resid32 = Xb != nullptr;          // padt_gemm_packed_resid32: C = R = fp32 row-major stream, Xb = its packed bf16 mirror
     if (resid32 && (epilogue != EPI_RESID || (act_packed & 2) || (ldxb & 7) || ((uintptr_t)Xb & 15) || ((uintptr_t)R & 15) || R != C)) {
@@ -874,6 +894,10 @@ static int gemm_packed_impl(void* stream, const void* A, long lda, const void* W
     }
     if (wscale && ((Kp & 63) || (N & 15) || ((uintptr_t)wscale & 15))) {
         padt_set_error("padt_gemm_packed_fp8: Kp % 64 == 0, N % 16 == 0 and 16-byte aligned scales required");
+        return -1;
+    }
+    if (wexp && ((Kp & 63) || (N & 15) || (K & 31) || ((uintptr_t)wexp & 15))) {
+        padt_set_error("padt_gemm_packed_fp4: Kp % 64 == 0, N % 16 == 0, K % 32 == 0 and 16-byte aligned exponents required");
         return -1;
     }
     if ((act_packed & ~3) || ((act_packed & 1) && (lda & 7)) || ((act_packed & 2) && ((ldc & 7) || (R != nullptr && ldr != ldc)))) {
@@ -904,6 +928,16 @@ static int gemm_packed_impl(void* stream, const void* A, long lda, const void* W
         a.split = split_k;
     }
     hipStream_t s = (hipStream_t)stream;
+    if (wexp) {                                                      // MXFP4 image: the block scales are applied in the fragments, no accumulator scale
+        a.we = (const unsigned char*)wexp;
+        if (resid32) dispatch_packed<EPI_RESID, false, 3, true>(a, 0.f, s);
+        else if (epilogue == EPI_SWIGLU) { if (norm) dispatch_packed<EPI_SWIGLU, true, 3>(a, norm_eps, s); else dispatch_packed<EPI_SWIGLU, false, 3>(a, 0.f, s); }
+        else if (epilogue == EPI_RESID) dispatch_packed<EPI_RESID, false, 3>(a, 0.f, s);
+        else { if (norm) dispatch_packed<EPI_NONE, true, 3>(a, norm_eps, s); else dispatch_packed<EPI_NONE, false, 3>(a, 0.f, s); }
+        hipError_t e4 = hipGetLastError();
+        if (e4 != hipSuccess) { padt_set_error(hipGetErrorString(e4)); return -2; }
+        return 0;
+    }
     if (resid32) {
         a.cs = wscale;
         if (wscale) dispatch_packed<EPI_RESID, false, 1, true>(a, 0.f, s);
@@ -950,6 +984,25 @@ extern "C" int PADT_TWIN(padt_gemm_packed_resid32)(void* stream, const void* A, 
     if (Xb == nullptr) { padt_set_error("padt_gemm_packed_resid32: the packed mirror is required"); return -1; }
     return gemm_packed_impl(stream, A, lda, Wp, Kp, nullptr, X32, ldx, X32, ldx, M, N, K, EPI_RESID, -1.0f, split_k, workspace, a_packed ? 1 : 0,
                             (const float*)scales, Xb, ldxb);
+}
+
+// The same projections over MXFP4 weights (OCP microscaling: e2m1 codes, one E8M0 exponent per 32 K-elements of a weight row; 4.25 bits per
+// weight): Wq = the nibble image [N/16][Kp/64][64 lanes][8 B], exps = [N/16][Kp/64][16][2] (ops.pack_weight_fp4).  Codes times 2^e are rebuilt
+// in registers as the 16-bit fragments of the dequantised matrix: C is what padt_gemm_packed_bf16 computes on that matrix, bit for bit.
+extern "C" int PADT_TWIN(padt_gemm_packed_fp4)(void* stream, const void* A, long lda, const void* Wq, long Kp, const void* exps, const void* bias,
+                                    void* C, long ldc, const void* R, long ldr, long M, long N, long K, int epilogue, float norm_eps,
+                                    int split_k, void* workspace, int act_packed) {
+    if (Wq == nullptr || exps == nullptr) { padt_set_error("padt_gemm_packed_fp4: the nibble image and its block exponents are required"); return -1; }
+    return gemm_packed_impl(stream, A, lda, Wq, Kp, bias, C, ldc, R, ldr, M, N, K, epilogue, norm_eps, split_k, workspace, act_packed,
+                            nullptr, nullptr, 0, exps);
+}
+
+extern "C" int PADT_TWIN(padt_gemm_packed_resid32_fp4)(void* stream, const void* A, long lda, const void* Wq, long Kp, const void* exps, void* X32, long ldx,
+                                            void* Xb, long ldxb, long M, long N, long K, int split_k, void* workspace, int a_packed) {
+    if (Wq == nullptr || exps == nullptr) { padt_set_error("padt_gemm_packed_resid32_fp4: the nibble image and its block exponents are required"); return -1; }
+    if (Xb == nullptr) { padt_set_error("padt_gemm_packed_resid32_fp4: the packed mirror is required"); return -1; }
+    return gemm_packed_impl(stream, A, lda, Wq, Kp, nullptr, X32, ldx, X32, ldx, M, N, K, EPI_RESID, -1.0f, split_k, workspace, a_packed ? 1 : 0,
+                            nullptr, Xb, ldxb, exps);
 }
 
 // fp8 x fp8 MFMA GEMM at prompt length (gemm256.hip, FP8 instantiations of the phase-pipelined kernel); takes a profile slot like every tile GEMM.

@@ -228,19 +228,22 @@ class DecodeSession:
         fp8 = W.llm_weights == "fp8"                              # fp8 weight images (+ per-row scales): half the bytes per step
         wk = ".wq" if fp8 else ".wp"
         ws = (lambda m: W[m + ".ws"]) if fp8 else (lambda m: None)
+        we = lambda m: None
+        if W.llm_weights == "fp4":                                # MXFP4 images (+ block exponents): the same launches over 4.25 bits per weight
+            wk, we = ".w4", (lambda m: W[m + ".we"])
         for i in range(cfg.num_hidden_layers):
             p = f"llm.{i}."
             # 6 launches per layer: [norm+qkv] [rope+append+split attention] [merge] [o+resid] [norm+gate/up+SwiGLU] [down+resid]
             ops.gemm_packed(self.x, W[p + "qkv" + wk], self.n_qkv, W[p + "qkv.b"], out=self.qkv, norm_eps=eps_n, a_packed=True, rows=B,
-                            scales=ws(p + "qkv"))
+                            scales=ws(p + "qkv"), exps=we(p + "qkv"))
             ops.decode_attn_rope(self.qkv, self.rope_cs, self.slot, self.kc[i], self.vtc[i], self.att, self.attn_ws, Hq, Hkv,
                                  hd, self.s_max, self.s_max, out_packed=True, cache_packed=self.cache_packed)
-            ops.gemm_packed_resid32(self.att, W[p + "o" + wk], D, self.x32, self.x, scales=ws(p + "o"), split_k=self.o_split,
+            ops.gemm_packed_resid32(self.att, W[p + "o" + wk], D, self.x32, self.x, scales=ws(p + "o"), exps=we(p + "o"), split_k=self.o_split,
                                     workspace=self.splitk_ws, rows=B)
             ops.gemm_packed(self.x, W[p + "gu" + wk], 2 * W.llm_ipad, out=self.h, epilogue=ops.EPI_SWIGLU, norm_eps=eps_n,
-                            a_packed=True, c_packed=True, rows=B, scales=ws(p + "gu"))
-            ops.gemm_packed_resid32(self.h, W[p + "down" + wk], D, self.x32, self.x, scales=ws(p + "down"), split_k=self.down_split,
-                                    workspace=self.splitk_ws, rows=B)
+                            a_packed=True, c_packed=True, rows=B, scales=ws(p + "gu"), exps=we(p + "gu"))
+            ops.gemm_packed_resid32(self.h, W[p + "down" + wk], D, self.x32, self.x, scales=ws(p + "down"), exps=we(p + "down"),
+                                    split_k=self.down_split, workspace=self.splitk_ws, rows=B)
         ops.rmsnorm_f32(self.x32, W["llm.norm"], out=self.hn, eps=cfg.rms_norm_eps)
         ops.check_finite(self.hn, self.nf, rows_per_flag=1, rows=B)      # sticky per-row flag, read once per generate (modeling.generate_collect)
         self.head_and_select(self.hn, advance=True)

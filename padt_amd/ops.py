@@ -301,6 +301,81 @@ def pack_weight_fp8(wq):
     return wq.view(Np // 16, 16, Kp // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5).contiguous().view(Np, Kp)
 
 
+_E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+MXFP4_BLOCK = 32
+
+
+def mxfp4_min_exponent(deq_dtype):
+    """Smallest block exponent e for which the smallest non-zero code, 0.5 * 2^e, is exactly representable in deq_dtype: fp16 ends at its
+    smallest subnormal 2^-24 (e = -23); bf16 reaches further down than E8M0 does, so the limit is E8M0 byte 1 (e = -126, whose scale is still
+    a normal fp32 number)."""
+    return -23 if deq_dtype == F16 else -126
+
+
+def quantize_mxfp4_rows(w, deq_dtype=BF16):
+    """OCP MXFP4 quantisation of a weight matrix [N][K] (K % 32 == 0): → (codes uint8 [N][K/2], exps uint8 [N][K/32] (E8M0), w_deq [N][K]
+    in deq_dtype).  One block = 32 consecutive K-elements of one row, scale 2^e with e = ceil(log2(amax / 6)) — nothing saturates, the
+    convention of quantize_fp8_rows with 6 in place of 448 — clamped from below to mxfp4_min_exponent(deq_dtype) (an all-zero block gets that
+    minimum).  Values round to the e2m1 grid {0, .5, 1, 1.5, 2, 3, 4, 6} to nearest, ties to the even code; code = sign << 3 | index, a zero
+    is always +0; element k of a row sits in nibble k % 2 (low first) of byte k / 2.  w_deq = sign * grid[index] * 2^e is exactly
+    representable in deq_dtype: what prefill multiplies with, what the oracle sees and what the decode kernel rebuilds in registers are the
+    same numbers.  |w_deq - w| <= amax_block / 5 on un-clamped blocks (worst case: 5/6 of amax at the tie 5 → 4)."""
+    N, K = w.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError("quantize_mxfp4_rows: K = %d is not a multiple of the MXFP4 block (32)" % K)
+    wd = w.double().view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wd.abs().amax(dim=-1)
+    e_min = mxfp4_min_exponent(deq_dtype)
+    e = torch.ceil(torch.log2(amax.clamp_min(1e-300) / 6.0))
+    e = torch.where(amax > 6.0 * torch.exp2(e), e + 1, e)              # log2 rounded across an integer: restore e = min{e : amax <= 6 * 2^e}
+    e = torch.where(amax <= 6.0 * torch.exp2(e - 1), e - 1, e)
+    e = torch.where(amax > 0, e, torch.full_like(e, e_min)).clamp(e_min, 127)
+    x = wd.abs() / torch.exp2(e)[..., None]                             # exact: a power-of-two scaling in double
+    idx = ((x > 0.25).to(torch.uint8) + (x >= 0.75).to(torch.uint8) + (x > 1.25).to(torch.uint8) + (x >= 1.75).to(torch.uint8)
+           + (x > 2.5).to(torch.uint8) + (x >= 3.5).to(torch.uint8) + (x > 5.0).to(torch.uint8))      # ties go to the even code
+    neg = (wd < 0) & (idx > 0)
+    nib = (idx | (neg.to(torch.uint8) << 3)).view(N, K // 2, 2)
+    codes = (nib[..., 0] | (nib[..., 1] << 4)).contiguous()
+    grid = torch.tensor(_E2M1_GRID, dtype=torch.float64, device=w.device)
+    deq = torch.where(neg, -1.0, 1.0) * grid[idx.long()] * torch.exp2(e)[..., None]
+    return codes, (e + 127).to(torch.uint8).contiguous(), deq.view(N, K).to(deq_dtype)
+
+
+def dequantize_mxfp4(codes, exps):
+    """(codes [N][K/2], exps [N][K/32]) → fp64 [N][K]: sign * grid[index] * 2^(exps - 127), the statement of the format."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    nib = torch.stack([codes & 15, codes >> 4], dim=-1).view(N, K)
+    grid = torch.tensor(_E2M1_GRID, dtype=torch.float64, device=codes.device)
+    v = grid[(nib & 7).long()] * torch.where((nib & 8) != 0, -1.0, 1.0)
+    return (v.view(N, K // MXFP4_BLOCK, MXFP4_BLOCK) * torch.exp2(exps.double() - 127)[..., None]).view(N, K)
+
+
+def pack_weight_fp4(codes, exps):
+    """(codes uint8 [N][K/2], exps uint8 [N][K/32]) → the decode image (nibbles uint8 [Np][Kp/2], exponents uint8 [Np/16][Kp/64][16][2]), N
+    and K zero-padded to 16 / 64 (zero codes; padded exponents are 127 = 2^0).  Nibbles: [Np/16][Kp/64][64 lanes][8 B], lane fq*16 + frow
+    holds row n16*16 + frow, k = kp*64 + half*32 + fq*8 + j in nibble j % 2 of byte half*4 + j/2 — the lane's fragment of K-step 2kp, then of
+    2kp + 1; the exponent of (row, K-step) sits at [n16][kp][frow][half]."""
+    N, K2 = codes.shape
+    K = K2 * 2
+    assert exps.shape == (N, K // MXFP4_BLOCK), (codes.shape, exps.shape)
+    Np, Kp = (N + 15) // 16 * 16, (K + 63) // 64 * 64
+    if (Np, Kp) != (N, K):
+        c, e = codes.new_zeros((Np, Kp // 2)), exps.new_full((Np, Kp // MXFP4_BLOCK), 127)
+        c[:N, :K2] = codes
+        e[:N, :K // MXFP4_BLOCK] = exps
+        codes, exps = c, e
+    img = codes.view(Np // 16, 16, Kp // 64, 2, 4, 4).permute(0, 2, 4, 1, 3, 5).contiguous().view(Np, Kp // 2)
+    return img, exps.view(Np // 16, 16, Kp // 64, 2).permute(0, 2, 1, 3).contiguous()
+
+
+def unpack_weight_fp4(img, exps_packed, N, K):
+    """Inverse of pack_weight_fp4 → (codes [N][K/2], exps [N][K/32])."""
+    Np, Kp = img.shape[0], img.shape[1] * 2
+    codes = img.view(Np // 16, Kp // 64, 4, 16, 2, 4).permute(0, 3, 1, 4, 2, 5).contiguous().view(Np, Kp // 2)
+    exps = exps_packed.permute(0, 2, 1, 3).contiguous().view(Np, Kp // MXFP4_BLOCK)
+    return codes[:N, :K // 2].contiguous(), exps[:N, :K // MXFP4_BLOCK].contiguous()
+
+
 def new_splitk_workspace(n, split_k, device):
     """Zero-initialised split-K workspace (ticket header must start at zero), one per concurrently decoding stream."""
     return torch.zeros(_lib.load().padt_gemm_splitk_workspace(n, split_k), dtype=torch.uint8, device=device)
@@ -315,10 +390,15 @@ def pack_rows(src, dst, M, to_packed=True):
 
 
 def gemm_packed(a, wp, n, bias=None, out=None, epilogue=EPI_NONE, residual=None, norm_eps=None, split_k=1, workspace=None,
-                a_packed=False, c_packed=False, rows=None, scales=None):
+                a_packed=False, c_packed=False, rows=None, scales=None, exps=None):
     """Decode-step projection over a pack_weight() image (rows <= 128): out = epi(rstd?(a) * (a @ w^T) + bias).
     a_packed / c_packed: a / (out and residual) are fragment-packed activation buffers holding `rows` valid rows.
-    scales given: wp is the fp8 image (pack_weight_fp8) and out = epi(rstd?(a) * scales[n] * (a @ wq^T) + bias)."""
+    scales given: wp is the fp8 image (pack_weight_fp8) and out = epi(rstd?(a) * scales[n] * (a @ wq^T) + bias).
+    exps given: wp is the MXFP4 nibble image and exps its block exponents (pack_weight_fp4): gemm_packed_fp4."""
+    if exps is not None:
+        assert scales is None
+        return gemm_packed_fp4(a, wp, exps, n, bias=bias, out=out, epilogue=epilogue, residual=residual, norm_eps=norm_eps, split_k=split_k,
+                               workspace=workspace, a_packed=a_packed, c_packed=c_packed, rows=rows)
     if scales is None:
         dt, name = _x16(a, wp, bias, residual, out), "padt_gemm_packed_bf16"
     else:
@@ -343,9 +423,12 @@ def gemm_packed_fp8(a, wq_packed, scales, n, *args, **kw):
     return gemm_packed(a, wq_packed, n, *args, scales=scales, **kw)
 
 
-def gemm_packed_resid32(a, wp, n, x32, xb_packed, scales=None, split_k=1, workspace=None, a_packed=True, rows=None):
+def gemm_packed_resid32(a, wp, n, x32, xb_packed, scales=None, split_k=1, workspace=None, a_packed=True, rows=None, exps=None):
     """Decode-step residual projection over the fp32 stream: x32[rows, n] += scales?[n] * (a @ w^T) in place, xb_packed = bf16(x32) in the
-    fragment-packed activation layout.  wp: pack_weight() image, or with scales the fp8 image."""
+    fragment-packed activation layout.  wp: pack_weight() image, or with scales the fp8 image, or with exps the MXFP4 image."""
+    if exps is not None:
+        assert scales is None
+        return gemm_packed_resid32_fp4(a, wp, exps, n, x32, xb_packed, split_k=split_k, workspace=workspace, a_packed=a_packed, rows=rows)
     dt = _x16(a, xb_packed, None if scales is not None else wp)
     M, K = a.shape
     if rows is not None:
@@ -354,6 +437,44 @@ def gemm_packed_resid32(a, wp, n, x32, xb_packed, scales=None, split_k=1, worksp
     _lib.check(_fn("padt_gemm_packed_resid32", dt)(_stream(), _p(a), a.stride(0), _p(wp), wp.shape[1], _p(scales), _p(x32), x32.stride(0),
                                             _p(xb_packed), xb_packed.stride(0), M, n, K, int(split_k), _p(workspace), 1 if a_packed else 0),
                "padt_gemm_packed_resid32")
+    return x32
+
+
+def _chk_fp4(wq, exps):
+    assert wq.dtype == torch.uint8 and exps.dtype == torch.uint8 and wq.is_cuda and exps.is_cuda and wq.is_contiguous() and exps.is_contiguous()
+    assert exps.numel() * 16 == wq.numel(), "exponents do not belong to this nibble image"     # 2 bytes per 16 rows x 64 elements / 16 = 32 B per 512 B
+
+
+def gemm_packed_fp4(a, wq, exps, n, bias=None, out=None, epilogue=EPI_NONE, residual=None, norm_eps=None, split_k=1, workspace=None,
+                    a_packed=False, c_packed=False, rows=None):
+    """gemm_packed over an MXFP4 image (pack_weight_fp4: nibbles + block exponents): out = epi(rstd?(a) * (a @ w_deq^T) + bias), bit for bit
+    what gemm_packed gives on pack_weight(w_deq)."""
+    _chk_fp4(wq, exps)
+    dt = _x16(a, bias, residual, out)
+    M, K = a.shape
+    if rows is not None:
+        M = rows
+    n_out = n // 2 if epilogue == EPI_SWIGLU else n
+    if out is None:
+        out = torch.empty((M, n_out), device=a.device, dtype=dt)
+    _lib.check(_fn("padt_gemm_packed_fp4", dt)(_stream(), _p(a), a.stride(0), _p(wq), wq.shape[1] * 2, _p(exps), _p(bias), _p(out), out.stride(0),
+                                               _p(residual), residual.stride(0) if residual is not None else 0, M, n, K, epilogue,
+                                               -1.0 if norm_eps is None else float(norm_eps), int(split_k), _p(workspace),
+                                               (1 if a_packed else 0) | (2 if c_packed else 0)), "padt_gemm_packed_fp4")
+    return out
+
+
+def gemm_packed_resid32_fp4(a, wq, exps, n, x32, xb_packed, split_k=1, workspace=None, a_packed=True, rows=None):
+    """gemm_packed_resid32 over an MXFP4 image: x32[rows, n] += a @ w_deq^T in place, xb_packed = X(x32) in the packed activation layout."""
+    _chk_fp4(wq, exps)
+    dt = _x16(a, xb_packed)
+    M, K = a.shape
+    if rows is not None:
+        M = rows
+    assert x32.dtype == torch.float32 and x32.stride(-1) == 1
+    _lib.check(_fn("padt_gemm_packed_resid32_fp4", dt)(_stream(), _p(a), a.stride(0), _p(wq), wq.shape[1] * 2, _p(exps), _p(x32), x32.stride(0),
+                                                       _p(xb_packed), xb_packed.stride(0), M, n, K, int(split_k), _p(workspace),
+                                                       1 if a_packed else 0), "padt_gemm_packed_resid32_fp4")
     return x32
 
 

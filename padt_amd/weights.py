@@ -232,9 +232,13 @@ def prepare_weights(sd: Dict[str, torch.Tensor], cfg: PaDTConfig, device="cuda",
     power-of-two scales (ops.quantize_fp8_rows); the decode step streams the fp8 images (half the bytes), prefill multiplies with the
     16-bit image of the SAME numbers (scale * q is exact) — BASELINE configs[4], the 7B "fp8 MFMA weight path".  "fp8+act" additionally
     runs the prompt pass as fp8 x fp8 MFMA GEMMs over e4m3 ACTIVATION rows quantised on the fly (1.6x the 16-bit tile GEMM on the 7B shapes;
-    costs precision: DESIGN.md §4 numerics) — opt-in since round 4 (it was implied by "fp8" in round 3)."""
-    if llm_weights not in ("bf16", "fp8", "fp8+act"):
-        raise ValueError("llm_weights must be 'bf16', 'fp8' or 'fp8+act'")
+    costs precision: DESIGN.md §4 numerics) — opt-in since round 4 (it was implied by "fp8" in round 3).
+    llm_weights = "fp4": the same matrices in OCP MXFP4 (e2m1 codes, one power-of-two scale per 32 K-elements of a row: ops.quantize_mxfp4_rows),
+    4.25 bits per weight in the decode images; `.w` again holds the exactly dequantised 16-bit image for prefill.  There is no "fp4+act"."""
+    if llm_weights == "fp4+act":
+        raise ValueError("llm_weights='fp4+act' is not supported: MXFP4 weights run with 16-bit prompt-pass activations only (use 'fp4')")
+    if llm_weights not in ("bf16", "fp8", "fp8+act", "fp4"):
+        raise ValueError("llm_weights must be 'bf16', 'fp8', 'fp8+act' or 'fp4'")
     operands = operands or os.environ.get("PADT_OPERANDS", "fp16")
     if operands not in ("bf16", "fp16"):
         raise ValueError("operands must be 'fp16' or 'bf16'")
@@ -313,7 +317,7 @@ def prepare_weights(sd: Dict[str, torch.Tensor], cfg: PaDTConfig, device="cuda",
         put(d + "down.w", _pad_cols(get(s + "mlp.down_proj.weight"), li_pad))
     # decode-step copies of the LLM matrices in MFMA-fragment order (ops.pack_weight): the single-token GEMVs stream
     # them with fully coalesced 1 KiB wave loads.  +5.5 GB for PaDT_Pro_3B — HBM capacity is not the constraint here.
-    from .ops import pack_weight, pack_weight_fp8, quantize_fp8_rows
+    from .ops import pack_weight, pack_weight_fp4, pack_weight_fp8, quantize_fp8_rows, quantize_mxfp4_rows
     for i in range(cfg.num_hidden_layers):
         d = f"llm.{i}."
         for nm in ("qkv", "o", "gu", "down"):
@@ -324,6 +328,10 @@ def prepare_weights(sd: Dict[str, torch.Tensor], cfg: PaDTConfig, device="cuda",
                 W[d + nm + ".ws"] = sc
                 if W.fp8_prefill and fp8_gemm_ok(q.shape[0], q.shape[1]):
                     W[d + nm + ".w8"] = q.contiguous()           # prefill: row-major e4m3 image for the fp8 x fp8 MFMA GEMM (padt_gemm_fp8)
+            elif llm_weights == "fp4":
+                c, e, deq = quantize_mxfp4_rows(W[d + nm + ".w"], deq_dtype=op16)
+                W[d + nm + ".w"] = deq                           # prefill: 16-bit image of the quantised matrix (exact)
+                W[d + nm + ".w4"], W[d + nm + ".we"] = pack_weight_fp4(c, e)   # decode: MXFP4 nibble image + E8M0 block exponents
             else:
                 W[d + nm + ".wp"] = pack_weight(W[d + nm + ".w"])
     # fragment-packed copy of the head table for the decode-step logit head (+0.62 GB at 3B; the row-major table stays: it is
