@@ -311,6 +311,15 @@ int  padt_vrt_head(void* stream, const void* hidden, long ldh, const void* embed
                    long n_proto, const int* vrt_off, const int* mode_table, const int* step, void* logits_f32,
                    long ld_logits, void* part_val, void* part_idx, long batch, long D, int eos,
                    const void* embed_table_packed, const void* gen_cfg, const void* seen, long seen_words);
+/* padt_vrt_head with a ban bitmap (nullable, device, [batch][ban_words] 32-bit words, bit r = table row r is banned for that sample this step:
+ * padt_gen_rules): a set bit makes the written logit and the arg-max partial -inf, exactly like a row outside the logit mask; the repetition
+ * penalty is then irrelevant for that logit.  ban = NULL is padt_vrt_head, bit for bit.  A sample whose every column is banned has no arg-max:
+ * padt_greedy_step's sentinel branch emits the pad token for it. */
+int  padt_vrt_head_ban(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab, const void* proto,
+                       long n_proto, const int* vrt_off, const int* mode_table, const int* step, void* logits_f32,
+                       long ld_logits, void* part_val, void* part_idx, long batch, long D, int eos,
+                       const void* embed_table_packed, const void* gen_cfg, const void* seen, long seen_words,
+                       const void* ban, long ban_words);
 /* argmax reduction (ties → lowest id), pad/EOS bookkeeping, token append, hidden-row stash, slot/len/position/step
  * advance — all on device.  padt.py:745-757, 732-737.  gen_cfg / seen as in padt_vrt_head: extra EOS ids stop a row too
  * (generation_config's eos_token_id list), and the chosen token's bit is set in the row's seen bitmap. */
@@ -348,6 +357,17 @@ int  padt_stash_step_f32(void* stream, const void* src_f32, long n, const int* s
 /* seen[rows[i]] |= bit(ids[i]) for the prompt tokens of a generate call (ids global in the session's table): the `input_ids` HF's
  * RepetitionPenaltyLogitsProcessor gathers over (generation/logits_process.py, reached from padt.py:717) — prompt and padding ids included. */
 int  padt_seen_init(void* stream, const long* ids, const int* rows, long n, void* seen, long seen_words);
+/* HF's pure-ban logits processors — suppress_tokens, begin_suppress_tokens, bad_words_ids, no_repeat_ngram_size (generation/logits_process.py,
+ * reached from padt.py:570-580,717) — as the step's ban bitmap for padt_vrt_head_ban.  One block per sample rebuilds ban[b][0..ban_words) from
+ * scratch (zero, barrier, atomic OR), so no bit survives a step it does not apply to.  The sample's history is HF's input_ids:
+ * h[i] = i < hist_len[b] ? hist[b][i] : tokens[b][i - hist_len[b]], cur = hist_len[b] + *step ids (tokens = padt_greedy_step's tokens_out).
+ * rules: 4096 int32 in DEVICE memory (nothing is baked into a captured graph), packed by ops.gen_rules_tensor:
+ *   [0] n-gram size n (0 off) [1] n_static [2] n_begin [3] n_words [4..) static ids | begin ids | word offsets | words as (m, id[0..m))
+ *   static ids (suppress_tokens, 1-token bad words): always;  begin ids: only when *step == 0;  a word of m > 1 ids: id[m-1] when cur >= m and
+ *   the last m - 1 history ids equal id[0..m-1);  n-gram: when cur + 1 >= n, h[i + n - 1] for every i in [0, cur - n] whose h[i..i + n - 2]
+ *   equals the last n - 1 history ids (n = 1: every id of the history).  Ids outside [0, n_cols) set no bit; n_cols <= 32 ban_words. */
+int  padt_gen_rules(void* stream, const int* rules, const int* hist, long ld_hist, const int* hist_len, const long* tokens, long ld_tokens,
+                    const int* step, void* ban, long ban_words, long n_cols, long batch);
 
 /* ---- caller-side post-processing --------------------------------------------------------------- */
 /* out[o][y][x] = sigmoid(bilinear(masks[o][:src_h[o]][:src_w[o]] → dst_h[o] x dst_w[o], align_corners=False))[y][x] > 0.5,

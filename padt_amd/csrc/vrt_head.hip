@@ -47,6 +47,7 @@ struct HeadArgs {
     const x16_t* Ep;                  // optional fragment-packed copy of E (PACKED kernels; h is then packed too)
     const GenCfg* gen;                 // optional generation config (repetition penalty) + per-sample seen-token bitmap
     const unsigned* seen; long seen_words;
+    const unsigned* ban; long ban_words;   // optional per-sample bitmap of banned table rows (gen_rules_kernel): bit set → the logit is -inf
 };
 
 // PACKED: text rows come from a fragment-packed copy of the table ([V/16][D/32][64 lanes][8], ops.pack_weight — every wave
@@ -146,6 +147,7 @@ __global__ __launch_bounds__(256) void vrt_head_kernel(HeadArgs p) {
                 if (row < p.V) ok = (mode == 0 || mode == 1 || (mode == 3 && row == p.eos));
                 else { const int jv = row - p.V; ok = (jv >= lo && jv < hi) && (mode == 0 || mode == 2); }
             }
+            if (p.ban && ok) ok = !((p.ban[(long)m * p.ban_words + (row >> 5)] >> (row & 31)) & 1u);   // a pure ban: the penalty no longer matters
             float sc = sum[r];
             if (pen != 1.0f && ok && ((p.seen[(long)m * p.seen_words + (row >> 5)] >> (row & 31)) & 1u)) sc = sc < 0.f ? sc * pen : sc / pen;
             const float v = ok ? sc : -INFINITY;
@@ -236,6 +238,75 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyArgs p) {
 __global__ void step_inc_kernel(int* step) { *step += 1; }
 
 extern "C" long padt_vrt_head_nblk(long vocab, long n_proto) { return (vocab + n_proto + 15) / 16; }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// HF's pure-ban logits processors (generation/logits_process.py: SuppressTokens, SuppressTokensAtBegin, NoBadWords = SequenceBias with
+// -inf, NoRepeatNGram) as ONE per-step bitmap the head tests next to the logit mask.  One block per session row rebuilds the row of `ban`
+// from scratch — zero, barrier, OR in — so no bit outlives the step it applies to.  The row's history is what HF's processors see as
+// input_ids: h[i] = i < L ? hist[row][i] (the caller's padded prompt row, padding included) : tokens[row][i - L], cur = L + *step ids.
+// Rule table (DEVICE memory like GenCfg, nothing baked into a captured graph; packed by ops.gen_rules_tensor, at most GEN_RULES_MAX ints):
+//   [0] n-gram size n (0 = off)  [1] n_static  [2] n_begin  [3] n_words  [4 ..) static ids | begin ids | word offsets | words (m, id[m])
+//   static ids (suppress_tokens and 1-token bad words): always;  begin ids: only at *step == 0;
+//   word of m > 1 ids: its last id when cur >= m and the last m - 1 history ids equal its first m - 1 (SequenceBiasLogitsProcessor skips a
+//   sequence LONGER than the input: cur >= m, not m - 1);
+//   n-gram: when cur + 1 >= n, for every i in [0, cur - n] with h[i .. i + n - 2] == the last n - 1 history ids: h[i + n - 1] (n = 1: every id
+//   of the history).  Finished rows are treated like live ones, as in HF.
+constexpr int GEN_RULES_MAX = 4096;
+struct RulesArgs {
+    const int* rules; const int* hist; long ld_hist; const int* hist_len; const long* tokens; long ld_tok; const int* step;
+    unsigned* ban; long ban_words; int n_cols;
+};
+
+__global__ __launch_bounds__(256) void gen_rules_kernel(RulesArgs p) {
+    const int row = blockIdx.x, tid = threadIdx.x;
+    unsigned* out = p.ban + (long)row * p.ban_words;
+    for (long w = tid; w < p.ban_words; w += 256) out[w] = 0u;
+    __syncthreads();
+    const int* r = p.rules;
+    int t = *p.step;
+    t = t < 0 ? 0 : (t > (int)p.ld_tok ? (int)p.ld_tok : t);
+    int L = p.hist_len[row];
+    L = L < 0 ? 0 : (L > (int)p.ld_hist ? (int)p.ld_hist : L);
+    const int cur = L + t;
+    const int* hrow = p.hist + (long)row * p.ld_hist;
+    const long* trow = p.tokens + (long)row * p.ld_tok;
+    auto h = [&](int i) -> int { return i < L ? hrow[i] : (int)trow[i - L]; };
+    auto set = [&](int id) { if (id >= 0 && id < p.n_cols) atomicOr(&out[id >> 5], 1u << (id & 31)); };
+    const int n = r[0], ns = r[1], nb = r[2], nw = r[3];
+    if (n < 0 || ns < 0 || nb < 0 || nw < 0 || 4L + ns + nb + nw > GEN_RULES_MAX) return;      // not a table ops.gen_rules_tensor packed
+    for (int i = tid; i < ns; i += 256) set(r[4 + i]);
+    if (t == 0)
+        for (int i = tid; i < nb; i += 256) set(r[4 + ns + i]);
+    for (int w = tid; w < nw; w += 256) {
+        const int o = r[4 + ns + nb + w];
+        if (o < 0 || o >= GEN_RULES_MAX) continue;
+        const int m = r[o];
+        if (m < 2 || o + m >= GEN_RULES_MAX || cur < m) continue;
+        bool eq = true;
+        for (int k = 0; k < m - 1 && eq; ++k) eq = h(cur - (m - 1) + k) == r[o + 1 + k];
+        if (eq) set(r[o + m]);
+    }
+    if (n > 0 && cur + 1 >= n)
+        for (int i = tid; i <= cur - n; i += 256) {
+            bool eq = true;
+            for (int k = 0; k < n - 1 && eq; ++k) eq = h(i + k) == h(cur - (n - 1) + k);
+            if (eq) set(h(i + n - 1));
+        }
+}
+
+extern "C" int padt_gen_rules(void* stream, const int* rules, const int* hist, long ld_hist, const int* hist_len, const long* tokens,
+                              long ld_tokens, const int* step, void* ban, long ban_words, long n_cols, long batch) {
+    if (batch <= 0) return 0;
+    if (!rules || !hist || !hist_len || !tokens || !step || !ban || ld_hist <= 0 || ld_tokens <= 0 || ld_hist + ld_tokens > 0x7fffffffL) {
+        padt_set_error("padt_gen_rules: rule table, history, token buffer, step counter and ban bitmap are required"); return -1;
+    }
+    if (n_cols <= 0 || n_cols > ban_words * 32) { padt_set_error("padt_gen_rules: ban bitmap narrower than the table"); return -1; }
+    RulesArgs a{rules, hist, ld_hist, hist_len, tokens, ld_tokens, step, (unsigned*)ban, ban_words, (int)n_cols};
+    hipLaunchKernelGGL(gen_rules_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    return 0;
+}
 #endif
 
 template <int MT, int NT, bool PACKED>
@@ -249,11 +320,11 @@ static void launch_head(const HeadArgs& a, int nblk, hipStream_t s) {
     hipLaunchKernelGGL((vrt_head_kernel<MT, NT, PACKED>), dim3((nblk + NT - 1) / NT), dim3(256), lds, s, a);
 }
 
-extern "C" int PADT_TWIN(padt_vrt_head)(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab,
-                             const void* proto, long n_proto, const int* vrt_off, const int* mode_table,
-                             const int* step, void* logits_f32, long ld_logits, void* part_val, void* part_idx,
-                             long batch, long D, int eos, const void* embed_table_packed, const void* gen_cfg,
-                             const void* seen, long seen_words) {
+static int vrt_head_impl(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab,
+                         const void* proto, long n_proto, const int* vrt_off, const int* mode_table,
+                         const int* step, void* logits_f32, long ld_logits, void* part_val, void* part_idx,
+                         long batch, long D, int eos, const void* embed_table_packed, const void* gen_cfg,
+                         const void* seen, long seen_words, const void* ban, long ban_words) {
     if (batch <= 0) return 0;
     if (batch > 128 || (D & 7) || (ldh & 7)) { padt_set_error("padt_vrt_head: batch <= 128, D % 8 == 0 required"); return -1; }
     if (embed_table_packed && ((D & 31) || (vocab & 15) || ((uintptr_t)embed_table_packed & 15) || ((uintptr_t)hidden & 15))) {
@@ -262,8 +333,10 @@ extern "C" int PADT_TWIN(padt_vrt_head)(void* stream, const void* hidden, long l
     }
     HeadArgs a{(const x16_t*)hidden, ldh, (const x16_t*)embed_table, (int)vocab, (const x16_t*)proto, (int)n_proto,
                vrt_off, mode_table, step, (float*)logits_f32, ld_logits, (float*)part_val, (int*)part_idx, (int)batch,
-               (int)D, eos, (const x16_t*)embed_table_packed, (const GenCfg*)gen_cfg, (const unsigned*)seen, seen_words};
+               (int)D, eos, (const x16_t*)embed_table_packed, (const GenCfg*)gen_cfg, (const unsigned*)seen, seen_words,
+               (const unsigned*)ban, ban_words};
     if (seen && seen_words * 32 < vocab + n_proto) { padt_set_error("padt_vrt_head: seen bitmap narrower than the table"); return -1; }
+    if (ban && ban_words * 32 < vocab + n_proto) { padt_set_error("padt_vrt_head_ban: ban bitmap narrower than the table"); return -1; }
     const int nblk = (int)padt_vrt_head_nblk(vocab, n_proto);
     hipStream_t s = (hipStream_t)stream;
     if (embed_table_packed) {                                   // NT = 4 table blocks per thread block (2 at 128 rows): profiles/r03_head_nt_ab.log
@@ -278,6 +351,26 @@ extern "C" int PADT_TWIN(padt_vrt_head)(void* stream, const void* hidden, long l
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
     return 0;
+}
+
+extern "C" int PADT_TWIN(padt_vrt_head)(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab,
+                             const void* proto, long n_proto, const int* vrt_off, const int* mode_table,
+                             const int* step, void* logits_f32, long ld_logits, void* part_val, void* part_idx,
+                             long batch, long D, int eos, const void* embed_table_packed, const void* gen_cfg,
+                             const void* seen, long seen_words) {
+    return vrt_head_impl(stream, hidden, ldh, embed_table, vocab, proto, n_proto, vrt_off, mode_table, step, logits_f32, ld_logits, part_val,
+                         part_idx, batch, D, eos, embed_table_packed, gen_cfg, seen, seen_words, nullptr, 0);
+}
+
+// padt_vrt_head with a ban bitmap [batch][ban_words] (padt_gen_rules): a set bit makes the written logit and the partial -inf, like a row
+// outside the logit mask.  A row whose every column is banned has no arg-max: padt_greedy_step's sentinel branch then emits pad.
+extern "C" int PADT_TWIN(padt_vrt_head_ban)(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab,
+                             const void* proto, long n_proto, const int* vrt_off, const int* mode_table,
+                             const int* step, void* logits_f32, long ld_logits, void* part_val, void* part_idx,
+                             long batch, long D, int eos, const void* embed_table_packed, const void* gen_cfg,
+                             const void* seen, long seen_words, const void* ban, long ban_words) {
+    return vrt_head_impl(stream, hidden, ldh, embed_table, vocab, proto, n_proto, vrt_off, mode_table, step, logits_f32, ld_logits, part_val,
+                         part_idx, batch, D, eos, embed_table_packed, gen_cfg, seen, seen_words, ban, ban_words);
 }
 
 #if !PADT_OP16_F16   // type-independent: compiled once

@@ -192,6 +192,14 @@ class DecodeSession:
         # generation-config slots (device memory, so the captured graph does not bake them in) + per-row seen-token bitmap
         self.gen_cfg = ops.gen_cfg_tensor(1.0, (), device)
         self.seen = z(B, (cfg.vocab_size + np_max + 31) // 32, dt=I32)
+        # HF's pure-ban processors (no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens): the packed rule table, each
+        # row's prompt ids as the caller passed them (padding included: what HF's processors see) and the per-step ban bitmap ops.gen_rules
+        # rebuilds from them and `tokens` — all device memory at fixed addresses, read by the captured step
+        self.rules_on = False
+        self.rules = z(ops.GEN_RULES_INTS, dt=I32)
+        self.hist = z(B, s_max, dt=I32)
+        self.hist_len = z(B, dt=I32)
+        self.ban = z(B, self.seen.shape[1], dt=I32)
         self.err = z(1, dt=I32)
         self.nf = z(B, dt=I32)           # per row: a decode step produced a non-finite hidden row (fp16 operand overflow; ops.check_finite)
         self.nf_batch = z(B, dt=I32)     # per batch of the decode group (slot k): ViT rows / prototypes / prompt-pass rows not finite
@@ -256,14 +264,17 @@ class DecodeSession:
             if self.logits is None:
                 self.logits = torch.empty((self.B, (cfg.vocab_size + self.np_max + 3) // 4 * 4), device=hn.device, dtype=torch.float32)
             lg = self.logits
+        ban = None
+        if self.rules_on:                                    # this step's ban bitmap from the rows' histories; the head then writes -inf there
+            ban = ops.gen_rules(self.rules, self.hist, self.hist_len, self.tokens, self.step, self.ban, cfg.vocab_size + self.np_max)
         if hp is not None:                                   # packed table + packed hidden rows: 1 KiB contiguous wave loads
             ops.pack_rows(hn, self.hn_pk, self.B, to_packed=True)
             ops.vrt_head(self.hn_pk, W["llm.head"], self.proto, self.vrt_off, self.part_val, self.part_idx, cfg.eos_token_id,
                          mode_table=self.mode_table, step=self.step, table_packed=hp, rows=self.B, gen_cfg=self.gen_cfg,
-                         seen=self.seen, logits=lg)
+                         seen=self.seen, logits=lg, ban=ban)
         else:
             ops.vrt_head(hn, W["llm.head"], self.proto, self.vrt_off, self.part_val, self.part_idx, cfg.eos_token_id,
-                         mode_table=self.mode_table, step=self.step, gen_cfg=self.gen_cfg, seen=self.seen, logits=lg)
+                         mode_table=self.mode_table, step=self.step, gen_cfg=self.gen_cfg, seen=self.seen, logits=lg, ban=ban)
         hk = self.hooks
         if hk is not None and hk["processors"]:
             # padt.py:717 `next_token_scores = logits_processor(input_ids, next_token_logits)` with the CALLER's processors: they see the rows the head
@@ -313,7 +324,7 @@ class DecodeSession:
             for _ in range(n):
                 one_step()
             return
-        gkey = (self.do_sample, self.keep_scores, self.keep_logits, self.step_fn is not None)   # different kernel sequences → one captured graph per mode
+        gkey = (self.do_sample, self.keep_scores, self.keep_logits, self.step_fn is not None, self.rules_on)   # different kernel sequences → one captured graph per mode
         if gkey not in self.graphs:
             one_step()                                       # real step; also pays every one-time kernel attribute call
             n -= 1

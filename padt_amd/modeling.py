@@ -94,15 +94,17 @@ _GENERATE_IGNORED = {
     # GenerationConfig fields callers pass routinely and the reference's generate() accepts without effect on this path:
     "bos_token_id": None, "decoder_start_token_id": None, "return_legacy_cache": None,
     "num_beams": (1, None), "num_beam_groups": (1, None), "num_return_sequences": (1, None), "penalty_alpha": (None,), "min_new_tokens": (0, None),
-    "min_length": (0, None), "no_repeat_ngram_size": (0, None), "bad_words_ids": (None,), "force_words_ids": (None,), "token_healing": (False, None),
+    "min_length": (0, None), "force_words_ids": (None,), "token_healing": (False, None),
     "length_penalty": (1.0, None), "early_stopping": (False, None), "typical_p": (1.0, None), "min_p": (None,), "epsilon_cutoff": (0.0, None),
     "eta_cutoff": (0.0, None), "encoder_repetition_penalty": (1.0, None), "guidance_scale": (None, 1.0), "renormalize_logits": (False, None),
 }
 # arguments the reference honours (padt.py:418-424,445,511-533,570-580,719-737) and this path does not implement
+# ... and, through generate()'s NAMED parameters only, the four pure-ban processors: as a stray keyword of check_generate_kwargs they stay refused
+_GENERATE_NAMED_ONLY = ("no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens")
 _GENERATE_REJECTED = ("inputs", "prefix_allowed_tokens_fn", "assistant_model", "streamer",
                       "negative_prompt_ids", "negative_prompt_attention_mask", "pixel_values_videos", "video_grid_thw", "second_per_grid_ts",
                       "inputs_embeds", "past_key_values", "position_ids", "cache_position", "rope_deltas", "stop_strings", "max_time",
-                      "sequence_bias", "suppress_tokens", "begin_suppress_tokens", "forced_bos_token_id", "forced_eos_token_id",
+                      "sequence_bias", "forced_bos_token_id", "forced_eos_token_id",
                       "exponential_decay_length_penalty", "prompt_lookup_num_tokens", "dola_layers", "labels")
 
 
@@ -111,7 +113,7 @@ def check_generate_kwargs(kwargs: dict, max_new_tokens, max_length, prompt_len) 
     argument the reference honours and this path does not, ValueError (HF's _validate_model_kwargs wording) for an unknown one."""
     for k in list(kwargs):
         v = kwargs[k]
-        if k in _GENERATE_REJECTED:
+        if k in _GENERATE_REJECTED or k in _GENERATE_NAMED_ONLY:
             if v is None:
                 continue                                              # the reference's own default
             raise NotImplementedError(f"generate({k}=...) is not implemented on the MI355X path (the reference honours it, padt.py:414-580): "
@@ -131,6 +133,33 @@ def check_generate_kwargs(kwargs: dict, max_new_tokens, max_length, prompt_len) 
             return int(max_length) - int(prompt_len)
         return 1024
     return int(max_new_tokens)
+
+
+# generate()'s named parameters a generation_config may carry: an explicit argument (not None) wins, as in HF (padt.py:436)
+_GENERATE_CONFIG_NAMED = ("max_new_tokens", "max_length", "do_sample", "repetition_penalty", "eos_token_id", "pad_token_id", "temperature", "top_k",
+                          "top_p", "no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens")
+# ... and those whose value is this path's own default either way (hidden states and the dict output are what its callers consume)
+_GENERATE_CONFIG_OWN = ("use_cache", "output_hidden_states", "return_dict_in_generate")
+
+
+def generation_config_fields(generation_config) -> dict:
+    """generate(generation_config=): the fields a ``transformers.GenerationConfig`` sets to something other than its default (to_diff_dict),
+    or the entries of a dict; bookkeeping entries (``transformers_version``, ``_from_model_config`` …) are dropped.  Anything else is not a
+    generation config: NotImplementedError naming the argument."""
+    if generation_config is None:
+        return {}
+    if isinstance(generation_config, dict):
+        d = dict(generation_config)
+    else:
+        try:
+            from transformers import GenerationConfig
+        except ImportError:                                           # no transformers: only dicts can be configs
+            GenerationConfig = ()
+        if not (GenerationConfig and isinstance(generation_config, GenerationConfig)):
+            raise NotImplementedError(f"generate(generation_config={generation_config!r}) is not implemented on the MI355X path: pass a "
+                                      "transformers.GenerationConfig or a dict of its fields")
+        d = generation_config.to_diff_dict()
+    return {k: v for k, v in d.items() if not k.startswith("_") and k != "transformers_version" and v is not None}
 
 
 class PaDTForConditionalGeneration:
@@ -194,7 +223,8 @@ class PaDTForConditionalGeneration:
         # :570-580 logits processors / stopping criteria); from_pretrained fills it, explicit generate() kwargs override it
         self.generation_config = SimpleNamespace(repetition_penalty=1.0, eos_token_id=[config.eos_token_id],
                                                  pad_token_id=config.pad_token_id, do_sample=False, temperature=1.0,
-                                                 top_k=50, top_p=1.0)          # HF GenerationConfig defaults
+                                                 top_k=50, top_p=1.0, no_repeat_ngram_size=0, bad_words_ids=None,
+                                                 suppress_tokens=None, begin_suppress_tokens=None)          # HF GenerationConfig defaults
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -224,7 +254,8 @@ class PaDTForConditionalGeneration:
 
     def load_generation_config(self, d: dict):
         """generation_config.json → defaults of generate(), as HF's GenerationMixin applies them (padt.py:436): repetition_penalty,
-        eos_token_id (int or list), pad_token_id, do_sample / temperature / top_k / top_p."""
+        eos_token_id (int or list), pad_token_id, do_sample / temperature / top_k / top_p, and the pure-ban processors no_repeat_ngram_size /
+        bad_words_ids / suppress_tokens / begin_suppress_tokens."""
         g = self.generation_config
         if d.get("repetition_penalty") is not None:
             g.repetition_penalty = float(d["repetition_penalty"])
@@ -236,6 +267,13 @@ class PaDTForConditionalGeneration:
         for k, cast in (("do_sample", bool), ("temperature", float), ("top_k", int), ("top_p", float)):
             if d.get(k) is not None:
                 setattr(g, k, cast(d[k]))
+        if d.get("no_repeat_ngram_size") is not None:
+            g.no_repeat_ngram_size = int(d["no_repeat_ngram_size"])
+        if d.get("bad_words_ids") is not None:
+            g.bad_words_ids = [[int(i) for i in wd] for wd in d["bad_words_ids"]]
+        for k in ("suppress_tokens", "begin_suppress_tokens"):
+            if d.get(k) is not None:
+                setattr(g, k, [int(i) for i in d[k]])
         return g
 
     @classmethod
@@ -269,8 +307,20 @@ class PaDTForConditionalGeneration:
                  use_graph: bool = True, lane: int = 0, repetition_penalty: Optional[float] = None, eos_token_id=None,
                  temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  seed: Optional[int] = None, max_length: Optional[int] = None, output_scores: bool = False, output_logits: bool = False,
-                 pad_token_id: Optional[int] = None, logits_processor=None, stopping_criteria=None, **kwargs):
+                 pad_token_id: Optional[int] = None, logits_processor=None, stopping_criteria=None, no_repeat_ngram_size: Optional[int] = None,
+                 bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, generation_config=None, **kwargs):
         """Greedy generation over the unified text‖VRT vocabulary.
+
+        ``no_repeat_ngram_size`` / ``bad_words_ids`` / ``suppress_tokens`` / ``begin_suppress_tokens`` (padt.py:570-580 → HF's NoRepeatNGram /
+        NoBadWords / SuppressTokens / SuppressTokensAtBegin processors): pure bans, served ON THE DEVICE in every mode — one kernel per step
+        builds each row's ban bitmap from its history (the padded prompt row and the tokens so far, VRT ids included) inside the captured step,
+        and the logit head writes ``-inf`` there (before the repetition penalty, which a banned logit no longer needs; before the caller's
+        ``logits_processor``).  Rule ids must be text ids (< vocab_size); n-gram size and bad-word length at most 16, the packed rules at most
+        4096 ints — ``NotImplementedError`` beyond.  A row whose every candidate is banned continues with the pad token.  Defaults come from the
+        checkpoint's generation_config.json.
+        ``generation_config``: a ``transformers.GenerationConfig`` or a dict of its fields; every field it sets goes through the policy of the
+        same-named argument (so one with ``num_beams=4`` raises naming ``num_beams``), explicit arguments win over it, as in HF;
+        ``use_cache`` / ``output_hidden_states`` / ``return_dict_in_generate`` follow the call's own arguments.
 
         ``logits_processor`` / ``stopping_criteria`` (padt.py:422-423,570-580,717,752; round 6): HF ``LogitsProcessorList`` / ``StoppingCriteriaList``
         objects or plain lists of callables ``f(input_ids, scores)``.  They run where the reference runs them — the processors on the step's fp32
@@ -280,7 +330,7 @@ class PaDTForConditionalGeneration:
         inside ``pipeline.PipelinedRunner``'s merged decode groups.
 
         Arguments of the reference's ``generate`` (padt.py:414-434 + the HF generation kwargs it forwards) that this path does not
-        implement are REJECTED by name (``NotImplementedError``: ``streamer``, ``prefix_allowed_tokens_fn``, ``min_length``,
+        implement are REJECTED by name (``NotImplementedError``: ``streamer``, ``prefix_allowed_tokens_fn``, ``min_length``, ``min_new_tokens``,
         ``num_beams`` > 1, video inputs, ``inputs_embeds`` …), arguments that cannot change the
         result here are accepted and ignored (``use_cache``, ``attn_implementation``, ``synced_gpus=False`` …), anything else raises the
         ``ValueError`` HF's ``_validate_model_kwargs`` raises (padt.py:440) — a caller never gets silently different behaviour.
@@ -298,7 +348,7 @@ class PaDTForConditionalGeneration:
         ``do_sample=True`` also after HF's warpers, which are part of ``logits_processor`` there (padt.py:717-720): ``logits / temperature`` on
         the tokens top-k / top-p keep, ``-inf`` on every other one.  Stopping criteria that take scores get the same rows.
         ``output_logits=True`` (padt.py:721-724, the rows BEFORE the processors and warpers): served when no processor is active
-        (repetition_penalty == 1, no schedule — then, under greedy decoding, they ARE the scores), rejected otherwise.  ``pad_token_id``: must be the config's (the greedy kernel pads finished
+        (repetition_penalty == 1, no schedule, none of the four bans — then, under greedy decoding, they ARE the scores), rejected otherwise.  ``pad_token_id``: must be the config's (the greedy kernel pads finished
         rows with it, padt.py:749).
         ``do_sample=True``: multinomial sampling after HF's Temperature → TopK → TopP warpers (``temperature`` / ``top_k`` /
         ``top_p``, defaults from generation_config, HF's own defaults 1.0 / 50 / 1.0) on a device counter-based generator keyed
@@ -308,6 +358,23 @@ class PaDTForConditionalGeneration:
         if synced_gpus:
             raise NotImplementedError("generate(synced_gpus=True) is the ZeRO-3 / FSDP lock-step loop (padt.py:445,670): every rank holds a full "
                                       "replica on this path — pass synced_gpus=False")
+        if generation_config is not None:
+            named = dict(max_new_tokens=max_new_tokens, max_length=max_length, do_sample=do_sample, repetition_penalty=repetition_penalty,
+                         eos_token_id=eos_token_id, pad_token_id=pad_token_id, temperature=temperature, top_k=top_k, top_p=top_p,
+                         no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens,
+                         begin_suppress_tokens=begin_suppress_tokens)
+            for k, v in generation_config_fields(generation_config).items():
+                if k in _GENERATE_CONFIG_NAMED:
+                    if named[k] is None:
+                        named[k] = v
+                elif k == "output_scores":
+                    output_scores = output_scores or bool(v)
+                elif k == "output_logits":
+                    output_logits = output_logits or bool(v)
+                elif k not in _GENERATE_CONFIG_OWN:
+                    kwargs.setdefault(k, v)                           # the keyword policy below names what this path does not implement
+            (max_new_tokens, max_length, do_sample, repetition_penalty, eos_token_id, pad_token_id, temperature, top_k, top_p, no_repeat_ngram_size,
+             bad_words_ids, suppress_tokens, begin_suppress_tokens) = (named[k] for k in _GENERATE_CONFIG_NAMED)
         max_new_tokens = check_generate_kwargs(kwargs, max_new_tokens, max_length, None if input_ids is None else input_ids.shape[1])
         if pad_token_id is not None and int(pad_token_id) != int(self.generation_config.pad_token_id):
             raise NotImplementedError(f"generate(pad_token_id={pad_token_id}): finished rows are padded with the checkpoint's pad token "
@@ -323,11 +390,13 @@ class PaDTForConditionalGeneration:
             if float(pen) != 1.0 or schedule is not None or processors is not None:
                 raise NotImplementedError("generate(output_logits=True) with a logits processor active (repetition_penalty != 1, a schedule or a "
                                           "logits_processor): only the processed rows are kept on this path — ask for output_scores=True")
+            # ... and so are the four bans under greedy decoding: generate_launch refuses there, where the defaults and the EOS filter are known
         ctx = self.generate_launch(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, do_sample,
                                    schedule, sync_every, use_graph, lane, repetition_penalty=repetition_penalty,
                                    eos_token_id=eos_token_id, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
                                    keep_scores=bool(output_scores or output_logits or hooks is not None), hooks=hooks,
-                                   keep_logits=bool(output_logits))
+                                   keep_logits=bool(output_logits), no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
+                                   suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens)
         return self.generate_collect(ctx, output_hidden_states, return_dict_in_generate, output_scores=bool(output_scores),
                                      output_logits=bool(output_logits))
 
@@ -335,7 +404,8 @@ class PaDTForConditionalGeneration:
     def generate_launch(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens=1024, do_sample=None,
                         schedule=None, sync_every=16, use_graph=True, lane=0, decode_stream=None, group=None, n_slots=1,
                         repetition_penalty=None, eos_token_id=None, temperature=None, top_k=None, top_p=None, seed=None,
-                        vit_stream=None, inputs_ready=None, keep_scores=False, hooks=None, keep_logits=False):
+                        vit_stream=None, inputs_ready=None, keep_scores=False, hooks=None, keep_logits=False, no_repeat_ngram_size=None,
+                        bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None):
         """Asynchronous half of generate(): host integer prep + every kernel up to the first host sync point, enqueued on
         the current stream (the decode steps on ``decode_stream`` if given, ordered after the prefill by an event).
         Returns a group context for generate_collect().
@@ -352,7 +422,8 @@ class PaDTForConditionalGeneration:
         if owner is not self:
             return owner.generate_launch(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, do_sample, schedule, sync_every,
                                          use_graph, lane, decode_stream, group, n_slots, repetition_penalty, eos_token_id, temperature, top_k, top_p,
-                                         seed, vit_stream, inputs_ready, keep_scores, hooks, keep_logits)
+                                         seed, vit_stream, inputs_ready, keep_scores, hooks, keep_logits, no_repeat_ngram_size, bad_words_ids,
+                                         suppress_tokens, begin_suppress_tokens)
         self._batches_seen += 1
         gc = self.generation_config
         do_sample = gc.do_sample if do_sample is None else do_sample
@@ -377,8 +448,16 @@ class PaDTForConditionalGeneration:
         if cfg.eos_token_id not in eos_list or len(eos_list) > 4:
             raise NotImplementedError("eos_token_id must contain config.eos_token_id and hold at most 4 ids")
         samp = (float(temperature), int(top_k), float(top_p), int(seed)) if do_sample else None
+        # the four pure bans in canonical form (None: nothing banned — then no kernel is added and the head gets no bitmap)
+        dflt = lambda name, v: getattr(gc, name, None) if v is None else v
+        rules = ops.gen_rules_key(dflt("no_repeat_ngram_size", no_repeat_ngram_size), dflt("bad_words_ids", bad_words_ids),
+                                  dflt("suppress_tokens", suppress_tokens), dflt("begin_suppress_tokens", begin_suppress_tokens),
+                                  eos_ids=eos_list, vocab_size=cfg.vocab_size)
+        if keep_logits and rules is not None and samp is None:
+            raise NotImplementedError("generate(output_logits=True) with a logits processor active (no_repeat_ngram_size, bad_words_ids, suppress_tokens "
+                                      "or begin_suppress_tokens): only the processed rows are kept on this path — ask for output_scores=True")
         # under sampling the scores are the warped rows (sample_token writes them back), so output_logits needs a stash of its own
-        gen_key = (float(repetition_penalty), tuple(eos_list), samp, bool(keep_scores), bool(keep_logits) and samp is not None)
+        gen_key = (float(repetition_penalty), tuple(eos_list), samp, bool(keep_scores), bool(keep_logits) and samp is not None, rules)
         grid = image_grid_thw.detach().cpu().long()
         B = input_ids.shape[0]
         T_max = int(max_new_tokens)
@@ -388,6 +467,8 @@ class PaDTForConditionalGeneration:
         plan = plan_prompt(cfg, input_ids, attention_mask, grid, dev, row0=row0, proto_row0=proto_row0)
         n_proto = plan.vrt_off[-1]
         need_s = max(plan.lens) + T_max
+        if rules is not None:
+            need_s = max(need_s, plan.L_pad)                      # the session's history rows hold the padded prompt row
         if hooks is not None and (group is not None or n_slots != 1):
             raise NotImplementedError("logits_processor / stopping_criteria run on generate()'s own (un-merged) decode loop, not inside a merged decode group")
         if group is None:
@@ -402,6 +483,10 @@ class PaDTForConditionalGeneration:
             sess.do_sample = samp is not None
             sess.keep_scores = bool(keep_scores)
             sess.keep_logits = gen_key[4]
+            sess.rules_on = rules is not None
+            if rules is not None:
+                sess.rules.copy_(ops.gen_rules_tensor(key=rules).to(dev, non_blocking=True))
+                sess.hist_len.zero_()                             # rows no batch of the group fills: an empty prompt
             sess.hooks = None
             if hooks is not None:
                 ids_dev = input_ids.detach().to(dev).long().contiguous()
@@ -483,13 +568,17 @@ class PaDTForConditionalGeneration:
         sess.lens[rows].copy_((lens_t + 1).to(dev, non_blocking=True))  # keys visible to the next token
         sess.pos3[:, rows].copy_(torch.tensor([plan.next_pos] * 3, dtype=torch.int32).to(dev, non_blocking=True))
         self.rope_deltas = plan.rope_deltas
-        if gen_key[0] != 1.0:
-            # RepetitionPenaltyLogitsProcessor sees the caller's full (B, L) input_ids, padding included
+        if gen_key[0] != 1.0 or rules is not None:
+            # HF's logits processors see the caller's full (B, L) input_ids, padding included
             ids_full = input_ids.detach().to(dev).long()
             if proto_row0:
                 ids_full = torch.where(ids_full >= cfg.vocab_size, ids_full + proto_row0, ids_full)
+        if gen_key[0] != 1.0:
             rws = (torch.arange(B, device=dev, dtype=torch.int32) + row0)[:, None].expand(B, ids_full.shape[1]).contiguous()
             ops.seen_init(ids_full.reshape(-1).contiguous(), rws.reshape(-1), sess.seen)
+        if rules is not None:
+            sess.hist[rows, : plan.L_pad].copy_(ids_full)         # int64 → int32 (ids are table rows)
+            sess.hist_len[rows].fill_(plan.L_pad)
 
         # ---- prefill; the first token is selected together with the other batches of the group (launch_decode)
         if self.ref is not None:
@@ -620,6 +709,10 @@ class PaDTForConditionalGeneration:
                           "instantiation" % (self.overflow_reruns, self._batches_seen), RuntimeWarning, stacklevel=3)
         am, pix, grid = sub["inputs"]
         pen, eos, samp = group["gen_key"][:3]
+        n_gram, static, begin, words = group["gen_key"][5] or (0, (), (), ())
+        # the canonical rules, explicit (an empty list is "off", not "the default"): the 1-token bad words travel as suppress_tokens
+        kw_rules = dict(no_repeat_ngram_size=n_gram, bad_words_ids=[list(wd) for wd in words], suppress_tokens=list(static),
+                        begin_suppress_tokens=list(begin))
         kw = dict(do_sample=False)
         if samp is not None:
             kw = dict(do_sample=True, temperature=samp[0], top_k=samp[1], top_p=samp[2], seed=samp[3])
@@ -629,7 +722,7 @@ class PaDTForConditionalGeneration:
                            schedule=group["schedule"], sync_every=group["sync_every"], use_graph=group["use_graph"], lane=("fb", group["lane"]),
                            repetition_penalty=pen, eos_token_id=list(eos), output_hidden_states=output_hidden_states,
                            return_dict_in_generate=return_dict_in_generate,
-                           output_scores=bool(group["gen_key"][3]) and (group.get("hooks") is None or group["hooks"]["pass_scores"]), **kw)
+                           output_scores=bool(group["gen_key"][3]) and (group.get("hooks") is None or group["hooks"]["pass_scores"]), **kw_rules, **kw)
 
     # ------------------------------------------------------------------ vl_decode (padt.py:342-412)
     @torch.no_grad()

@@ -1,5 +1,7 @@
 """Thin torch-tensor → C-ABI wrappers.  PyTorch is used for device memory and streams only; every arithmetic op below
 is a hand-written gfx950 kernel in libpadt_hip.so (see include/padt_hip.h).  No fallbacks."""
+import operator
+
 import torch
 
 from . import _lib
@@ -708,21 +710,123 @@ def vrt_head_nblk(vocab, n_proto):
 
 
 def vrt_head(hidden, table, proto, vrt_off, part_val, part_idx, eos, mode_table=None, step=None, logits=None,
-             table_packed=None, rows=None, gen_cfg=None, seen=None):
-    """table_packed: pack_weight(table) — then `hidden` is a fragment-packed activation buffer holding `rows` valid rows."""
+             table_packed=None, rows=None, gen_cfg=None, seen=None, ban=None):
+    """table_packed: pack_weight(table) — then `hidden` is a fragment-packed activation buffer holding `rows` valid rows.
+    ban: int32 (rows, words) bitmap of banned table rows (gen_rules) → padt_vrt_head_ban; None is padt_vrt_head itself."""
     dt = _x16(hidden, table, proto, table_packed)
     B = hidden.shape[0] if rows is None else rows
-    _lib.check(_fn("padt_vrt_head", dt)(_stream(), _p(hidden), hidden.stride(0), _p(table), table.shape[0], _p(proto),
-                                 proto.shape[0], _p(vrt_off), _p(mode_table), _p(step), _p(logits),
-                                 logits.stride(0) if logits is not None else 0, _p(part_val), _p(part_idx),
-                                 B, hidden.shape[1], eos, _p(table_packed), _p(gen_cfg), _p(seen),
-                                 seen.shape[1] if seen is not None else 0), "padt_vrt_head")
+    name, extra = "padt_vrt_head", ()
+    if ban is not None:
+        assert ban.dtype == torch.int32 and ban.is_cuda and ban.dim() == 2 and ban.is_contiguous() and ban.shape[0] >= B
+        name, extra = "padt_vrt_head_ban", (_p(ban), ban.shape[1])
+    _lib.check(_fn(name, dt)(_stream(), _p(hidden), hidden.stride(0), _p(table), table.shape[0], _p(proto),
+                             proto.shape[0], _p(vrt_off), _p(mode_table), _p(step), _p(logits),
+                             logits.stride(0) if logits is not None else 0, _p(part_val), _p(part_idx),
+                             B, hidden.shape[1], eos, _p(table_packed), _p(gen_cfg), _p(seen),
+                             seen.shape[1] if seen is not None else 0, *extra), name)
 
 
 def seen_init(ids, rows, seen):
     """ids int64 (n,), rows int32 (n,) device tensors: set bit ids[i] in seen[rows[i]] (prompt tokens of a generate call)."""
     assert ids.dtype == torch.int64 and rows.dtype == torch.int32 and ids.numel() == rows.numel() and seen.dtype == torch.int32
     _lib.check(_lib.load().padt_seen_init(_stream(), _p(ids), _p(rows), ids.numel(), _p(seen), seen.shape[1]), "padt_seen_init")
+
+
+GEN_RULES_INTS = 4096      # the packed rule table: fixed size, so a session's copy never moves (captured graphs read it)
+GEN_RULES_MAX_NGRAM = 16
+GEN_RULES_MAX_WORD = 16
+
+
+def _rule_ids(name, ids, vocab_size):
+    out = []
+    for i in ids:
+        try:
+            if isinstance(i, bool):
+                raise TypeError
+            i = operator.index(i)                                    # Python / numpy integers and one-element integer tensors
+        except TypeError:
+            raise ValueError(f"{name}: token ids must be integers, got {i!r}") from None
+        if i < 0:
+            raise ValueError(f"{name}: token ids must be non-negative, got {i}")
+        if vocab_size is not None and i >= vocab_size:
+            raise NotImplementedError(f"{name}: id {i} is not a text id (< {vocab_size}): VRT ids are numbered per batch and cannot be named in a rule")
+        out.append(i)
+    return out
+
+
+def gen_rules_key(no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, eos_ids=(), vocab_size=None):
+    """The canonical form of HF's four pure-ban generate arguments: (n, static ids, begin ids, words) — sorted tuples without duplicates, static
+    = suppress_tokens and the 1-token bad words (HF's NoBadWordsLogitsProcessor drops those equal to an EOS id: so does this), words = the
+    bad words of two ids and more — or None when nothing is banned.  Raises by argument name: NotImplementedError above the kernel's caps
+    (n-gram size / word length 16, the packed table GEN_RULES_INTS ints) and for ids that are not text ids, ValueError for malformed values."""
+    n = 0 if no_repeat_ngram_size is None else no_repeat_ngram_size
+    try:
+        n = -1 if isinstance(n, bool) else operator.index(n)
+    except TypeError:
+        n = -1
+    if n < 0:
+        raise ValueError(f"no_repeat_ngram_size has to be a non-negative integer, got {no_repeat_ngram_size!r}")
+    if n > GEN_RULES_MAX_NGRAM:
+        raise NotImplementedError(f"no_repeat_ngram_size={n}: at most {GEN_RULES_MAX_NGRAM} on the MI355X path")
+    static = set(_rule_ids("suppress_tokens", suppress_tokens if suppress_tokens is not None else (), vocab_size))
+    begin = set(_rule_ids("begin_suppress_tokens", begin_suppress_tokens if begin_suppress_tokens is not None else (), vocab_size))
+    words = set()
+    eos = {int(e) for e in eos_ids}
+    for wd in (bad_words_ids if bad_words_ids is not None else ()):
+        if isinstance(wd, (int, str)) or len(wd) == 0:
+            raise ValueError(f"bad_words_ids has to be a list of non-empty lists of token ids, got {bad_words_ids!r}")
+        wd = _rule_ids("bad_words_ids", wd, vocab_size)
+        if len(wd) > GEN_RULES_MAX_WORD:
+            raise NotImplementedError(f"bad_words_ids: a bad word of {len(wd)} ids; at most {GEN_RULES_MAX_WORD} on the MI355X path")
+        if len(wd) == 1:
+            if wd[0] not in eos:
+                static.add(wd[0])
+        else:
+            words.add(tuple(wd))
+    key = (int(n), tuple(sorted(static)), tuple(sorted(begin)), tuple(sorted(words)))
+    size = 4 + len(key[1]) + len(key[2]) + len(key[3]) + sum(1 + len(w) for w in key[3])
+    if size > GEN_RULES_INTS:
+        raise NotImplementedError(f"bad_words_ids / suppress_tokens / begin_suppress_tokens: the packed rule table takes {size} ints; "
+                                  f"at most {GEN_RULES_INTS} on the MI355X path")
+    return key if (n or key[1] or key[2] or key[3]) else None
+
+
+def gen_rules_tensor(no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, eos_ids=(), vocab_size=None,
+                     key=None):
+    """→ the int32 CPU rule table padt_gen_rules reads (GEN_RULES_INTS ints, zero-padded; layout in include/padt_hip.h) for the arguments as
+    gen_rules_key() canonicalises them, or for an already canonical `key`."""
+    if key is None:
+        key = gen_rules_key(no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens, eos_ids, vocab_size)
+    n, static, begin, words = key if key is not None else (0, (), (), ())
+    t = [n, len(static), len(begin), len(words), *static, *begin]
+    o = len(t) + len(words)
+    offs, recs = [], []
+    for w in words:
+        offs.append(o + len(recs))
+        recs += [len(w), *w]
+    t += offs + recs
+    assert len(t) <= GEN_RULES_INTS
+    return torch.tensor(t + [0] * (GEN_RULES_INTS - len(t)), dtype=torch.int32)
+
+
+def gen_rules_unpack(table):
+    """Inverse of gen_rules_tensor → the canonical (n, static ids, begin ids, words)."""
+    t = table.tolist()
+    n, ns, nb, nw = t[:4]
+    o = 4 + ns + nb
+    return (n, tuple(t[4: 4 + ns]), tuple(t[4 + ns: o]), tuple(tuple(t[f + 1: f + 1 + t[f]]) for f in t[o: o + nw]))
+
+
+def gen_rules(rules, hist, hist_len, tokens, step, ban, n_cols):
+    """ban[b] = the step's bitmap of banned table rows for every row b of hist (padt_gen_rules): rules int32 (GEN_RULES_INTS,) device copy of
+    gen_rules_tensor, hist int32 (B, >= hist_len) prompt ids, tokens int64 (B, T) the generated ids, step the device step counter."""
+    assert rules.dtype == torch.int32 and rules.is_cuda and rules.is_contiguous() and rules.numel() >= GEN_RULES_INTS
+    assert hist.dtype == torch.int32 and hist.stride(1) == 1 and hist_len.dtype == torch.int32 and hist_len.numel() >= hist.shape[0]
+    assert tokens.dtype == torch.int64 and tokens.stride(1) == 1 and tokens.shape[0] >= hist.shape[0] and step.dtype == torch.int32
+    assert ban.dtype == torch.int32 and ban.is_contiguous() and ban.shape[0] >= hist.shape[0]
+    _lib.check(_lib.load().padt_gen_rules(_stream(), _p(rules), _p(hist), hist.stride(0), _p(hist_len), _p(tokens), tokens.stride(0), _p(step),
+                                          _p(ban), ban.shape[1], int(n_cols), hist.shape[0]), "padt_gen_rules")
+    return ban
 
 
 def gen_cfg_tensor(repetition_penalty=1.0, eos_ids=(), device="cuda", do_sample=False, seed=0, temperature=1.0, top_k=0, top_p=1.0,

@@ -81,7 +81,8 @@ class PipelinedRunner:
         self.pending.append(g)
 
     def submit(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens=1024, schedule=None,
-               need_thinking_mask=None, sync_every=None, repetition_penalty=None, eos_token_id=None, **sampling):
+               need_thinking_mask=None, sync_every=None, repetition_penalty=None, eos_token_id=None, no_repeat_ngram_size=None,
+               bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, **sampling):
         done = []
         bid = self.n_batches
         self.n_batches += 1
@@ -113,6 +114,8 @@ class PipelinedRunner:
                                                  sched, sync_every or max_new_tokens, self.use_graph, g["lane"],
                                                  self.decode_streams[g["lane"]], group=g["ctx"], n_slots=self.merge,
                                                  repetition_penalty=repetition_penalty, eos_token_id=eos_token_id,
+                                                 no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
+                                                 suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
                                                  vit_stream=self.vit_stream, inputs_ready=ev_in, **sampling)
             if ctx is not None:
                 break

@@ -11,7 +11,10 @@ window is reported with the extremes.  Prints one JSON line per case:
   bytes_per_step   weight_bytes + the 16-bit head table + the K and V rows the step reads
   TB_per_s         bytes_per_step / median step time
 
-usage: python tools/bench_decode_weights.py [--models 3b,7b] [--rows 8,64] [--weights bf16,fp8,fp4] [--operands fp16|bf16]"""
+--rules adds the device-side bans of generate() to the step (ops.gen_rules in front of the head, the head reading the ban bitmap):
+no_repeat_ngram_size=3, 8 two-token bad words and 16 suppressed ids over a random prompt history of `--context` ids per row.
+
+usage: python tools/bench_decode_weights.py [--models 3b,7b] [--rows 8,64] [--weights bf16,fp8,fp4] [--operands fp16|bf16] [--rules]"""
 import argparse
 import json
 import os
@@ -71,6 +74,12 @@ def time_case(cfg, mode, rows, op16, args, device):
     sess = DecodeSession(cfg, W, rows, s_max, 16, window + 1, device)
     g = torch.Generator(device=device).manual_seed(1)
     first = torch.randint(0, cfg.vocab_size, (rows,), generator=g, device=device)
+    if args.rules:
+        ids = torch.randint(0, cfg.vocab_size, (40,), generator=g, device=device).tolist()
+        sess.rules.copy_(ops.gen_rules_tensor(3, [ids[2 * i: 2 * i + 2] for i in range(8)], ids[16: 32], vocab_size=cfg.vocab_size))
+        sess.hist[:, : args.context] = torch.randint(0, cfg.vocab_size, (rows, args.context), generator=g, device=device).to(torch.int32)
+        sess.hist_len.fill_(args.context)
+        sess.rules_on = True
 
     def reset():
         """`context` cached tokens per row, step counter at zero: every window replays the same steps (a window never runs past s_max / t_max)."""
@@ -98,7 +107,7 @@ def time_case(cfg, mode, rows, op16, args, device):
     kv = rows * (args.context + args.steps / 2.0) * 2 * cfg.num_key_value_heads * cfg.head_dim * 2 * cfg.num_hidden_layers
     step_bytes = wbytes + head.numel() * head.element_size() + kv
     med = statistics.median(us)
-    return {"weights": mode, "rows": rows, "layers": cfg.num_hidden_layers, "hidden": cfg.hidden_size, "operands": str(op16).split(".")[-1],
+    return {"weights": mode, "rules": bool(args.rules), "rows": rows, "layers": cfg.num_hidden_layers, "hidden": cfg.hidden_size, "operands": str(op16).split(".")[-1],
             "context": args.context, "us_per_step": round(med, 1), "us_min": round(min(us), 1), "us_max": round(max(us), 1),
             "windows": args.repeats, "steps_per_window": args.steps, "weight_bytes": int(wbytes), "bytes_per_step": int(step_bytes),
             "TB_per_s": round(step_bytes / (med * 1e-6) / 1e12, 3), "weight_TB_per_s": round(wbytes / (med * 1e-6) / 1e12, 3)}
@@ -114,6 +123,7 @@ def main():
     ap.add_argument("--steps", type=int, default=32, help="graph replays per timed window")
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--rules", action="store_true", help="n-gram, bad-word and suppress-token bans active in the step")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_decode_weights.py times kernels on an MI355X: no GPU found")
