@@ -232,6 +232,17 @@ int padt_llm_qkv_post(void* stream, const void* qkv, long ld_qkv, const int* pos
                       const int* lens, const void* inv_freq, void* q_out, long ld_q, void* k_pack, long ld_kp,
                       void* k_cache, void* vt_cache, long T, int n_heads, int n_kv_heads, int head_dim, int s_max,
                       int sec0, int sec1, int cache_packed);
+/* padt_llm_qkv_post with FAN-OUT, for a prompt pass over a shared token set (several queries on one image: the common prompt prefix is
+ * computed once).  Token t is rotated once and its q row written once, exactly as padt_llm_qkv_post does; its roped K row and its V row go
+ * to every destination n in [dst_off[t], dst_off[t+1]) (CSR, dst_off has T + 1 entries): the K / V^T cache image of session row
+ * dst_sample[n] at slot dst_slot[n] (cache_packed as above; skipped unless 0 <= sample < batch and 0 <= slot < s_max) and row dst_row[n] of
+ * the row-major join buffers k_join / v_join [n_join][n_kv_heads * head_dim] (skipped unless 0 <= row < n_join), which padt_attn_varlen
+ * then reads as k and v.  Every destination receives bit for bit what padt_llm_qkv_post writes for a copy of the token's qkv row.
+ * Returns -1 without launching on a null pointer or bad dimensions. */
+int padt_llm_qkv_post_shared(void* stream, const void* qkv, long ld_qkv, const int* pos3, const void* inv_freq, void* q_out, long ld_q,
+                             void* k_join, long ld_kj, void* v_join, long ld_vj, long n_join, void* k_cache, void* vt_cache,
+                             const int* dst_off, const int* dst_sample, const int* dst_slot, const int* dst_row, long T, int n_heads,
+                             int n_kv_heads, int head_dim, int s_max, int batch, int sec0, int sec1, int cache_packed);
 /* PaDT mask head tail: per-patch 4x4 dot with the object's mask token, scattered to (n_obj, 4H, 4W) fp32.
  * padt_decoder.py:241-274. */
 int padt_mask_scatter(void* stream, const void* e2, long ld_e2, const void* mask_tok, long ld_tok, const int* cu_patch,

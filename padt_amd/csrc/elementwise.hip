@@ -664,6 +664,161 @@ extern "C" int PADT_TWIN(padt_llm_qkv_post)(void* stream, const void* qkv, long 
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The same post-processing with FAN-OUT (prompt pass over a shared token set: one image's prompt prefix computed once for every query on
+// it, llm.plan_prompt_shared).  Token t is rotated ONCE — the angles, rope_lo / rope_hi expressions and the single rounding of
+// llm_qkv_post_kernel — its q row is written once, and its roped K row / V row go to every destination n in [dst_off[t], dst_off[t+1]):
+//   * cache image of session row dst_sample[n] at slot dst_slot[n] (both cache forms), skipped when either is out of range;
+//   * row dst_row[n] of the row-major join buffers k_join / v_join (the k / v operands of the prompt pass's attn_varlen), skipped when
+//     the row is outside [0, n_join).
+// What a destination receives is bit for bit what llm_qkv_post_kernel writes for a copy of the token's qkv row: pure data movement.
+struct QkvPostSharedArgs {
+    const x16_t* qkv; long ld;
+    const int* pos;            // [3][T]
+    const float* inv_freq;     // [D/2]
+    x16_t* q_out; long ld_q;
+    x16_t* k_join; long ld_kj; // [n_join][Hkv*D] roped K rows
+    x16_t* v_join; long ld_vj; // [n_join][Hkv*D] V rows
+    x16_t* kc; x16_t* vtc;     // caches
+    const int* dst_off;        // [T+1] CSR offsets into the three lists below
+    const int* dst_sample; const int* dst_slot; const int* dst_row;
+    int T, Hq, Hkv, D, S_max, B, n_join, sec0, sec1, cache_packed;
+};
+
+__global__ __launch_bounds__(256) void llm_qkv_post_shared_kernel(QkvPostSharedArgs p) {
+    __shared__ float cs[2][128];                                  // cos / sin of this token's D/2 angles (D <= 256)
+    const int t = blockIdx.x;
+    const int half = p.D >> 1;
+    const int n0 = p.dst_off[t], n1 = p.dst_off[t + 1];
+    const x16_t* row = p.qkv + (long)t * p.ld;
+    for (int d = threadIdx.x; d < half; d += blockDim.x) {
+        const int axis = d < p.sec0 ? 0 : (d < p.sec0 + p.sec1 ? 1 : 2);
+        const float ang = (float)p.pos[(long)axis * p.T + t] * p.inv_freq[d];
+        cs[0][d] = cosf(ang);
+        cs[1][d] = sinf(ang);
+    }
+    __syncthreads();
+    auto cache_ok = [&](int n) { return (unsigned)p.dst_sample[n] < (unsigned)p.B && (unsigned)p.dst_slot[n] < (unsigned)p.S_max; };
+    auto join_ok = [&](int n) { return (unsigned)p.dst_row[n] < (unsigned)p.n_join; };
+    const bool vec = (half & 7) == 0 && (p.ld & 7) == 0 && (p.ld_q & 7) == 0 && (p.ld_kj & 7) == 0 && (p.ld_vj & 7) == 0;
+    if (vec) {
+        // 16-byte path: item = (head, 8-wide chunk of the first half); its partner chunk sits D/2 further
+        const int cph = half >> 3;
+        const int items = (p.Hq + p.Hkv) * cph;
+        for (int i = threadIdx.x; i < items; i += blockDim.x) {
+            const int h = i / cph, d = (i % cph) * 8;
+            const x16_t* x = row + (long)h * p.D + d;
+            float x1[8], x2[8], o1[8], o2[8];
+            unpack8(*reinterpret_cast<const u32x4*>(x), x1);
+            unpack8(*reinterpret_cast<const u32x4*>(x + half), x2);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float c = cs[0][d + e], sn = cs[1][d + e];
+                o1[e] = rope_lo(x1[e], x2[e], c, sn);
+                o2[e] = rope_hi(x1[e], x2[e], c, sn);
+            }
+            const u32x4 r1 = pack8(o1), r2 = pack8(o2);
+            if (h < p.Hq) {
+                x16_t* q = p.q_out + (long)t * p.ld_q + (long)h * p.D + d;
+                *reinterpret_cast<u32x4*>(q) = r1;
+                *reinterpret_cast<u32x4*>(q + half) = r2;
+                continue;
+            }
+            const int g = h - p.Hq;
+            for (int n = n0; n < n1; ++n) {
+                if (cache_ok(n)) {
+                    const int slot = p.dst_slot[n];
+                    x16_t* kc = p.kc + ((long)p.dst_sample[n] * p.Hkv + g) * p.S_max * p.D;
+                    *reinterpret_cast<u32x4*>(kc + kc_offset(slot, d, p.D, p.cache_packed)) = r1;
+                    *reinterpret_cast<u32x4*>(kc + kc_offset(slot, d + half, p.D, p.cache_packed)) = r2;
+                }
+                if (join_ok(n)) {
+                    x16_t* kj = p.k_join + (long)p.dst_row[n] * p.ld_kj + (long)g * p.D + d;
+                    *reinterpret_cast<u32x4*>(kj) = r1;
+                    *reinterpret_cast<u32x4*>(kj + half) = r2;
+                }
+            }
+        }
+    } else {
+        const int nqk = (p.Hq + p.Hkv) * half;
+        for (int i = threadIdx.x; i < nqk; i += blockDim.x) {
+            const int h = i / half, d = i % half;
+            const float c = cs[0][d], s = cs[1][d];
+            const x16_t* x = row + (long)h * p.D;
+            const float x1 = x2f(x[d]), x2 = x2f(x[d + half]);
+            const x16_t o1 = f2x(rounded32(rope_lo(x1, x2, c, s))), o2 = f2x(rounded32(rope_hi(x1, x2, c, s)));
+            if (h < p.Hq) {
+                x16_t* q = p.q_out + (long)t * p.ld_q + (long)h * p.D;
+                q[d] = o1; q[d + half] = o2;
+                continue;
+            }
+            const int g = h - p.Hq;
+            for (int n = n0; n < n1; ++n) {
+                if (cache_ok(n)) {
+                    const int slot = p.dst_slot[n];
+                    x16_t* kc = p.kc + ((long)p.dst_sample[n] * p.Hkv + g) * p.S_max * p.D;
+                    kc[kc_offset(slot, d, p.D, p.cache_packed)] = o1; kc[kc_offset(slot, d + half, p.D, p.cache_packed)] = o2;
+                }
+                if (join_ok(n)) {
+                    x16_t* kj = p.k_join + (long)p.dst_row[n] * p.ld_kj + (long)g * p.D;
+                    kj[d] = o1; kj[d + half] = o2;
+                }
+            }
+        }
+    }
+    const x16_t* v = row + (long)(p.Hq + p.Hkv) * p.D;
+    const int nv = p.Hkv * p.D;
+    for (int n = n0; n < n1; ++n) {
+        if (cache_ok(n)) {
+            const int b = p.dst_sample[n], slot = p.dst_slot[n];
+            for (int i = threadIdx.x; i < nv; i += blockDim.x) {
+                const int g = i / p.D, d = i % p.D;
+                p.vtc[((long)b * p.Hkv + g) * p.D * p.S_max + vtc_offset(slot, d, p.S_max, p.cache_packed)] = v[i];
+            }
+        }
+        if (join_ok(n)) {
+            x16_t* vj = p.v_join + (long)p.dst_row[n] * p.ld_vj;
+            if (vec) {                                            // D % 16 == 0 here: the V part of the row starts on a 16-byte boundary
+                for (int i = threadIdx.x * 8; i < nv; i += blockDim.x * 8)
+                    *reinterpret_cast<u32x4*>(vj + i) = *reinterpret_cast<const u32x4*>(v + i);
+            } else {
+                for (int i = threadIdx.x; i < nv; i += blockDim.x) vj[i] = v[i];
+            }
+        }
+    }
+}
+
+extern "C" int PADT_TWIN(padt_llm_qkv_post_shared)(void* stream, const void* qkv, long ld_qkv, const int* pos3, const void* inv_freq,
+                                        void* q_out, long ld_q, void* k_join, long ld_kj, void* v_join, long ld_vj, long n_join,
+                                        void* k_cache, void* vt_cache, const int* dst_off, const int* dst_sample,
+                                        const int* dst_slot, const int* dst_row, long T, int n_heads, int n_kv_heads,
+                                        int head_dim, int s_max, int batch, int sec0, int sec1, int cache_packed) {
+    if (!qkv || !pos3 || !inv_freq || !q_out || !k_join || !v_join || !k_cache || !vt_cache || !dst_off || !dst_sample || !dst_slot ||
+        !dst_row) {
+        padt_set_error("padt_llm_qkv_post_shared: null pointer argument");
+        return -1;
+    }
+    if (T < 0 || n_join <= 0 || n_join > 0x7fffffffL || T > 0x7fffffffL || n_heads <= 0 || n_kv_heads <= 0 || s_max <= 0 || batch <= 0 ||
+        sec0 < 0 || sec1 < 0 || sec0 + sec1 > head_dim / 2) {
+        padt_set_error("padt_llm_qkv_post_shared: bad dimensions");
+        return -1;
+    }
+    if (head_dim <= 0 || head_dim > 256 || (head_dim & 1)) { padt_set_error("padt_llm_qkv_post_shared: head_dim must be even and <= 256"); return -1; }
+    const long row = (long)(n_heads + 2 * n_kv_heads) * head_dim, kv = (long)n_kv_heads * head_dim;
+    if (ld_qkv < row || ld_q < (long)n_heads * head_dim || ld_kj < kv || ld_vj < kv) {
+        padt_set_error("padt_llm_qkv_post_shared: a row stride is shorter than its row");
+        return -1;
+    }
+    if (cache_packed && ((head_dim & 31) || (s_max & 31))) { padt_set_error("padt_llm_qkv_post_shared: packed caches need head_dim % 32 == 0 and s_max % 32 == 0"); return -1; }
+    if (T == 0) return 0;
+    QkvPostSharedArgs a{(const x16_t*)qkv, ld_qkv, pos3, (const float*)inv_freq, (x16_t*)q_out, ld_q, (x16_t*)k_join, ld_kj,
+                        (x16_t*)v_join, ld_vj, (x16_t*)k_cache, (x16_t*)vt_cache, dst_off, dst_sample, dst_slot, dst_row,
+                        (int)T, n_heads, n_kv_heads, head_dim, s_max, batch, (int)n_join, sec0, sec1, cache_packed ? 1 : 0};
+    hipLaunchKernelGGL(llm_qkv_post_shared_kernel, dim3((unsigned)T), dim3(256), 0, (hipStream_t)stream, a);
+    PADT_CHECK_LAUNCH("llm_qkv_post_shared");
+    return 0;
+}
+
 #if !PADT_OP16_F16   // type-independent (or bf16-decoder-only): compiled once
 // ---------------------------------------------------------------------------------------------------------------------
 // PaDT mask head tail (padt_decoder.py:241-274): e2[(n,a,b)][(c,d,:)] · mask_tok[obj(n)] → masks[obj][4*row+2a+c][4*col+2b+d]

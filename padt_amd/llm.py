@@ -77,6 +77,7 @@ class PromptPlan:
     rope_deltas: torch.Tensor        # (B,1) int64, 4.50 convention: max+1 - L_pad
     vrt_off: List[int]               # (B+1) prototype row offsets
     first_row: int = 0               # decode-session row of this batch's first sample (merged decode groups)
+    shared: Optional["SharedPrompt"] = None   # generate(image_index=): the smaller token set the prompt pass computes (plan_prompt_shared)
 
 
 def plan_prompt(cfg: PaDTConfig, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
@@ -114,6 +115,153 @@ def plan_prompt(cfg: PaDTConfig, input_ids: torch.Tensor, attention_mask: Option
         pos3=torch.cat(pos, dim=1).to(I32).contiguous().to(device), sample=sample.to(device), slot=slot.to(device),
         cu=torch.tensor(cu, dtype=I32, device=device), last_idx=torch.tensor([c - 1 for c in cu[1:]], dtype=I32, device=device),
         next_pos=nxt, rope_deltas=torch.tensor([[n - L] for n in nxt], dtype=torch.int64), vrt_off=off, first_row=row0)
+
+
+@dataclass
+class SharedPrompt:
+    """The token set a prompt pass with ``image_index`` computes (plan_prompt_shared): every share group's prefix ONCE, then every
+    sample's own tokens.  Segment s < G is the prefix of group s, segment G + b the own tokens of sample b."""
+    n_images: int
+    groups: List[tuple]              # (prefix length P, member samples) per share group, in order of the first member
+    prefix_of: List[int]             # per sample: its group's index, or -1 (no shared prefix: every token is its own)
+    ids: torch.Tensor                # (Ts,) int64 global ids
+    img_index: torch.Tensor          # (Ts,) int32 row of the per-SAMPLE merged embeddings (a prefix reads its first member's), or -1
+    pos3: torch.Tensor               # (3, Ts) int32: slices of the full rows' mRoPE positions
+    dst_off: torch.Tensor            # (Ts+1,) int32 CSR offsets into the destination lists
+    dst_sample: torch.Tensor         # session row whose K / V^T cache images get the token, or -1: a join row only
+    dst_slot: torch.Tensor           # ... at this slot
+    dst_row: torch.Tensor            # row of the attention's key / value join buffers
+    n_join: int
+    cu_q: torch.Tensor               # (G+B+1,) int32 query segments (the token set itself)
+    cu_k: torch.Tensor               # (G+B+1,) int32 key segments of the join buffers: [prefix] / [group prefix | own tokens]
+    max_q: int
+    unshare: torch.Tensor            # (T,) int32: row of the token set behind each row of the unshared packed order (PromptPlan.ids)
+    low_rows: torch.Tensor           # (sum merged per sample,) int32: the image's merged row behind each per-sample merged row
+    patch_rows: torch.Tensor         # (sum patches per sample,) int32: the same for the patch-level rows (high_res, visual_pe)
+    grid_x: torch.Tensor             # (B, 3) image_grid_thw[image_index]
+    dst_host: tuple = ()             # host copies of (dst_sample, dst_slot, dst_row) for check_shared_destinations
+
+
+def check_image_index(cfg: PaDTConfig, image_index, B: int, rows: List[List[int]], grids: List[List[int]]) -> List[int]:
+    """generate(image_index=): → the index as a list, after the host-side validation of the argument (ValueError)."""
+    idx = [int(i) for i in (image_index.detach().cpu().reshape(-1).tolist() if isinstance(image_index, torch.Tensor) else list(image_index))]
+    N = len(grids)
+    if len(idx) != B:
+        raise ValueError(f"image_index has {len(idx)} entries for a batch of {B} samples")
+    for b, u in enumerate(idx):
+        if not 0 <= u < N:
+            raise ValueError(f"image_index[{b}] = {u} is outside [0, {N}): pixel_values / image_grid_thw hold {N} images")
+    unused = sorted(set(range(N)) - set(idx))
+    if unused:
+        raise ValueError(f"image_index uses no sample for image(s) {unused}: every image of pixel_values must belong to a sample")
+    for b, u in enumerate(idx):
+        n_tok, n_feat = rows[b].count(cfg.image_token_id), grids[u][0] * grids[u][1] * grids[u][2] // cfg.merge_unit
+        if n_tok != n_feat:
+            raise ValueError(f"Image features and image tokens do not match: tokens: {n_tok}, features {n_feat} (sample {b}, image {u})")
+    return idx
+
+
+def plan_prompt_shared(cfg: PaDTConfig, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], grid_thw: torch.Tensor,
+                       image_index, device, row0: int = 0, proto_row0: int = 0) -> PromptPlan:
+    """plan_prompt for B samples over N <= B images (sample b uses image image_index[b]): → the PromptPlan of the EXPANDED inputs
+    (image_grid_thw[image_index], one image per sample — lens, cu, last_idx, positions, VRT ranges are what every consumer downstream of
+    the prompt pass reads) with ``shared`` set to the smaller token set the pass computes.
+
+    Share group: the samples of one image whose unpadded rows agree up to and including the last image token.  Its prefix length is
+    P = min(longest common prefix of the rows, shortest row - 1) — every sample keeps a token of its own, its last hidden row is needed.
+    One member, or a P that does not cover the image tokens: no prefix.  The prompt is causal, so the hidden rows and K / V rows of a
+    prefix token are the same in every member's full row: they are computed once and fanned out (ops.llm_qkv_post_shared)."""
+    ids_cpu = input_ids.detach().cpu()
+    B, L = ids_cpu.shape
+    am = attention_mask.detach().cpu() if attention_mask is not None else torch.ones_like(ids_cpu)
+    grids = [[int(x) for x in r] for r in torch.as_tensor(grid_thw).tolist()]
+    rows = [ids_cpu[b][am[b] == 1].tolist() for b in range(B)]
+    idx = check_image_index(cfg, image_index, B, rows, grids)
+    base = plan_prompt(cfg, input_ids, attention_mask, torch.tensor([grids[u] for u in idx], dtype=torch.long), "cpu", row0=row0,
+                       proto_row0=proto_row0)
+    lens, cu = base.lens, base.cu.tolist()
+    # ---- share groups
+    by_key = {}
+    for b, r in enumerate(rows):
+        last_img = len(r) - 1 - r[::-1].index(cfg.image_token_id)
+        by_key.setdefault((idx[b], tuple(r[: last_img + 1])), []).append(b)
+    groups, prefix_of = [], [-1] * B
+    for (u, key), members in by_key.items():
+        if len(members) < 2:
+            continue
+        P = min(lens[b] for b in members) - 1
+        first = rows[members[0]]
+        for b in members[1:]:
+            r, n = rows[b], 0
+            while n < P and r[n] == first[n]:
+                n += 1
+            P = n
+        if P < len(key):                                         # by definition the GROUP has no prefix then (a member's row ends at the image:
+            continue                                             # shortest row - 1 stops inside it) — its other members lose theirs too
+        for b in members:
+            prefix_of[b] = len(groups)
+        groups.append((P, members))
+    # ---- unique-image row tables: merged rows (embeddings, prototypes) and patch rows (high_res, visual_pe) per sample
+    merged = [g[0] * g[1] * g[2] // cfg.merge_unit for g in grids]
+    low_off, patch_off = [0], [0]
+    for g, n in zip(grids, merged):
+        low_off.append(low_off[-1] + n)
+        patch_off.append(patch_off[-1] + g[0] * g[1] * g[2])
+    low_rows = torch.cat([torch.arange(low_off[u], low_off[u + 1], dtype=I32) for u in idx])
+    patch_rows = torch.cat([torch.arange(patch_off[u], patch_off[u + 1], dtype=I32) for u in idx])
+    # ---- the token set: (sample whose full row the token is read from, first position, count) per segment
+    segs = [(members[0], 0, P) for P, members in groups]
+    segs += [(b, groups[prefix_of[b]][0] if prefix_of[b] >= 0 else 0, None) for b in range(B)]
+    segs = [(b, a, (lens[b] - a) if n is None else n) for b, a, n in segs]
+    G = len(groups)
+    cu_q = [0]
+    for _, _, n in segs:
+        cu_q.append(cu_q[-1] + n)
+    cu_k = [0]
+    for s, (b, a, n) in enumerate(segs):
+        cu_k.append(cu_k[-1] + (n if s < G else a + n))
+    src = torch.cat([torch.arange(cu[b] + a, cu[b] + a + n, dtype=torch.int64) for b, a, n in segs])     # rows of the unshared packed order
+    ids_s, pos_s, img_s = base.ids[src], base.pos3[:, src].contiguous(), base.img_index[src]
+    # ---- destinations and the rows of the unshared order
+    dst_off, d_sample, d_slot, d_row = [0], [], [], []
+    unshare = torch.empty((cu[-1],), dtype=I32)
+    for s, (P, members) in enumerate(groups):
+        for j in range(P):
+            d_sample.append(-1), d_slot.append(j), d_row.append(cu_k[s] + j)           # the prefix's own key segment
+            for b in members:
+                d_sample.append(row0 + b), d_slot.append(j), d_row.append(cu_k[G + b] + j)
+            dst_off.append(len(d_sample))
+        for b in members:
+            unshare[cu[b]: cu[b] + P] = torch.arange(cu_q[s], cu_q[s] + P, dtype=I32)
+    for b in range(B):
+        _, a, n = segs[G + b]
+        for j in range(n):
+            d_sample.append(row0 + b), d_slot.append(a + j), d_row.append(cu_k[G + b] + a + j)
+            dst_off.append(len(d_sample))
+        unshare[cu[b] + a: cu[b] + a + n] = torch.arange(cu_q[G + b], cu_q[G + b] + n, dtype=I32)
+    t32 = lambda v: torch.tensor(v, dtype=I32).to(device)
+    base.shared = SharedPrompt(
+        n_images=len(grids), groups=groups, prefix_of=prefix_of, ids=ids_s.to(device), img_index=img_s.to(device), pos3=pos_s.to(device),
+        dst_off=t32(dst_off), dst_sample=t32(d_sample), dst_slot=t32(d_slot), dst_row=t32(d_row), n_join=cu_k[-1], cu_q=t32(cu_q),
+        cu_k=t32(cu_k), max_q=max(n for _, _, n in segs), unshare=unshare.to(device), low_rows=low_rows.to(device),
+        patch_rows=patch_rows.to(device), grid_x=torch.tensor([grids[u] for u in idx], dtype=torch.long), dst_host=tuple(torch.tensor(v, dtype=I32) for v in (d_sample, d_slot, d_row)))
+    for f in ("ids", "img_index", "pos3", "sample", "slot", "cu", "last_idx"):
+        setattr(base, f, getattr(base, f).to(device))
+    return base
+
+
+def check_shared_destinations(sh: SharedPrompt, n_rows: int, s_max: int):
+    """Host check of a shared plan against the session it is about to write: every cache destination inside [0, n_rows) x [0, s_max), no
+    (row, slot) written twice, every join row inside the join buffers."""
+    sample, slot, row = sh.dst_host
+    if bool(((row < 0) | (row >= sh.n_join)).any()):
+        raise ValueError("shared prompt plan: a join row is outside the join buffers")
+    keep = sample >= 0
+    sample, slot = sample[keep].long(), slot[keep].long()
+    if bool(((sample >= n_rows) | (slot < 0) | (slot >= s_max)).any()):
+        raise ValueError(f"shared prompt plan: a KV destination is outside the session's {n_rows} rows x {s_max} slots")
+    if torch.unique(sample * s_max + slot).numel() != sample.numel():
+        raise ValueError("shared prompt plan: a (row, slot) of the KV cache is written twice")
 
 
 # ------------------------------------------------------------------------------------------------ decode session
@@ -391,10 +539,12 @@ class LanguageModel:
         nf: int32 device flag set when a post-norm row is not finite (the residual stream absorbs every upstream inf / NaN)."""
         cfg, W = self.cfg, self.W
         Hq, Hkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
-        T = plan.ids.numel()
+        sh = plan.shared                                         # generate(image_index=): the smaller token set (plan_prompt_shared);
+        src = plan if sh is None else sh
+        T = src.ids.numel()
         dev = image_embeds.device
         bf = W.op16
-        x = ops.embed_tokens(plan.ids, plan.img_index, W["llm.embed"], sess.proto, image_embeds, err_flag=sess.err)
+        x = ops.embed_tokens(src.ids, src.img_index, W["llm.embed"], sess.proto, image_embeds, err_flag=sess.err)
         x32 = ops.cast_x16_f32(x)                                # fp32 residual stream; x stays its 16-bit mirror
         eps_n = W.eps_m(cfg.rms_norm_eps)
         if ops.stream_scale(bf) != 1.0:
@@ -403,7 +553,11 @@ class LanguageModel:
         rstd = torch.empty((T,), device=dev, dtype=torch.float32)
         qkv = torch.empty((T, (Hq + 2 * Hkv) * hd), device=dev, dtype=bf)
         q = torch.empty((T, Hq * hd), device=dev, dtype=bf)
-        kp = torch.empty((T, Hkv * hd), device=dev, dtype=bf)
+        if sh is None:
+            kp = torch.empty((T, Hkv * hd), device=dev, dtype=bf)
+        else:                                                    # roped K / V rows of every key segment: [prefix] / [group prefix | own tokens]
+            kj = torch.empty((sh.n_join, Hkv * hd), device=dev, dtype=bf)
+            vj = torch.empty((sh.n_join, Hkv * hd), device=dev, dtype=bf)
         att = torch.empty((T, Hq * hd), device=dev, dtype=bf)
         h = torch.empty((T, W.llm_ipad), device=dev, dtype=bf)
         mx = max(plan.lens)
@@ -423,9 +577,17 @@ class LanguageModel:
             else:
                 ops.row_rstd(x, eps=eps_n, out=rstd)                       # norm weight is folded into qkv.w
                 ops.gemm(x, W[p + "qkv.w"], W[p + "qkv.b"], out=qkv, row_scale=rstd)
-            ops.llm_qkv_post(qkv, plan.pos3, sess.inv_freq, q, sess.kc[i], sess.vtc[i], Hq, Hkv, hd, sess.s_max,
-                             cfg.mrope_section, sample=plan.sample, slot=plan.slot, k_pack=kp, cache_packed=sess.cache_packed)
-            ops.attn_varlen(q, kp, qkv[:, (Hq + Hkv) * hd:], att, plan.cu, plan.cu, mx, Hq, Hkv, hd, causal=True)
+            if sh is None:
+                ops.llm_qkv_post(qkv, plan.pos3, sess.inv_freq, q, sess.kc[i], sess.vtc[i], Hq, Hkv, hd, sess.s_max,
+                                 cfg.mrope_section, sample=plan.sample, slot=plan.slot, k_pack=kp, cache_packed=sess.cache_packed)
+                ops.attn_varlen(q, kp, qkv[:, (Hq + Hkv) * hd:], att, plan.cu, plan.cu, mx, Hq, Hkv, hd, causal=True)
+            else:
+                # a token is rotated once and fanned out to every member's cache images and key segment; a suffix's queries then see
+                # [group prefix | own tokens] under the bottom-right aligned causal mask (Lk > Lq), exactly the keys of its full row
+                ops.llm_qkv_post_shared(qkv, sh.pos3, sess.inv_freq, q, sess.kc[i], sess.vtc[i], kj, vj, sh.dst_off, sh.dst_sample,
+                                        sh.dst_slot, sh.dst_row, Hq, Hkv, hd, sess.s_max, cfg.mrope_section,
+                                        cache_packed=sess.cache_packed)
+                ops.attn_varlen(q, kj, vj, att, sh.cu_q, sh.cu_k, sh.max_q, Hq, Hkv, hd, causal=True)
             if f8 and (p + "o.w8") in W:
                 ops.quant_rows_fp8(att, out=a8, rs=rs8)
                 ops.gemm_fp8(a8, W[p + "o.w8"], W[p + "o.ws"], rs8, epilogue=ops.EPI_RESID, x32=x32, xb=x)
@@ -445,4 +607,6 @@ class LanguageModel:
         ops.rmsnorm_f32(x32, W["llm.norm"], out=n, eps=cfg.rms_norm_eps)
         if nf is not None:
             ops.check_finite(n, nf)
+        if sh is not None:                                       # back to the unshared packed per-sample order every consumer reads
+            n = ops.gather_rows(n, sh.unshare)
         return n

@@ -20,7 +20,7 @@ import torch
 from . import _lib, ops
 from .config import PaDTConfig
 from .decoder import PaDTDecoder
-from .llm import MODE, LanguageModel, plan_prompt
+from .llm import MODE, LanguageModel, check_shared_destinations, plan_prompt, plan_prompt_shared
 from .vision import VisionEncoder
 from .weights import Fp16RangeError, load_checkpoint_state_dict, prepare_weights, synthetic_state_dict
 
@@ -308,8 +308,16 @@ class PaDTForConditionalGeneration:
                  temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  seed: Optional[int] = None, max_length: Optional[int] = None, output_scores: bool = False, output_logits: bool = False,
                  pad_token_id: Optional[int] = None, logits_processor=None, stopping_criteria=None, no_repeat_ngram_size: Optional[int] = None,
-                 bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, generation_config=None, **kwargs):
+                 bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, generation_config=None, image_index=None, **kwargs):
         """Greedy generation over the unified text‖VRT vocabulary.
+
+        ``image_index`` (several queries on one image): a length-B sequence or int tensor; sample b uses image ``image_index[b]`` of the
+        N <= B images in ``pixel_values`` / ``image_grid_thw``.  The call returns what it returns on the expanded inputs (image
+        ``image_index[b]``'s patches repeated for sample b, ``image_grid_thw[image_index]``, no index) — sequences, per-sample VRT id ranges,
+        hidden states, scores, ``rope_deltas``, one ``past_*`` entry per sample — but the ViT runs on the N images only and the prompt pass
+        computes the rows that queries on one image have in common (everything up to the first token in which they differ: system text,
+        image tokens, a repeated instruction) ONCE, fanning their K / V rows out to every member's cache.  Nothing is kept between calls.  Pass
+        ``image_grid_thw[image_index]`` to ``vl_decode``.  Not available with ``precision="reference"``.
 
         ``no_repeat_ngram_size`` / ``bad_words_ids`` / ``suppress_tokens`` / ``begin_suppress_tokens`` (padt.py:570-580 → HF's NoRepeatNGram /
         NoBadWords / SuppressTokens / SuppressTokensAtBegin processors): pure bans, served ON THE DEVICE in every mode — one kernel per step
@@ -396,7 +404,7 @@ class PaDTForConditionalGeneration:
                                    eos_token_id=eos_token_id, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
                                    keep_scores=bool(output_scores or output_logits or hooks is not None), hooks=hooks,
                                    keep_logits=bool(output_logits), no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
-                                   suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens)
+                                   suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens, image_index=image_index)
         return self.generate_collect(ctx, output_hidden_states, return_dict_in_generate, output_scores=bool(output_scores),
                                      output_logits=bool(output_logits))
 
@@ -405,7 +413,7 @@ class PaDTForConditionalGeneration:
                         schedule=None, sync_every=16, use_graph=True, lane=0, decode_stream=None, group=None, n_slots=1,
                         repetition_penalty=None, eos_token_id=None, temperature=None, top_k=None, top_p=None, seed=None,
                         vit_stream=None, inputs_ready=None, keep_scores=False, hooks=None, keep_logits=False, no_repeat_ngram_size=None,
-                        bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None):
+                        bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None):
         """Asynchronous half of generate(): host integer prep + every kernel up to the first host sync point, enqueued on
         the current stream (the decode steps on ``decode_stream`` if given, ordered after the prefill by an event).
         Returns a group context for generate_collect().
@@ -416,14 +424,21 @@ class PaDTForConditionalGeneration:
         once the group is full (or on launch_decode()).  Every sample's math is unchanged (rows are independent in every
         decode kernel); the weights are streamed once per step for all rows.  Returns None instead of adding when the
         batch does not fit the group's session (caller closes the group and starts a new one).
+
+        ``image_index`` (see generate()): the ViT and the prototype projection run on the N unique images and their rows are expanded per
+        sample on the device; the prompt pass runs llm.plan_prompt_shared's token set.  Only THIS batch's prompt pass changes: the decode
+        steps, and the rows of other batches of a merged group, are what they are without an index.
         """
+        if image_index is not None and getattr(self, "precision", "default") == "reference":
+            raise NotImplementedError("generate(image_index=...) is not implemented with precision='reference' (its prompt pass is its own: "
+                                      "reference.ReferencePath.prefill): expand the inputs or use precision='default'")
         # operands="auto" whose checkpoint keeps overflowing fp16: new decode groups start on the bf16 twin (a group stays with its owner)
         owner = group["owner"] if group is not None else (self.fallback_model() if self.prefers_bf16 else self)
         if owner is not self:
             return owner.generate_launch(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, do_sample, schedule, sync_every,
                                          use_graph, lane, decode_stream, group, n_slots, repetition_penalty, eos_token_id, temperature, top_k, top_p,
                                          seed, vit_stream, inputs_ready, keep_scores, hooks, keep_logits, no_repeat_ngram_size, bad_words_ids,
-                                         suppress_tokens, begin_suppress_tokens)
+                                         suppress_tokens, begin_suppress_tokens, image_index)
         self._batches_seen += 1
         gc = self.generation_config
         do_sample = gc.do_sample if do_sample is None else do_sample
@@ -464,7 +479,11 @@ class PaDTForConditionalGeneration:
         k = 0 if group is None else len(group["subs"])
         row0 = k * B
         proto_row0 = 0 if group is None else group["proto_rows"]
-        plan = plan_prompt(cfg, input_ids, attention_mask, grid, dev, row0=row0, proto_row0=proto_row0)
+        if image_index is None:
+            plan = plan_prompt(cfg, input_ids, attention_mask, grid, dev, row0=row0, proto_row0=proto_row0)
+        else:
+            plan = plan_prompt_shared(cfg, input_ids, attention_mask, grid, image_index, dev, row0=row0, proto_row0=proto_row0)
+        sh = plan.shared
         n_proto = plan.vrt_off[-1]
         need_s = max(plan.lens) + T_max
         if rules is not None:
@@ -521,6 +540,8 @@ class PaDTForConditionalGeneration:
                     or schedule != group["schedule"] or gen_key != group["gen_key"] or sess.s_max < need_s
                     or sess.np_max < proto_row0 + n_proto):
                 return None
+        if sh is not None:
+            check_shared_destinations(sh, sess.B, sess.s_max)
         rows = slice(row0, row0 + B)
         sess.nf[rows].zero_()
         # this batch's range guard (ViT rows, prototypes, prompt-pass hidden rows).  Its zero fill must be ordered before EVERY check that ORs
@@ -537,8 +558,7 @@ class PaDTForConditionalGeneration:
             low, high, pe = self.ref.visual(pixel_values.to(dev), grid, nf=nf)
             proto = self.ref.prototypes(low, sess, proto_row0, nf=nf)     # fp32 rows (→ past_image_embeds); sess.proto gets their fp16 image
         elif vit_stream is None:
-            low, high, pe = self.visual(pixel_values.to(dev), grid, nf=nf)
-            proto = self.lm.prototypes(low, out=sess.proto[proto_row0: proto_row0 + n_proto], nf=nf)
+            low, high, pe, proto = self._vit_and_prototypes(pixel_values, grid, sess.proto[proto_row0: proto_row0 + n_proto], nf, sh)
         else:
             # the ViT of this batch on its own stream: it needs the inputs (event `inputs_ready` of the caller's stream) and nothing of the
             # current stream — so it runs while the PREVIOUS batch's prefill is still on the current stream — except for the first batch of a
@@ -550,8 +570,7 @@ class PaDTForConditionalGeneration:
                 vit_stream.wait_stream(cur)
             with torch.cuda.stream(vit_stream):
                 nf.zero_()
-                low, high, pe = self.visual(pixel_values.to(dev), grid, nf=nf)
-                proto = self.lm.prototypes(low, out=sess.proto[proto_row0: proto_row0 + n_proto], nf=nf)
+                low, high, pe, proto = self._vit_and_prototypes(pixel_values, grid, sess.proto[proto_row0: proto_row0 + n_proto], nf, sh)
             cur.wait_stream(vit_stream)                           # the prefill below reads low / the prototype rows
             for t_ in (low, high, pe[0], pe[1]):                   # allocated on vit_stream, read on the prefill / decode streams
                 t_.record_stream(cur)
@@ -590,11 +609,19 @@ class PaDTForConditionalGeneration:
             ops.gather_rows(hn_all, plan.last_idx, out=sess.hn_first[rows])
         group["subs"].append(dict(plan=plan, low=low, high=high, pe=pe, proto=proto, hn_all=hn_all, input_ids=input_ids,
                                   n_proto=n_proto, row0=row0, proto_row0=proto_row0, nf=nf,
-                                  inputs=(attention_mask, pixel_values, image_grid_thw)))       # what a re-run on the bf16 twin needs
+                                  inputs=(attention_mask, pixel_values, image_grid_thw, image_index)))       # what a re-run on the bf16 twin needs
         group["proto_rows"] = proto_row0 + n_proto
         if len(group["subs"]) == group["n_slots"]:
             self.launch_decode(group)
         return group
+
+    def _vit_and_prototypes(self, pixel_values, grid, proto_out, nf, sh):
+        """ViT → prototypes into the session's table rows ``proto_out``, on the current stream: → (low, high, pe, proto).  With a shared plan
+        (generate(image_index=)) the ViT blocks run on the N unique images and every output comes back per sample (VisionEncoder's
+        ``expand``: device row copies of the patch-level rows, merger and prototype projection at the expanded row count)."""
+        expand = None if sh is None else (sh.low_rows, sh.patch_rows, sh.grid_x)
+        low, high, pe = self.visual(pixel_values.to(self.device), grid, nf=nf, expand=expand)
+        return low, high, pe, self.lm.prototypes(low, out=proto_out, nf=nf)
 
     @torch.no_grad()
     def launch_decode(self, group):
@@ -707,7 +734,7 @@ class PaDTForConditionalGeneration:
             self.prefers_bf16 = True
             warnings.warn("padt_amd: %d of %d batches exceeded fp16's range — operands='auto' now starts every new decode group on the bf16 "
                           "instantiation" % (self.overflow_reruns, self._batches_seen), RuntimeWarning, stacklevel=3)
-        am, pix, grid = sub["inputs"]
+        am, pix, grid, image_index = sub["inputs"]
         pen, eos, samp = group["gen_key"][:3]
         n_gram, static, begin, words = group["gen_key"][5] or (0, (), (), ())
         # the canonical rules, explicit (an empty list is "off", not "the default"): the 1-token bad words travel as suppress_tokens
@@ -721,7 +748,7 @@ class PaDTForConditionalGeneration:
         return fb.generate(input_ids=sub["input_ids"], attention_mask=am, pixel_values=pix, image_grid_thw=grid, max_new_tokens=group["T_max"],
                            schedule=group["schedule"], sync_every=group["sync_every"], use_graph=group["use_graph"], lane=("fb", group["lane"]),
                            repetition_penalty=pen, eos_token_id=list(eos), output_hidden_states=output_hidden_states,
-                           return_dict_in_generate=return_dict_in_generate,
+                           return_dict_in_generate=return_dict_in_generate, image_index=image_index,
                            output_scores=bool(group["gen_key"][3]) and (group.get("hooks") is None or group["hooks"]["pass_scores"]), **kw_rules, **kw)
 
     # ------------------------------------------------------------------ vl_decode (padt.py:342-412)

@@ -695,6 +695,30 @@ def llm_qkv_post(qkv, pos3, inv_freq, q_out, k_cache, vt_cache, n_heads, n_kv_he
                "padt_llm_qkv_post")
 
 
+def llm_qkv_post_shared(qkv, pos3, inv_freq, q_out, k_cache, vt_cache, k_join, v_join, dst_off, dst_sample, dst_slot, dst_row,
+                        n_heads, n_kv_heads, head_dim, s_max, sections, cache_packed=False):
+    """llm_qkv_post with fan-out (padt_llm_qkv_post_shared): token t's roped K / V go to the cache images (session row dst_sample[n], slot
+    dst_slot[n]) and join-buffer rows dst_row[n] of every n in [dst_off[t], dst_off[t+1]); a destination out of range is skipped."""
+    dt = _x16(qkv, q_out, k_cache, vt_cache, k_join, v_join)
+    T = qkv.shape[0]
+    assert pos3.dtype == torch.int32 and pos3.is_contiguous() and pos3.shape == (3, T) and inv_freq.dtype == torch.float32
+    assert qkv.shape[1] == (n_heads + 2 * n_kv_heads) * head_dim and q_out.shape == (T, n_heads * head_dim)
+    assert k_join.shape == v_join.shape and k_join.shape[1] == n_kv_heads * head_dim
+    assert k_cache.is_contiguous() and vt_cache.is_contiguous() and k_cache.numel() == vt_cache.numel()
+    assert k_cache.numel() % (n_kv_heads * s_max * head_dim) == 0
+    batch = k_cache.numel() // (n_kv_heads * s_max * head_dim)
+    for t in (dst_off, dst_sample, dst_slot, dst_row):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+    assert dst_off.numel() == T + 1 and dst_sample.numel() == dst_slot.numel() == dst_row.numel()
+    for t in (qkv, q_out, k_join, v_join, k_cache, vt_cache):       # the kernel's 16-byte accesses
+        assert t.data_ptr() % 16 == 0
+    _lib.check(_fn("padt_llm_qkv_post_shared", dt)(_stream(), _p(qkv), qkv.stride(0), _p(pos3), _p(inv_freq), _p(q_out), q_out.stride(0),
+                                            _p(k_join), k_join.stride(0), _p(v_join), v_join.stride(0), k_join.shape[0], _p(k_cache),
+                                            _p(vt_cache), _p(dst_off), _p(dst_sample), _p(dst_slot), _p(dst_row), T, n_heads, n_kv_heads,
+                                            head_dim, s_max, batch, sections[0], sections[1], 1 if cache_packed else 0),
+               "padt_llm_qkv_post_shared")
+
+
 def mask_scatter(e2, mask_tok, cu_patch, obj_w, masks, n_obj, total_patches, dm):
     lib = _lib.load()
     _chk_bf16(e2, mask_tok)

@@ -12,14 +12,26 @@ import torch
 from .processor import parseVRTintoCompletion
 
 
+def sample_grids(image_grid_thw, image_index):
+    """image_grid_thw[image_index]: one grid row per sample of a batch whose samples share images (generate(image_index=))."""
+    idx = image_index if isinstance(image_index, torch.Tensor) else torch.tensor([int(i) for i in image_index])
+    return image_grid_thw[idx.to(device=image_grid_thw.device, dtype=torch.long)]
+
+
 def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens=1024,
-              schedule: Optional[Sequence] = None, need_thinking_mask=None, **gen_kw):
+              schedule: Optional[Sequence] = None, need_thinking_mask=None, image_index=None, **gen_kw):
     """→ (decoded dict of vl_decode, completions, labels, vrts).  ``input_ids`` carries LOCAL VRT ids (as a processor
-    emits them) and is updated in place exactly like the reference's callers do."""
+    emits them) and is updated in place exactly like the reference's callers do.
+    ``image_index``: sample b asks about image image_index[b] of the N <= B images given (generate(image_index=)); everything per sample
+    (VRT id ranges, vl_decode) then follows ``image_grid_thw[image_index]``."""
     B = input_ids.shape[0]
+    grid_in = image_grid_thw
+    if image_index is not None:
+        gen_kw = dict(gen_kw, image_index=image_index)
+        image_grid_thw = sample_grids(image_grid_thw, image_index)
     ids = processor.assign_to_global_vrt_id(input_ids, image_grid_thw)
     out = model.generate(input_ids=ids, attention_mask=attention_mask, pixel_values=pixel_values,
-                         image_grid_thw=image_grid_thw, use_cache=True, max_new_tokens=max_new_tokens, do_sample=False,
+                         image_grid_thw=grid_in, use_cache=True, max_new_tokens=max_new_tokens, do_sample=False,
                          output_hidden_states=True, return_dict_in_generate=True, schedule=schedule, **gen_kw)
     L = input_ids.shape[1]
     seq_local = processor.assign_to_local_vrt_id(out["sequences"].cpu(), image_grid_thw.cpu())
@@ -82,10 +94,14 @@ class PipelinedRunner:
 
     def submit(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens=1024, schedule=None,
                need_thinking_mask=None, sync_every=None, repetition_penalty=None, eos_token_id=None, no_repeat_ngram_size=None,
-               bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, **sampling):
+               bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None, **sampling):
+        """image_index: see generate(); the batch's results are those of the expanded batch."""
         done = []
         bid = self.n_batches
         self.n_batches += 1
+        grid_in = image_grid_thw                                  # the N images' grids (what the ViT sees)
+        if image_index is not None:                               # ... and one grid per sample for everything downstream of the prompt pass
+            image_grid_thw = sample_grids(image_grid_thw, image_index)
         ids = self.processor.assign_to_global_vrt_id(input_ids, image_grid_thw)
         sched = tuple(schedule) if schedule is not None else None
         for attempt in range(2):
@@ -102,7 +118,7 @@ class PipelinedRunner:
             # ... and are consumed on the prefill / decode streams, possibly long after the caller dropped them: tell the
             # caching allocator (record_stream) so their blocks are not handed to the caller's next batch while a lagging
             # side stream still reads them; the group also holds references until its results were collected
-            for t in (ids, attention_mask, pixel_values, image_grid_thw):
+            for t in (ids, attention_mask, pixel_values, image_grid_thw, grid_in):
                 if isinstance(t, torch.Tensor) and t.is_cuda:
                     t.record_stream(pre)
                     t.record_stream(self.decode_streams[g["lane"]])
@@ -110,13 +126,13 @@ class PipelinedRunner:
                         t.record_stream(self.vit_stream)
             self._mark(bid, "prefill_begin", pre)
             with torch.cuda.stream(pre):
-                ctx = self.model.generate_launch(ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, False,
+                ctx = self.model.generate_launch(ids, attention_mask, pixel_values, grid_in, max_new_tokens, False,
                                                  sched, sync_every or max_new_tokens, self.use_graph, g["lane"],
                                                  self.decode_streams[g["lane"]], group=g["ctx"], n_slots=self.merge,
                                                  repetition_penalty=repetition_penalty, eos_token_id=eos_token_id,
                                                  no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                                                  suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
-                                                 vit_stream=self.vit_stream, inputs_ready=ev_in, **sampling)
+                                                 vit_stream=self.vit_stream, inputs_ready=ev_in, image_index=image_index, **sampling)
             if ctx is not None:
                 break
             self._close_cur()                                     # batch does not fit this group's session: start a new one

@@ -118,9 +118,14 @@ class VisionEncoder:
         ops.gemm(x, W[p + "gu.w"], W[p + "gu.b"], out=hbuf, epilogue=ops.EPI_SWIGLU, row_scale=rstd)
         ops.gemm_resid32(hbuf, W[p + "down.w"], W[p + "down.b"], x32, x)
 
-    def __call__(self, pixel_values: torch.Tensor, grid_thw: torch.Tensor, proto_out=None, nf=None):
+    def __call__(self, pixel_values: torch.Tensor, grid_thw: torch.Tensor, proto_out=None, nf=None, expand=None):
         """pixel_values (P, C*T*p*p) fp32 / bf16 / fp16 on device → (image_embeds (N,D), high_res (P,vh), (cos,sin) (P,hd)).
-        nf: int32 device flag, set when the encoder's output rows are not finite (an fp16 operand overflowed in some block; ops.check_finite)."""
+        nf: int32 device flag, set when the encoder's output rows are not finite (an fp16 operand overflowed in some block; ops.check_finite).
+        expand = (merged_rows, patch_rows, grid_per_sample) (generate(image_index=), llm.SharedPrompt): the blocks run on the images given,
+        once each; what is returned is per SAMPLE — row tables on the device name the image row behind every sample row.  The patch-level
+        outputs are row copies.  The merger runs on the expanded rows: by its shapes it is about 1.5 % of the encoder's work (an estimate, profiles/shared_prefix.md §3), and run at the expanded call's row
+        count it goes through the same GEMM kernel as there (the kernel family depends on the row count, its summation order on the
+        family), so image_embeds — and the prototypes behind them — are the expanded call's bit for bit."""
         cfg, W = self.cfg, self.W
         v = cfg.vision_config
         plan = self.plan(grid_thw)
@@ -148,7 +153,13 @@ class VisionEncoder:
         if nf is not None:                                                     # inf / NaN of any block is absorbing in the residual stream
             ops.check_finite(x32, nf)
         ops.rmsnorm_f32(x32, W["vit.merger.ln_q"], out=n)
-        m = ops.gemm(n.view(plan.N, vh * cfg.merge_unit), W["vit.merger.0.w"], W["vit.merger.0.b"], epilogue=ops.EPI_GELU)
+        n4, reverse = n.view(plan.N, vh * cfg.merge_unit), plan.reverse
+        if expand is not None:                                                 # an image's merged rows are one block in window order too
+            merged_rows, patch_rows, grid_x = expand
+            n4, reverse = ops.gather_rows(n4, merged_rows), self.plan(grid_x).reverse
+        m = ops.gemm(n4, W["vit.merger.0.w"], W["vit.merger.0.b"], epilogue=ops.EPI_GELU)
         low_win = ops.gemm(m, W["vit.merger.2.w"], W["vit.merger.2.b"])
-        low = ops.gather_rows(low_win, plan.reverse)                           # raster order (padt.py:103-104)
+        low = ops.gather_rows(low_win, reverse)                                # raster order (padt.py:103-104)
+        if expand is not None:
+            return low, ops.gather_rows(x32, patch_rows), (ops.gather_rows(plan.cos, patch_rows), ops.gather_rows(plan.sin, patch_rows))
         return low, x32, (plan.cos.clone(), plan.sin.clone())     # the caller owns past_visual_pe (plan tables are cached)
