@@ -331,6 +331,14 @@ int  padt_vrt_head_ban(void* stream, const void* hidden, long ldh, const void* e
                        long ld_logits, void* part_val, void* part_idx, long batch, long D, int eos,
                        const void* embed_table_packed, const void* gen_cfg, const void* seen, long seen_words,
                        const void* ban, long ban_words);
+/* padt_vrt_head_ban that also writes part_sum[blk * batch + b] = Σ exp(v - part_val[blk * batch + b]) over block blk's 16 masked / penalised /
+ * ban-filtered logits v of sample b (0 for a block without an allowed row): generate(output_token_logprobs=True).  Tokens, partials and any
+ * written logits are those of padt_vrt_head_ban, bit for bit; no logit row is needed. */
+int  padt_vrt_head_lse(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab, const void* proto,
+                       long n_proto, const int* vrt_off, const int* mode_table, const int* step, void* logits_f32,
+                       long ld_logits, void* part_val, void* part_idx, long batch, long D, int eos,
+                       const void* embed_table_packed, const void* gen_cfg, const void* seen, long seen_words,
+                       const void* ban, long ban_words, void* part_sum);
 /* argmax reduction (ties → lowest id), pad/EOS bookkeeping, token append, hidden-row stash, slot/len/position/step
  * advance — all on device.  padt.py:745-757, 732-737.  gen_cfg / seen as in padt_vrt_head: extra EOS ids stop a row too
  * (generation_config's eos_token_id list), and the chosen token's bit is set in the row's seen bitmap. */
@@ -338,6 +346,13 @@ int  padt_greedy_step(void* stream, const void* part_val, const void* part_idx, 
                       int pad, long t_max, int* unfinished, long* tokens_out, long* cur_tok, int* step, int* slot,
                       int* lens, int* pos3, const void* hidden, void* hidden_buf, int advance, const void* gen_cfg,
                       void* seen, long seen_words);
+/* padt_greedy_step over padt_vrt_head_lse's partials: also logprobs[b][*step] (fp32 [batch][t_max]) = log_softmax(the step's masked row)[token]
+ * = -log Σ_blk part_sum · exp(part_val - max), summed in a fixed order; 0 for a row already finished on entry (the EOS step itself holds its
+ * value), -inf where the row has no candidate and pad is emitted; nothing is written once *step >= t_max. */
+int  padt_greedy_step_lp(void* stream, const void* part_val, const void* part_idx, long nblk, long batch, long D, int eos,
+                         int pad, long t_max, int* unfinished, long* tokens_out, long* cur_tok, int* step, int* slot,
+                         int* lens, int* pos3, const void* hidden, void* hidden_buf, int advance, const void* gen_cfg,
+                         void* seen, long seen_words, const void* part_sum, void* logprobs);
 /* Sampling branch (padt.py:740-743 multinomial over softmax of the warped scores): one token per row drawn from the fp32 logits
  * padt_vrt_head wrote (logits_f32), after HF's Temperature → TopK → TopP warpers (generation/logits_process.py) with the
  * parameters in gen_cfg (DEVICE: {float penalty; int eos[4]; int do_sample; unsigned seed; float temperature; int top_k;
@@ -352,6 +367,11 @@ int  padt_sample_token(void* stream, void* logits_f32, long ld_logits, long n_ro
  * (torch.argmax, padt.py:745): the selection of the HOOKED decode loop, where caller-supplied logits processors (padt.py:717) have rewritten
  * the rows padt_vrt_head wrote. */
 int  padt_argmax_rows_f32(void* stream, const void* scores_f32, long ld, long n_cols, void* part_val, void* part_idx, long batch);
+/* Token log-probs where the selection does not come from the head's partials (sampling, caller logits processors): one block per fp32 score
+ * row (under sampling the warped row: gen_cfg's write_back), launched between the selection kernel and padt_greedy_step:
+ * logprobs[b][*step] = unfinished[b] ? rows[b][part_idx[b]] - logsumexp(rows[b][0..n_cols)) : 0; -inf for a row without a candidate. */
+int  padt_token_logprob_rows_f32(void* stream, const void* rows_f32, long ld, long n_cols, const void* part_idx, const int* unfinished,
+                                 const int* step, void* logprobs, long t_max, long batch);
 /* The synchronising half of generate() (padt.py:745-757 stop rule, :203 table assert, the range guard's flags) in ONE launch + one small
  * D2H copy: out[0] = *err, out[1] = any(unfinished[0..n_rows)), out[2..] = nf_rows[n_rows], nf_batch[n_batch], first_eos[n_rows] — the first
  * step t < done at which a row's token is an EOS id (eos or gen_cfg's list), -1 if none.  out holds 2 + 2 n_rows + n_batch int32. */

@@ -48,6 +48,7 @@ struct HeadArgs {
     const GenCfg* gen;                 // optional generation config (repetition penalty) + per-sample seen-token bitmap
     const unsigned* seen; long seen_words;
     const unsigned* ban; long ban_words;   // optional per-sample bitmap of banned table rows (gen_rules_kernel): bit set → the logit is -inf
+    float* part_sum;                   // LSE kernels: [nblk][B] Σ exp(v - block max) over the block's 16 masked logits (token log-probs)
 };
 
 // PACKED: text rows come from a fragment-packed copy of the table ([V/16][D/32][64 lanes][8], ops.pack_weight — every wave
@@ -56,7 +57,11 @@ struct HeadArgs {
 // NT: 16-row table blocks per thread block — they share every hidden-row fragment a wave loads (at 64 rows a wave loads 4 KiB of hidden
 // fragments per K-step: with one table block per thread block that is 4 bytes of L2 traffic per byte of table, 2.5 GB per step; with NT = 4,
 // 1:1).  The K-step → wave map and the cross-wave order are those of NT = 1: a logit's bits depend neither on NT nor on the row count.
-template <int MT, int NT, bool PACKED>
+// LSE (generate(output_token_logprobs=True)): the finishing wave also writes s = Σ exp(v - best) over the block's 16 masked / penalised /
+// ban-filtered logits of a sample — greedy_step_kernel<true> folds the (best, s) pairs into log p(token) without any logit row in memory.
+// exp is v_exp_f32 on (v - best)·log2e: the argument is <= 0, so nothing overflows however large the logits are; a block without an allowed
+// row (best = -inf) yields s = 0.  MFMA order, cross-wave sum and the (best, idx) partials are those of LSE = false, bit for bit.
+template <int MT, int NT, bool PACKED, bool LSE = false>
 __global__ __launch_bounds__(256) void vrt_head_kernel(HeadArgs p) {
     extern __shared__ __attribute__((aligned(16))) float red_raw[];
     typedef float RedT[NT * MT][64][4];
@@ -139,6 +144,7 @@ __global__ __launch_bounds__(256) void vrt_head_kernel(HeadArgs p) {
         int bidx = 0x7fffffff;
         int lo = 0, hi = 0;
         if (m < p.B) { lo = p.vrt_off[m]; hi = p.vrt_off[m + 1]; }
+        float vr[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = n0 + fq * 4 + r;
@@ -153,6 +159,7 @@ __global__ __launch_bounds__(256) void vrt_head_kernel(HeadArgs p) {
             const float v = ok ? sc : -INFINITY;
             if (p.logits && m < p.B && row < NTOT) p.logits[(long)m * p.ldl + row] = v;
             if (v > best) { best = v; bidx = row; }               // rows ascend with r → first max wins
+            vr[r] = v;
         }
         // combine the 4 lanes (fq = 0..3) that hold the same sample
 #pragma unroll
@@ -164,6 +171,15 @@ __global__ __launch_bounds__(256) void vrt_head_kernel(HeadArgs p) {
         if (fq == 0 && m < p.B) {
             p.part_val[(long)blk * p.B + m] = best;
             p.part_idx[(long)blk * p.B + m] = bidx;
+        }
+        if constexpr (LSE) {
+            float s = 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)                           // a masked logit adds an exact 0 (and -inf - -inf never reaches the exp)
+                s += vr[r] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f((vr[r] - best) * 1.44269504088896341f);
+            s += __shfl_xor(s, 16, 64);                           // the same two steps that combined `best`: a fixed order
+            s += __shfl_xor(s, 32, 64);
+            if (fq == 0 && m < p.B) p.part_sum[(long)blk * p.B + m] = s;
         }
     }
 }
@@ -183,11 +199,18 @@ struct GreedyArgs {
     int advance;              // 1: bump slot/lens/pos (decode steps and after prefill)
     const GenCfg* gen;        // optional: extra EOS ids
     unsigned* seen; long seen_words;   // optional: bitmap of ids present in each row (repetition penalty), updated here
+    const float* part_sum;    // LP: [nblk][B] Σ exp(v - block max) of the LSE head kernels
+    float* logprobs;          // LP: [B][T_max] log-prob of the token each step selected
 };
 
+// LP (padt_greedy_step_lp): next to the arg-max, S = Σ_blk part_sum · exp(part_val - M) with M the global max — the row's Σ exp(logit - M) —
+// in a fixed order (the arg-max's strided block → thread map and LDS tree; an all-masked block adds an exact 0).  The selection IS the arg-max,
+// so log p(token) = -log S.  Rows finished on entry hold 0 (a completion's log-prob is then the row sum), a row without any candidate -inf.
+template <bool LP>
 __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyArgs p) {
     __shared__ float sv[256];
     __shared__ int si[256];
+    __shared__ float ss[LP ? 256 : 1];
     const int b = blockIdx.x, tid = threadIdx.x;
     float best = -INFINITY;
     int bidx = 0x7fffffff;
@@ -205,6 +228,21 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyArgs p) {
         }
         __syncthreads();
     }
+    if constexpr (LP) {
+        const float M = sv[0];
+        float acc = 0.f;
+        for (int i = tid; i < p.nblk; i += 256) {
+            const float s = p.part_sum[(long)i * p.B + b];
+            const float v = p.part_val[(long)i * p.B + b];
+            acc += (s == 0.f || v == -INFINITY) ? 0.f : s * __builtin_amdgcn_exp2f((v - M) * 1.44269504088896341f);
+        }
+        ss[tid] = acc;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (tid < s) ss[tid] += ss[tid + s];
+            __syncthreads();
+        }
+    }
     const int step = *p.step;
     if (step < p.T_max) {
         const x16_t* h = p.hidden + (long)b * p.D;
@@ -217,8 +255,12 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyArgs p) {
         long next = unf ? (long)si[0] : (long)p.pad;                 // padt.py:749
         // a row whose logits are all NaN (an fp16 operand overflowed upstream: the range guard flags the batch, padt_check_finite) has no
         // arg-max — bidx is still the sentinel; continue with the pad token so that every later index stays inside its table
-        if (si[0] == 0x7fffffff || next < 0 || (p.seen && (next >> 5) >= p.seen_words)) next = (long)p.pad;
+        const bool no_choice = si[0] == 0x7fffffff || next < 0 || (p.seen && (next >> 5) >= p.seen_words);
+        if (no_choice) next = (long)p.pad;
         if (step < p.T_max) p.tokens_out[(long)b * p.T_max + step] = next;
+        if constexpr (LP) {
+            if (step >= 0 && step < p.T_max) p.logprobs[(long)b * p.T_max + step] = !unf ? 0.f : no_choice ? -INFINITY : 0.f - logf(ss[0]);
+        }
         p.cur_tok[b] = next;
         bool is_eos = next == p.eos;
         if (p.gen) {
@@ -309,22 +351,35 @@ extern "C" int padt_gen_rules(void* stream, const int* rules, const int* hist, l
 }
 #endif
 
-template <int MT, int NT, bool PACKED>
+template <int MT, int NT, bool PACKED, bool LSE>
 static void launch_head(const HeadArgs& a, int nblk, hipStream_t s) {
     constexpr int lds = 4 * NT * MT * 64 * 16;
     if constexpr (lds > 64 * 1024) {
         static PerDeviceOnce once;
-        once.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vrt_head_kernel<MT, NT, PACKED>),
+        once.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vrt_head_kernel<MT, NT, PACKED, LSE>),
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
     }
-    hipLaunchKernelGGL((vrt_head_kernel<MT, NT, PACKED>), dim3((nblk + NT - 1) / NT), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((vrt_head_kernel<MT, NT, PACKED, LSE>), dim3((nblk + NT - 1) / NT), dim3(256), lds, s, a);
+}
+
+template <bool LSE>
+static void dispatch_head(const HeadArgs& a, int nblk, hipStream_t s) {
+    if (a.Ep) {                                                 // NT = 4 table blocks per thread block (2 at 128 rows): profiles/r03_head_nt_ab.log
+        if (a.B <= 16) launch_head<1, 4, true, LSE>(a, nblk, s);
+        else if (a.B <= 32) launch_head<2, 4, true, LSE>(a, nblk, s);
+        else if (a.B <= 64) launch_head<4, 4, true, LSE>(a, nblk, s);
+        else launch_head<8, 2, true, LSE>(a, nblk, s);
+    } else if (a.B <= 16) launch_head<1, 1, false, LSE>(a, nblk, s);
+    else if (a.B <= 32) launch_head<2, 1, false, LSE>(a, nblk, s);
+    else if (a.B <= 64) launch_head<4, 1, false, LSE>(a, nblk, s);
+    else launch_head<8, 1, false, LSE>(a, nblk, s);
 }
 
 static int vrt_head_impl(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab,
                          const void* proto, long n_proto, const int* vrt_off, const int* mode_table,
                          const int* step, void* logits_f32, long ld_logits, void* part_val, void* part_idx,
                          long batch, long D, int eos, const void* embed_table_packed, const void* gen_cfg,
-                         const void* seen, long seen_words, const void* ban, long ban_words) {
+                         const void* seen, long seen_words, const void* ban, long ban_words, void* part_sum = nullptr) {
     if (batch <= 0) return 0;
     if (batch > 128 || (D & 7) || (ldh & 7)) { padt_set_error("padt_vrt_head: batch <= 128, D % 8 == 0 required"); return -1; }
     if (embed_table_packed && ((D & 31) || (vocab & 15) || ((uintptr_t)embed_table_packed & 15) || ((uintptr_t)hidden & 15))) {
@@ -334,20 +389,13 @@ static int vrt_head_impl(void* stream, const void* hidden, long ldh, const void*
     HeadArgs a{(const x16_t*)hidden, ldh, (const x16_t*)embed_table, (int)vocab, (const x16_t*)proto, (int)n_proto,
                vrt_off, mode_table, step, (float*)logits_f32, ld_logits, (float*)part_val, (int*)part_idx, (int)batch,
                (int)D, eos, (const x16_t*)embed_table_packed, (const GenCfg*)gen_cfg, (const unsigned*)seen, seen_words,
-               (const unsigned*)ban, ban_words};
+               (const unsigned*)ban, ban_words, (float*)part_sum};
     if (seen && seen_words * 32 < vocab + n_proto) { padt_set_error("padt_vrt_head: seen bitmap narrower than the table"); return -1; }
     if (ban && ban_words * 32 < vocab + n_proto) { padt_set_error("padt_vrt_head_ban: ban bitmap narrower than the table"); return -1; }
     const int nblk = (int)padt_vrt_head_nblk(vocab, n_proto);
     hipStream_t s = (hipStream_t)stream;
-    if (embed_table_packed) {                                   // NT = 4 table blocks per thread block (2 at 128 rows): profiles/r03_head_nt_ab.log
-        if (batch <= 16) launch_head<1, 4, true>(a, nblk, s);
-        else if (batch <= 32) launch_head<2, 4, true>(a, nblk, s);
-        else if (batch <= 64) launch_head<4, 4, true>(a, nblk, s);
-        else launch_head<8, 2, true>(a, nblk, s);
-    } else if (batch <= 16) launch_head<1, 1, false>(a, nblk, s);
-    else if (batch <= 32) launch_head<2, 1, false>(a, nblk, s);
-    else if (batch <= 64) launch_head<4, 1, false>(a, nblk, s);
-    else launch_head<8, 1, false>(a, nblk, s);
+    if (part_sum) dispatch_head<true>(a, nblk, s);
+    else dispatch_head<false>(a, nblk, s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
     return 0;
@@ -373,6 +421,19 @@ extern "C" int PADT_TWIN(padt_vrt_head_ban)(void* stream, const void* hidden, lo
                          part_idx, batch, D, eos, embed_table_packed, gen_cfg, seen, seen_words, ban, ban_words);
 }
 
+// padt_vrt_head_ban that also writes part_sum[blk * batch + b] = Σ exp(v - part_val) over block blk's 16 masked logits of sample b (the LSE
+// kernels): with padt_greedy_step_lp, the log-prob of every selected token without a logit row in memory.  Tokens, partials and any written
+// logits are those of padt_vrt_head_ban, bit for bit.
+extern "C" int PADT_TWIN(padt_vrt_head_lse)(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab,
+                             const void* proto, long n_proto, const int* vrt_off, const int* mode_table,
+                             const int* step, void* logits_f32, long ld_logits, void* part_val, void* part_idx,
+                             long batch, long D, int eos, const void* embed_table_packed, const void* gen_cfg,
+                             const void* seen, long seen_words, const void* ban, long ban_words, void* part_sum) {
+    if (batch > 0 && part_sum == nullptr) { padt_set_error("padt_vrt_head_lse: part_sum is required"); return -1; }
+    return vrt_head_impl(stream, hidden, ldh, embed_table, vocab, proto, n_proto, vrt_off, mode_table, step, logits_f32, ld_logits, part_val,
+                         part_idx, batch, D, eos, embed_table_packed, gen_cfg, seen, seen_words, ban, ban_words, part_sum);
+}
+
 #if !PADT_OP16_F16   // type-independent: compiled once
 extern "C" int padt_greedy_step(void* stream, const void* part_val, const void* part_idx, long nblk, long batch, long D,
                                 int eos, int pad, long t_max, int* unfinished, long* tokens_out, long* cur_tok,
@@ -382,9 +443,29 @@ extern "C" int padt_greedy_step(void* stream, const void* part_val, const void* 
     if (D & 7) { padt_set_error("padt_greedy_step: D % 8 == 0 required"); return -1; }
     GreedyArgs a{(const float*)part_val, (const int*)part_idx, (int)nblk, (int)batch, (int)D, eos, pad, (int)t_max,
                  unfinished, tokens_out, cur_tok, step, slot, lens, pos3, (const x16_t*)hidden, (x16_t*)hidden_buf,
-                 advance, (const GenCfg*)gen_cfg, (unsigned*)seen, seen_words};
+                 advance, (const GenCfg*)gen_cfg, (unsigned*)seen, seen_words, nullptr, nullptr};
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(greedy_step_kernel, dim3((unsigned)batch), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(greedy_step_kernel<false>, dim3((unsigned)batch), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, s, step);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    return 0;
+}
+
+// padt_greedy_step over the partials of padt_vrt_head_lse: also logprobs[b][*step] = log softmax(step's masked row)[selected token] — 0 for
+// a row already finished on entry, -inf where the sentinel branch emits pad (no candidate) — nothing once *step >= t_max.
+extern "C" int padt_greedy_step_lp(void* stream, const void* part_val, const void* part_idx, long nblk, long batch, long D,
+                                   int eos, int pad, long t_max, int* unfinished, long* tokens_out, long* cur_tok,
+                                   int* step, int* slot, int* lens, int* pos3, const void* hidden, void* hidden_buf,
+                                   int advance, const void* gen_cfg, void* seen, long seen_words, const void* part_sum, void* logprobs) {
+    if (batch <= 0) return 0;
+    if (D & 7) { padt_set_error("padt_greedy_step_lp: D % 8 == 0 required"); return -1; }
+    if (part_sum == nullptr || logprobs == nullptr) { padt_set_error("padt_greedy_step_lp: part_sum and logprobs are required"); return -1; }
+    GreedyArgs a{(const float*)part_val, (const int*)part_idx, (int)nblk, (int)batch, (int)D, eos, pad, (int)t_max,
+                 unfinished, tokens_out, cur_tok, step, slot, lens, pos3, (const x16_t*)hidden, (x16_t*)hidden_buf,
+                 advance, (const GenCfg*)gen_cfg, (unsigned*)seen, seen_words, (const float*)part_sum, (float*)logprobs};
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(greedy_step_kernel<true>, dim3((unsigned)batch), dim3(256), 0, s, a);
     hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, s, step);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
@@ -681,6 +762,67 @@ extern "C" int padt_argmax_rows_f32(void* stream, const void* scores_f32, long l
     }
     hipLaunchKernelGGL(argmax_rows_f32_kernel, dim3((unsigned)batch), dim3(1024), 0, (hipStream_t)stream, (const float*)scores_f32, ld, (int)n_cols,
                        (float*)part_val, (int*)part_idx);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    return 0;
+}
+
+// Token log-probs of the ROW path (generate(output_token_logprobs=True) under do_sample or with caller logits processors: the selection does
+// not come from the head's partials): one block per fp32 score row as the selection kernel left it (under sampling the warped row:
+// gen_cfg's write_back), between padt_sample_token / padt_argmax_rows_f32 and padt_greedy_step, which clears `unfinished`:
+// logprobs[b][*step] = unfinished[b] ? row[tok] - max - log Σ exp(row - max) : 0 with tok = part_idx[b]; -inf when the row has no candidate
+// or tok is not one.  Fixed order: strided columns per thread, LDS trees.
+__global__ __launch_bounds__(1024) void token_logprob_rows_f32_kernel(const float* __restrict__ x, long ld, int n, const int* __restrict__ part_idx,
+                                                                     const int* __restrict__ unfinished, const int* __restrict__ step,
+                                                                     float* __restrict__ logprobs, int t_max) {
+    __shared__ float red[1024];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* row = x + (long)b * ld;
+    float mx = -INFINITY;
+    for (int i = tid; i < n; i += 1024) { const float v = row[i]; mx = (v > mx || v != v) ? v : mx; }     // a NaN stays: the result is NaN then
+    red[tid] = mx;
+    __syncthreads();
+    for (int s2 = 512; s2 > 0; s2 >>= 1) {
+        if (tid < s2) { const float o = red[tid + s2], c = red[tid]; red[tid] = (o > c || o != o) ? o : c; }
+        __syncthreads();
+    }
+    const float M = red[0];
+    __syncthreads();
+    float acc = 0.f;
+    for (int i = tid; i < n; i += 1024) {
+        const float v = row[i];
+        acc += v == -INFINITY ? 0.f : __builtin_amdgcn_exp2f((v - M) * 1.44269504088896341f);
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int s2 = 512; s2 > 0; s2 >>= 1) {
+        if (tid < s2) red[tid] += red[tid + s2];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int t = *step;
+        if (t >= 0 && t < t_max) {
+            const int tok = part_idx[b];
+            float lp = 0.f;
+            if (unfinished[b]) {
+                const float v = (tok >= 0 && tok < n) ? row[tok] : -INFINITY;
+                lp = (v == -INFINITY || M == -INFINITY) ? -INFINITY : (v - M) - logf(red[0]);
+            }
+            logprobs[(long)b * t_max + t] = lp;
+        }
+    }
+}
+
+extern "C" int padt_token_logprob_rows_f32(void* stream, const void* rows_f32, long ld, long n_cols, const void* part_idx, const int* unfinished,
+                                           const int* step, void* logprobs, long t_max, long batch) {
+    if (batch <= 0) return 0;
+    if (rows_f32 == nullptr || n_cols <= 0 || n_cols > 0x7fffffffL || ld < n_cols || part_idx == nullptr || unfinished == nullptr || step == nullptr ||
+        logprobs == nullptr || t_max <= 0 || t_max > 0x7fffffffL) {
+        padt_set_error("padt_token_logprob_rows_f32: score rows (ld >= n_cols), the selection, the unfinished flags, the step counter and logprobs [batch][t_max] are required");
+        return -1;
+    }
+    hipLaunchKernelGGL(token_logprob_rows_f32_kernel, dim3((unsigned)batch), dim3(1024), 0, (hipStream_t)stream, (const float*)rows_f32, ld, (int)n_cols,
+                       (const int*)part_idx, unfinished, step, (float*)logprobs, (int)t_max);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
     return 0;

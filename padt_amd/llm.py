@@ -358,6 +358,9 @@ class DecodeSession:
         self.scores = None
         self.keep_logits = False         # output_logits=True under sampling: the rows before the warpers, in `raw_scores` [t_max][B][W]
         self.raw_scores = None
+        self.keep_lp = False             # output_token_logprobs=True: log p of every selected token in `logprobs` [B][t_max], no logit row kept
+        self.part_sum = None             # ... from the head's per-block Σ exp(logit - block max) [nblk][B] (fused path), allocated on first use
+        self.logprobs = None
         self.rope_cs = z(B, hd // 2, 2, dt=torch.float32)
         self.n_qkv = (cfg.num_attention_heads + 2 * Hkv) * hd
         self.graphs = {}                 # captured decode-step graph per mode (greedy / sampling: different kernel sequences)
@@ -404,10 +407,28 @@ class DecodeSession:
         ops.check_finite(self.hn, self.nf, rows_per_flag=1, rows=B)      # sticky per-row flag, read once per generate (modeling.generate_collect)
         self.head_and_select(self.hn, advance=True)
 
+    def want_logprobs(self, on: bool):
+        """Start of a generate: output_token_logprobs on / off; the buffers are allocated on first use and zeroed for every generate that asks."""
+        self.keep_lp = bool(on)
+        if not on:
+            return
+        if self.logprobs is None:
+            dev = self.part_val.device
+            self.part_sum = torch.zeros(self.nblk * self.B, device=dev, dtype=torch.float32)
+            self.logprobs = torch.zeros((self.B, self.t_max), device=dev, dtype=torch.float32)
+        else:
+            self.part_sum.zero_()
+            self.logprobs.zero_()
+
     def head_and_select(self, hn, advance: bool):
         cfg, W = self.cfg, self.W
         hp = W.get("llm.head.wp")
         lg = None
+        hk = self.hooks
+        # token log-probs: from the head's partials (the LSE head + padt_greedy_step_lp, no logit row) when the token is their arg-max; from
+        # the fp32 row the selection kernel read when it is not (sampling, caller processors rewrote the row)
+        lp_rows = self.keep_lp and (self.do_sample or (hk is not None and bool(hk["processors"])))
+        psum = self.part_sum if (self.keep_lp and not lp_rows) else None
         if self.do_sample or self.keep_scores:               # the sampling kernel / output_scores need the whole masked / penalised logit row
             if self.logits is None:
                 self.logits = torch.empty((self.B, (cfg.vocab_size + self.np_max + 3) // 4 * 4), device=hn.device, dtype=torch.float32)
@@ -419,11 +440,11 @@ class DecodeSession:
             ops.pack_rows(hn, self.hn_pk, self.B, to_packed=True)
             ops.vrt_head(self.hn_pk, W["llm.head"], self.proto, self.vrt_off, self.part_val, self.part_idx, cfg.eos_token_id,
                          mode_table=self.mode_table, step=self.step, table_packed=hp, rows=self.B, gen_cfg=self.gen_cfg,
-                         seen=self.seen, logits=lg, ban=ban)
+                         seen=self.seen, logits=lg, ban=ban, **({} if psum is None else {"part_sum": psum}))
         else:
             ops.vrt_head(hn, W["llm.head"], self.proto, self.vrt_off, self.part_val, self.part_idx, cfg.eos_token_id,
-                         mode_table=self.mode_table, step=self.step, gen_cfg=self.gen_cfg, seen=self.seen, logits=lg, ban=ban)
-        hk = self.hooks
+                         mode_table=self.mode_table, step=self.step, gen_cfg=self.gen_cfg, seen=self.seen, logits=lg, ban=ban,
+                         **({} if psum is None else {"part_sum": psum}))
         if hk is not None and hk["processors"]:
             # padt.py:717 `next_token_scores = logits_processor(input_ids, next_token_logits)` with the CALLER's processors: they see the rows the head
             # wrote (logit mask + the built-in processors applied) and the sequences so far, and what they return is what is scored / selected / kept
@@ -441,7 +462,7 @@ class DecodeSession:
             ops.stash_step_f32(lg, self.step, self.scores)
         nblk = self.nblk
         if self.do_sample:                                   # padt.py:740-743: multinomial over softmax of the warped scores
-            # with keep_scores the session's gen_cfg has write_back set: lg then holds the warped rows (l / T, -inf outside top-k / top-p),
+            # with keep_scores (or keep_lp) the session's gen_cfg has write_back set: lg then holds the warped rows (l / T, -inf outside top-k / top-p),
             # HF's next_token_scores — the warpers are part of its logits_processor (padt.py:717)
             ops.sample_token(lg, cfg.vocab_size + self.np_max, self.gen_cfg, self.step, self.part_val, self.part_idx, self.B)
             if self.keep_scores:
@@ -450,9 +471,12 @@ class DecodeSession:
         elif hk is not None and hk["processors"]:            # the head's fused arg-max partials describe the rows BEFORE the caller's processors
             ops.argmax_rows(lg, cfg.vocab_size + self.np_max, self.part_val, self.part_idx, self.B)
             nblk = 1
+        if lp_rows:                                          # before greedy_step clears `unfinished` and bumps the step counter
+            ops.token_logprob_rows(lg, cfg.vocab_size + self.np_max, self.part_idx, self.unfinished, self.step, self.logprobs, self.B)
         ops.greedy_step(self.part_val, self.part_idx, nblk, hn, self.hidden_buf, self.unfinished, self.tokens,
                         self.cur_tok, self.step, self.slot, self.lens, self.pos3, cfg.eos_token_id, cfg.pad_token_id,
-                        advance=advance, gen_cfg=self.gen_cfg, seen=self.seen)
+                        advance=advance, gen_cfg=self.gen_cfg, seen=self.seen,
+                        **({} if psum is None else {"part_sum": psum, "logprobs": self.logprobs}))
         if hk is not None:
             hk["t"] += 1
             if hk["criteria"]:
@@ -472,7 +496,7 @@ class DecodeSession:
             for _ in range(n):
                 one_step()
             return
-        gkey = (self.do_sample, self.keep_scores, self.keep_logits, self.step_fn is not None, self.rules_on)   # different kernel sequences → one captured graph per mode
+        gkey = (self.do_sample, self.keep_scores, self.keep_logits, self.step_fn is not None, self.rules_on, self.keep_lp)   # different kernel sequences → one captured graph per mode
         if gkey not in self.graphs:
             one_step()                                       # real step; also pays every one-time kernel attribute call
             n -= 1

@@ -308,7 +308,8 @@ class PaDTForConditionalGeneration:
                  temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  seed: Optional[int] = None, max_length: Optional[int] = None, output_scores: bool = False, output_logits: bool = False,
                  pad_token_id: Optional[int] = None, logits_processor=None, stopping_criteria=None, no_repeat_ngram_size: Optional[int] = None,
-                 bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, generation_config=None, image_index=None, **kwargs):
+                 bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, generation_config=None, image_index=None,
+                 output_token_logprobs: bool = False, **kwargs):
         """Greedy generation over the unified text‖VRT vocabulary.
 
         ``image_index`` (several queries on one image): a length-B sequence or int tensor; sample b uses image ``image_index[b]`` of the
@@ -355,6 +356,14 @@ class PaDTForConditionalGeneration:
         (padt.py:292-301) and the logits processors (repetition penalty, the synthetic ``schedule``), i.e. what the arg-max saw; under
         ``do_sample=True`` also after HF's warpers, which are part of ``logits_processor`` there (padt.py:717-720): ``logits / temperature`` on
         the tokens top-k / top-p keep, ``-inf`` on every other one.  Stopping criteria that take scores get the same rows.
+        ``output_token_logprobs=True``: ``.token_logprobs`` = a (B, n_steps) fp32 tensor (n_steps = the generated columns of ``sequences``) with
+        ``token_logprobs[b, t] = log_softmax(scores[t][b])[token]`` for the rows ``output_scores=True`` would return — after the logit mask, the
+        ``schedule``, the repetition penalty, the four bans, the caller's ``logits_processor`` and, under ``do_sample=True``, the warpers: HF's
+        ``compute_transition_scores(..., normalize_logits=True)`` — WITHOUT any logit row being written: the head reduces every 16-row block to
+        (max, Σ exp) in registers and the bookkeeping kernel folds the blocks (sampling / caller processors: one extra pass over the fp32 row
+        the selection kernel reads anyway).  Two deviations: steps after a row's EOS (its pad tokens) hold ``0.0``, so ``token_logprobs.sum(1)``
+        is the completion's log-prob (the EOS step holds its value); a row whose every candidate is banned emits pad and holds ``-inf`` there.
+        Default ``False``: the field is ``None`` and no kernel changes.
         ``output_logits=True`` (padt.py:721-724, the rows BEFORE the processors and warpers): served when no processor is active
         (repetition_penalty == 1, no schedule, none of the four bans — then, under greedy decoding, they ARE the scores), rejected otherwise.  ``pad_token_id``: must be the config's (the greedy kernel pads finished
         rows with it, padt.py:749).
@@ -404,7 +413,8 @@ class PaDTForConditionalGeneration:
                                    eos_token_id=eos_token_id, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
                                    keep_scores=bool(output_scores or output_logits or hooks is not None), hooks=hooks,
                                    keep_logits=bool(output_logits), no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
-                                   suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens, image_index=image_index)
+                                   suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens, image_index=image_index,
+                                   output_token_logprobs=bool(output_token_logprobs))
         return self.generate_collect(ctx, output_hidden_states, return_dict_in_generate, output_scores=bool(output_scores),
                                      output_logits=bool(output_logits))
 
@@ -413,7 +423,7 @@ class PaDTForConditionalGeneration:
                         schedule=None, sync_every=16, use_graph=True, lane=0, decode_stream=None, group=None, n_slots=1,
                         repetition_penalty=None, eos_token_id=None, temperature=None, top_k=None, top_p=None, seed=None,
                         vit_stream=None, inputs_ready=None, keep_scores=False, hooks=None, keep_logits=False, no_repeat_ngram_size=None,
-                        bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None):
+                        bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None, output_token_logprobs=False):
         """Asynchronous half of generate(): host integer prep + every kernel up to the first host sync point, enqueued on
         the current stream (the decode steps on ``decode_stream`` if given, ordered after the prefill by an event).
         Returns a group context for generate_collect().
@@ -438,7 +448,7 @@ class PaDTForConditionalGeneration:
             return owner.generate_launch(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, do_sample, schedule, sync_every,
                                          use_graph, lane, decode_stream, group, n_slots, repetition_penalty, eos_token_id, temperature, top_k, top_p,
                                          seed, vit_stream, inputs_ready, keep_scores, hooks, keep_logits, no_repeat_ngram_size, bad_words_ids,
-                                         suppress_tokens, begin_suppress_tokens, image_index)
+                                         suppress_tokens, begin_suppress_tokens, image_index, output_token_logprobs)
         self._batches_seen += 1
         gc = self.generation_config
         do_sample = gc.do_sample if do_sample is None else do_sample
@@ -472,7 +482,9 @@ class PaDTForConditionalGeneration:
             raise NotImplementedError("generate(output_logits=True) with a logits processor active (no_repeat_ngram_size, bad_words_ids, suppress_tokens "
                                       "or begin_suppress_tokens): only the processed rows are kept on this path — ask for output_scores=True")
         # under sampling the scores are the warped rows (sample_token writes them back), so output_logits needs a stash of its own
-        gen_key = (float(repetition_penalty), tuple(eos_list), samp, bool(keep_scores), bool(keep_logits) and samp is not None, rules)
+        # output_token_logprobs changes the step's kernels (LSE head / row kernel): part of the key, so batches that disagree never share a session
+        gen_key = (float(repetition_penalty), tuple(eos_list), samp, bool(keep_scores), bool(keep_logits) and samp is not None, rules,
+                   bool(output_token_logprobs))
         grid = image_grid_thw.detach().cpu().long()
         B = input_ids.shape[0]
         T_max = int(max_new_tokens)
@@ -498,10 +510,11 @@ class PaDTForConditionalGeneration:
             sess.gen_cfg.copy_(ops.gen_cfg_tensor(gen_key[0], gen_key[1], "cpu", do_sample=samp is not None, seed=samp[3] if samp else 0,
                                                   temperature=samp[0] if samp else 1.0, top_k=samp[1] if samp else 0,
                                                   top_p=samp[2] if samp else 1.0,
-                                                  write_back=samp is not None and bool(keep_scores)).to(dev, non_blocking=True))
+                                                  write_back=samp is not None and bool(keep_scores or output_token_logprobs)).to(dev, non_blocking=True))
             sess.do_sample = samp is not None
             sess.keep_scores = bool(keep_scores)
             sess.keep_logits = gen_key[4]
+            sess.want_logprobs(gen_key[6])
             sess.rules_on = rules is not None
             if rules is not None:
                 sess.rules.copy_(ops.gen_rules_tensor(key=rules).to(dev, non_blocking=True))
@@ -709,6 +722,7 @@ class PaDTForConditionalGeneration:
             out = CustomGenerateDecoderOnlyOutput(
                 sequences=sequences, scores=scores if output_scores else None, logits=logits, attentions=None,
                 hidden_states=hidden if output_hidden_states else None, past_key_values=sess,
+                token_logprobs=sess.logprobs[row0: row0 + B, :n_steps].clone() if group["gen_key"][6] else None,
                 past_image_embeds=sub["proto"].clone(),
                 past_logit_mask=ops.logit_mask(sess.vrt_off[row0: row0 + B + 1], cfg.vocab_size, table_rows, sub["proto_row0"], B),
                 past_high_res_image_embeds=sub["high"], past_visual_pe=sub["pe"])
@@ -749,7 +763,7 @@ class PaDTForConditionalGeneration:
                            schedule=group["schedule"], sync_every=group["sync_every"], use_graph=group["use_graph"], lane=("fb", group["lane"]),
                            repetition_penalty=pen, eos_token_id=list(eos), output_hidden_states=output_hidden_states,
                            return_dict_in_generate=return_dict_in_generate, image_index=image_index,
-                           output_scores=bool(group["gen_key"][3]) and (group.get("hooks") is None or group["hooks"]["pass_scores"]), **kw_rules, **kw)
+                           output_token_logprobs=bool(group["gen_key"][6]), output_scores=bool(group["gen_key"][3]) and (group.get("hooks") is None or group["hooks"]["pass_scores"]), **kw_rules, **kw)
 
     # ------------------------------------------------------------------ vl_decode (padt.py:342-412)
     @torch.no_grad()

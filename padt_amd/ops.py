@@ -734,15 +734,20 @@ def vrt_head_nblk(vocab, n_proto):
 
 
 def vrt_head(hidden, table, proto, vrt_off, part_val, part_idx, eos, mode_table=None, step=None, logits=None,
-             table_packed=None, rows=None, gen_cfg=None, seen=None, ban=None):
+             table_packed=None, rows=None, gen_cfg=None, seen=None, ban=None, part_sum=None):
     """table_packed: pack_weight(table) — then `hidden` is a fragment-packed activation buffer holding `rows` valid rows.
-    ban: int32 (rows, words) bitmap of banned table rows (gen_rules) → padt_vrt_head_ban; None is padt_vrt_head itself."""
+    ban: int32 (rows, words) bitmap of banned table rows (gen_rules) → padt_vrt_head_ban; None is padt_vrt_head itself.
+    part_sum: fp32 (nblk * rows) → padt_vrt_head_lse: also each block's Σ exp(logit - block max) per row (greedy_step(part_sum=, logprobs=))."""
     dt = _x16(hidden, table, proto, table_packed)
     B = hidden.shape[0] if rows is None else rows
     name, extra = "padt_vrt_head", ()
     if ban is not None:
         assert ban.dtype == torch.int32 and ban.is_cuda and ban.dim() == 2 and ban.is_contiguous() and ban.shape[0] >= B
         name, extra = "padt_vrt_head_ban", (_p(ban), ban.shape[1])
+    if part_sum is not None:
+        assert part_sum.dtype == torch.float32 and part_sum.is_cuda and part_sum.is_contiguous()
+        assert part_sum.numel() >= (table.shape[0] + proto.shape[0] + 15) // 16 * B
+        name, extra = "padt_vrt_head_lse", ((_p(ban), ban.shape[1]) if ban is not None else (0, 0)) + (_p(part_sum),)
     _lib.check(_fn(name, dt)(_stream(), _p(hidden), hidden.stride(0), _p(table), table.shape[0], _p(proto),
                              proto.shape[0], _p(vrt_off), _p(mode_table), _p(step), _p(logits),
                              logits.stride(0) if logits is not None else 0, _p(part_val), _p(part_idx),
@@ -880,10 +885,31 @@ def argmax_rows(scores, n_cols, part_val, part_idx, batch):
                "padt_argmax_rows_f32")
 
 
+def token_logprob_rows(rows, n_cols, part_idx, unfinished, step, logprobs, batch):
+    """logprobs[b][*step] = unfinished[b] ? log_softmax(rows[b][:n_cols])[part_idx[b]] : 0 (padt_token_logprob_rows_f32): the token log-prob
+    where the selection came from sample_token / argmax_rows; runs between that kernel and greedy_step (which clears `unfinished`)."""
+    assert rows.dtype == torch.float32 and rows.is_cuda and rows.dim() == 2 and rows.stride(1) == 1 and rows.shape[0] >= batch and rows.shape[1] >= n_cols
+    assert part_idx.dtype == torch.int32 and part_idx.numel() >= batch and unfinished.dtype == torch.int32 and unfinished.numel() >= batch
+    assert step.dtype == torch.int32 and logprobs.dtype == torch.float32 and logprobs.dim() == 2 and logprobs.is_contiguous() and logprobs.shape[0] >= batch
+    _lib.check(_lib.load().padt_token_logprob_rows_f32(_stream(), _p(rows), rows.stride(0), int(n_cols), _p(part_idx), _p(unfinished), _p(step),
+                                                       _p(logprobs), logprobs.shape[1], int(batch)), "padt_token_logprob_rows_f32")
+
+
 def greedy_step(part_val, part_idx, nblk, hidden, hidden_buf, unfinished, tokens_out, cur_tok, step, slot, lens, pos3,
-                eos, pad, advance=True, gen_cfg=None, seen=None):
+                eos, pad, advance=True, gen_cfg=None, seen=None, part_sum=None, logprobs=None):
+    """part_sum / logprobs (both or neither): vrt_head(part_sum=)'s block sums and the fp32 (B, T_max) buffer that gets the selected token's
+    log-prob at the device step counter (padt_greedy_step_lp)."""
     lib = _lib.load()
     B, D = hidden.shape
+    if part_sum is not None or logprobs is not None:
+        assert part_sum is not None and logprobs is not None, "greedy_step: part_sum and logprobs go together"
+        assert part_sum.dtype == torch.float32 and part_sum.is_cuda and part_sum.is_contiguous() and part_sum.numel() >= nblk * B
+        assert logprobs.dtype == torch.float32 and logprobs.is_cuda and logprobs.is_contiguous() and logprobs.shape == (B, tokens_out.shape[1])
+        _lib.check(lib.padt_greedy_step_lp(_stream(), _p(part_val), _p(part_idx), nblk, B, D, eos, pad, tokens_out.shape[1],
+                                           _p(unfinished), _p(tokens_out), _p(cur_tok), _p(step), _p(slot), _p(lens), _p(pos3),
+                                           _p(hidden), _p(hidden_buf), 1 if advance else 0, _p(gen_cfg), _p(seen),
+                                           seen.shape[1] if seen is not None else 0, _p(part_sum), _p(logprobs)), "padt_greedy_step_lp")
+        return
     _lib.check(lib.padt_greedy_step(_stream(), _p(part_val), _p(part_idx), nblk, B, D, eos, pad, tokens_out.shape[1],
                                     _p(unfinished), _p(tokens_out), _p(cur_tok), _p(step), _p(slot), _p(lens), _p(pos3),
                                     _p(hidden), _p(hidden_buf), 1 if advance else 0, _p(gen_cfg), _p(seen),

@@ -39,6 +39,8 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
     mask = need_thinking_mask if need_thinking_mask is not None else torch.Tensor([False] * B)
     completions, feats, labels, vrts, _ = parseVRTintoCompletion(processor, completion_ids, out["hidden_states"], mask)
     decoded = model.vl_decode(feats, out.past_image_embeds, out.past_high_res_image_embeds, image_grid_thw, out.past_visual_pe)
+    if out.token_logprobs is not None:                            # generate(output_token_logprobs=True) through **gen_kw
+        decoded["token_logprobs"] = out.token_logprobs
     return decoded, completions, labels, vrts
 
 
@@ -163,6 +165,8 @@ class PipelinedRunner:
                 self._mark(bid, "vl_begin", self.decode_streams[lane])
                 decoded = self.model.vl_decode(feats, out.past_image_embeds, out.past_high_res_image_embeds, grid, out.past_visual_pe)
                 self._mark(bid, "vl_end", self.decode_streams[lane])
+                if out.token_logprobs is not None:                # submit(output_token_logprobs=True)
+                    decoded["token_logprobs"] = out.token_logprobs
                 res.append((decoded, completions, labels, vrts))
         self.decode_streams[lane].synchronize()
         return res
