@@ -372,6 +372,22 @@ int  padt_argmax_rows_f32(void* stream, const void* scores_f32, long ld, long n_
  * logprobs[b][*step] = unfinished[b] ? rows[b][part_idx[b]] - logsumexp(rows[b][0..n_cols)) : 0; -inf for a row without a candidate. */
 int  padt_token_logprob_rows_f32(void* stream, const void* rows_f32, long ld, long n_cols, const void* part_idx, const int* unfinished,
                                  const int* step, void* logprobs, long t_max, long batch);
+/* generate(top_logprobs=k, output_patch_logprobs=True) (topk_rows.hip): the k best columns of every fp32 score row and their log-probs, and the
+ * log-probs of the sample's own patch columns, launched where padt_token_logprob_rows_f32 is (after the head, the sampler's write-back and the
+ * caller's processors; before padt_greedy_step).  At t = *step (nothing is written unless 0 <= t < t_max), for j < k:
+ * top_idx[b][t][j] (int32) = the column with the j-th largest value of rows[b][0..n_cols) — fp32 compare, equal values to the lower column
+ * first (padt_greedy_step's rule; -0.0 == +0.0; a NaN orders first) — and top_val[b][t][j] = that value - logsumexp(row); -1 / -inf once the
+ * finite columns run out.  patch_lp[b][t][j] (j < p_cap) = rows[b][vocab + vrt_off[b] + j] - logsumexp(row) for j < vrt_off[b + 1] - vrt_off[b],
+ * -inf beyond.  A finished row (unfinished[b] == 0) gets -1 / -inf in every slot.  top_idx / top_val are null exactly when k == 0 (then
+ * patch_lp is required); patch_lp may be null, vrt_off with it.  The rows are not written, columns at n_cols and beyond are not read.  Two
+ * launches: a (chunk of padt_topk_rows_chunk() columns, row) grid that leaves each chunk's max, sum of exponentials and k best in
+ * `workspace` (padt_topk_rows_workspace bytes, 8-byte aligned), then one block per row; exact selection and fixed-order sums: the same
+ * rows give the same bits.  k <= 32, n_cols <= 128 chunks. */
+long padt_topk_rows_chunk(void);
+long padt_topk_rows_workspace(long n_cols, long k, long batch);
+int  padt_topk_logprob_rows_f32(void* stream, const void* rows_f32, long ld, long n_cols, long k, const int* unfinished, const int* step,
+                                long t_max, void* top_idx, void* top_val, const int* vrt_off, long vocab, void* patch_lp, long p_cap,
+                                void* workspace, long batch);
 /* The synchronising half of generate() (padt.py:745-757 stop rule, :203 table assert, the range guard's flags) in ONE launch + one small
  * D2H copy: out[0] = *err, out[1] = any(unfinished[0..n_rows)), out[2..] = nf_rows[n_rows], nf_batch[n_batch], first_eos[n_rows] — the first
  * step t < done at which a row's token is an EOS id (eos or gen_cfg's list), -1 if none.  out holds 2 + 2 n_rows + n_batch int32. */

@@ -361,6 +361,13 @@ class DecodeSession:
         self.keep_lp = False             # output_token_logprobs=True: log p of every selected token in `logprobs` [B][t_max], no logit row kept
         self.part_sum = None             # ... from the head's per-block Σ exp(logit - block max) [nblk][B] (fused path), allocated on first use
         self.logprobs = None
+        self.top_k = 0                   # top_logprobs=k: the k best columns of every step's score row in `top_idx` / `top_val` [B][t_max][k] (per k, on first use)
+        self.top_idx = self.top_val = None
+        self.top_flat = None             # ... views of ONE flat pair sized for k = 32
+        self.keep_patch = False          # output_patch_logprobs=True: every sample's own patch columns in `patch_lp` [B][t_max][p_cap]
+        self.p_cap = 0
+        self.patch_lp = None
+        self.topk_ws = None              # padt_topk_logprob_rows_f32's chunk workspace, sized for k = 32
         self.rope_cs = z(B, hd // 2, 2, dt=torch.float32)
         self.n_qkv = (cfg.num_attention_heads + 2 * Hkv) * hd
         self.graphs = {}                 # captured decode-step graph per mode (greedy / sampling: different kernel sequences)
@@ -420,6 +427,36 @@ class DecodeSession:
             self.part_sum.zero_()
             self.logprobs.zero_()
 
+    GKEY_PATCH = 7                       # position of keep_patch in run_steps' graph key (want_top drops the graphs captured over an outgrown patch buffer)
+
+    def want_top(self, k: int, patches: bool, p_cap: int = 0):
+        """Start of a generate: top_logprobs=k (0: off) and output_patch_logprobs (p_cap: the largest patch count of one sample).  The
+        buffers are allocated on first use — ONE flat (ids, values) pair sized for k = 32, of which a generate uses the leading B * t_max * k
+        elements as [B][t_max][k], so a captured step keeps its addresses and memory does not grow with the k values asked; the patch buffer
+        grows, and the graphs captured over the smaller one go with it — and set to the finished-row values (-1 / -inf) for every generate that asks."""
+        self.top_k, self.keep_patch = int(k), bool(patches)
+        self.top_idx = self.top_val = None
+        if not (self.top_k or self.keep_patch):
+            return
+        dev = self.part_val.device
+        if self.topk_ws is None:
+            nbytes = ops.topk_rows_workspace(self.cfg.vocab_size + self.np_max, ops.TOPK_ROWS_MAX_K, self.B)
+            self.topk_ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        if self.top_k:
+            if self.top_flat is None:
+                n = self.B * self.t_max * ops.TOPK_ROWS_MAX_K
+                self.top_flat = (torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=torch.float32))
+            n = self.B * self.t_max * self.top_k
+            self.top_idx, self.top_val = (f[:n].view(self.B, self.t_max, self.top_k) for f in self.top_flat)
+            self.top_idx.fill_(-1)
+            self.top_val.fill_(float("-inf"))
+        if self.keep_patch:
+            if self.patch_lp is None or self.p_cap < p_cap:
+                self.graphs = {g: v for g, v in self.graphs.items() if not g[self.GKEY_PATCH]}      # their launches hold the old buffer's address
+                self.p_cap = max(int(p_cap), 1)
+                self.patch_lp = torch.empty((self.B, self.t_max, self.p_cap), device=dev, dtype=torch.float32)
+            self.patch_lp.fill_(float("-inf"))
+
     def head_and_select(self, hn, advance: bool):
         cfg, W = self.cfg, self.W
         hp = W.get("llm.head.wp")
@@ -429,7 +466,8 @@ class DecodeSession:
         # the fp32 row the selection kernel read when it is not (sampling, caller processors rewrote the row)
         lp_rows = self.keep_lp and (self.do_sample or (hk is not None and bool(hk["processors"])))
         psum = self.part_sum if (self.keep_lp and not lp_rows) else None
-        if self.do_sample or self.keep_scores:               # the sampling kernel / output_scores need the whole masked / penalised logit row
+        top_on = bool(self.top_k or self.keep_patch)          # top_logprobs / output_patch_logprobs read the whole processed row too
+        if self.do_sample or self.keep_scores or top_on:     # the sampling kernel / output_scores need the whole masked / penalised logit row
             if self.logits is None:
                 self.logits = torch.empty((self.B, (cfg.vocab_size + self.np_max + 3) // 4 * 4), device=hn.device, dtype=torch.float32)
             lg = self.logits
@@ -473,6 +511,10 @@ class DecodeSession:
             nblk = 1
         if lp_rows:                                          # before greedy_step clears `unfinished` and bumps the step counter
             ops.token_logprob_rows(lg, cfg.vocab_size + self.np_max, self.part_idx, self.unfinished, self.step, self.logprobs, self.B)
+        if top_on:                                           # the row as selected from (warped under sampling: write_back), `unfinished` as on entry
+            ops.topk_logprob_rows(lg, cfg.vocab_size + self.np_max, self.unfinished, self.step, self.topk_ws, self.B, top_idx=self.top_idx,
+                                  top_val=self.top_val, vrt_off=self.vrt_off if self.keep_patch else None, vocab=cfg.vocab_size,
+                                  patch_lp=self.patch_lp if self.keep_patch else None)
         ops.greedy_step(self.part_val, self.part_idx, nblk, hn, self.hidden_buf, self.unfinished, self.tokens,
                         self.cur_tok, self.step, self.slot, self.lens, self.pos3, cfg.eos_token_id, cfg.pad_token_id,
                         advance=advance, gen_cfg=self.gen_cfg, seen=self.seen,
@@ -496,7 +538,8 @@ class DecodeSession:
             for _ in range(n):
                 one_step()
             return
-        gkey = (self.do_sample, self.keep_scores, self.keep_logits, self.step_fn is not None, self.rules_on, self.keep_lp)   # different kernel sequences → one captured graph per mode
+        gkey = (self.do_sample, self.keep_scores, self.keep_logits, self.step_fn is not None, self.rules_on, self.keep_lp, self.top_k,
+                self.keep_patch)   # keep_patch sits at GKEY_PATCH; different kernel sequences (and output buffers) → one captured graph per mode
         if gkey not in self.graphs:
             one_step()                                       # real step; also pays every one-time kernel attribute call
             n -= 1

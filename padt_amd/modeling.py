@@ -11,6 +11,7 @@ There is no HuggingFace modeling code and no PyTorch compute on this path: the m
 libpadt_hip.so (see vision.py / llm.py / decoder.py) and fail loudly if that library is missing.
 """
 import json
+import numbers
 import os
 from types import SimpleNamespace
 from typing import Optional, Sequence
@@ -133,6 +134,22 @@ def check_generate_kwargs(kwargs: dict, max_new_tokens, max_length, prompt_len) 
             return int(max_length) - int(prompt_len)
         return 1024
     return int(max_new_tokens)
+
+
+TOP_LOGPROBS_MAX = ops.TOPK_ROWS_MAX_K
+
+
+def check_top_logprobs(top_logprobs) -> int:
+    """generate(top_logprobs=...) → k: None / 0 is off (0), 1 <= k <= 32 asks for the k best candidates of every step; a negative or
+    non-integer value raises ValueError, a larger one NotImplementedError naming the argument and the cap."""
+    if top_logprobs is None:
+        return 0
+    if isinstance(top_logprobs, bool) or not isinstance(top_logprobs, numbers.Integral) or int(top_logprobs) < 0:
+        raise ValueError(f"generate(top_logprobs={top_logprobs!r}): a non-negative integer (or None) is required")
+    if int(top_logprobs) > TOP_LOGPROBS_MAX:
+        raise NotImplementedError(f"generate(top_logprobs={int(top_logprobs)}): at most top_logprobs={TOP_LOGPROBS_MAX} candidates per step are "
+                                  "selected on the device — ask for output_scores=True and reduce the rows yourself beyond that")
+    return int(top_logprobs)
 
 
 # generate()'s named parameters a generation_config may carry: an explicit argument (not None) wins, as in HF (padt.py:436)
@@ -309,7 +326,7 @@ class PaDTForConditionalGeneration:
                  seed: Optional[int] = None, max_length: Optional[int] = None, output_scores: bool = False, output_logits: bool = False,
                  pad_token_id: Optional[int] = None, logits_processor=None, stopping_criteria=None, no_repeat_ngram_size: Optional[int] = None,
                  bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, generation_config=None, image_index=None,
-                 output_token_logprobs: bool = False, **kwargs):
+                 output_token_logprobs: bool = False, top_logprobs: Optional[int] = None, output_patch_logprobs: bool = False, **kwargs):
         """Greedy generation over the unified text‖VRT vocabulary.
 
         ``image_index`` (several queries on one image): a length-B sequence or int tensor; sample b uses image ``image_index[b]`` of the
@@ -364,6 +381,20 @@ class PaDTForConditionalGeneration:
         the selection kernel reads anyway).  Two deviations: steps after a row's EOS (its pad tokens) hold ``0.0``, so ``token_logprobs.sum(1)``
         is the completion's log-prob (the EOS step holds its value); a row whose every candidate is banned emits pad and holds ``-inf`` there.
         Default ``False``: the field is ``None`` and no kernel changes.
+        ``top_logprobs=k`` (1 <= k <= 32; ``None`` / 0: off; negative or not an integer: ``ValueError``; above 32: ``NotImplementedError``):
+        ``.top_token_ids`` (B, n_steps, k) int64 and ``.top_logprobs`` (B, n_steps, k) fp32 — entry j of step t is the column with the j-th
+        largest value of the row ``output_scores=True`` would return as ``scores[t][b]`` (same processing as above, warpers included) and
+        ``log_softmax(scores[t][b])`` there; descending, equal values to the lower column first (the arg-max's rule: under greedy decoding
+        entry 0 is the generated token).  Ids are numbered like ``sequences`` (VRT ids >= vocab_size, within the batch).  A step with fewer
+        than k finite candidates (a forced EOS, a sampler ``top_k`` below k, every column banned) fills the rest with id ``-1`` / ``-inf``;
+        so do all slots of the steps after a row's EOS (the EOS step holds its values).
+        ``output_patch_logprobs=True``: ``.patch_logprobs`` (B, n_steps, P) fp32, P = the largest patch count of the batch's samples:
+        ``patch_logprobs[b, t, j] = log_softmax(scores[t][b])[vocab_size + vrt_off[b] + j]`` — sample b's own patch j under the full-row
+        normaliser: the model's pointing belief over the image at that step; ``-inf`` for j past the sample's patch count, after the row's
+        EOS, and wherever the mask, schedule, a ban or a warper removed the column.
+        Both come from one selection pass over the step's fp32 row (``padt_topk_logprob_rows_f32``, inside the captured step; in plain
+        greedy mode the head writes the row into the session's single row buffer) — no row is kept.  They are independent of each other, of
+        ``output_token_logprobs`` and of ``output_scores``; a ``generation_config`` may carry them; off: the fields are ``None`` and no kernel changes.
         ``output_logits=True`` (padt.py:721-724, the rows BEFORE the processors and warpers): served when no processor is active
         (repetition_penalty == 1, no schedule, none of the four bans — then, under greedy decoding, they ARE the scores), rejected otherwise.  ``pad_token_id``: must be the config's (the greedy kernel pads finished
         rows with it, padt.py:749).
@@ -388,11 +419,16 @@ class PaDTForConditionalGeneration:
                     output_scores = output_scores or bool(v)
                 elif k == "output_logits":
                     output_logits = output_logits or bool(v)
+                elif k == "top_logprobs":
+                    top_logprobs = v if top_logprobs is None else top_logprobs
+                elif k == "output_patch_logprobs":
+                    output_patch_logprobs = output_patch_logprobs or bool(v)
                 elif k not in _GENERATE_CONFIG_OWN:
                     kwargs.setdefault(k, v)                           # the keyword policy below names what this path does not implement
             (max_new_tokens, max_length, do_sample, repetition_penalty, eos_token_id, pad_token_id, temperature, top_k, top_p, no_repeat_ngram_size,
              bad_words_ids, suppress_tokens, begin_suppress_tokens) = (named[k] for k in _GENERATE_CONFIG_NAMED)
         max_new_tokens = check_generate_kwargs(kwargs, max_new_tokens, max_length, None if input_ids is None else input_ids.shape[1])
+        top_logprobs = check_top_logprobs(top_logprobs)
         if pad_token_id is not None and int(pad_token_id) != int(self.generation_config.pad_token_id):
             raise NotImplementedError(f"generate(pad_token_id={pad_token_id}): finished rows are padded with the checkpoint's pad token "
                                       f"({self.generation_config.pad_token_id}) on this path")
@@ -414,7 +450,8 @@ class PaDTForConditionalGeneration:
                                    keep_scores=bool(output_scores or output_logits or hooks is not None), hooks=hooks,
                                    keep_logits=bool(output_logits), no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                                    suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens, image_index=image_index,
-                                   output_token_logprobs=bool(output_token_logprobs))
+                                   output_token_logprobs=bool(output_token_logprobs), top_logprobs=top_logprobs,
+                                   output_patch_logprobs=bool(output_patch_logprobs))
         return self.generate_collect(ctx, output_hidden_states, return_dict_in_generate, output_scores=bool(output_scores),
                                      output_logits=bool(output_logits))
 
@@ -423,7 +460,8 @@ class PaDTForConditionalGeneration:
                         schedule=None, sync_every=16, use_graph=True, lane=0, decode_stream=None, group=None, n_slots=1,
                         repetition_penalty=None, eos_token_id=None, temperature=None, top_k=None, top_p=None, seed=None,
                         vit_stream=None, inputs_ready=None, keep_scores=False, hooks=None, keep_logits=False, no_repeat_ngram_size=None,
-                        bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None, output_token_logprobs=False):
+                        bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None, output_token_logprobs=False,
+                        top_logprobs=None, output_patch_logprobs=False):
         """Asynchronous half of generate(): host integer prep + every kernel up to the first host sync point, enqueued on
         the current stream (the decode steps on ``decode_stream`` if given, ordered after the prefill by an event).
         Returns a group context for generate_collect().
@@ -448,7 +486,9 @@ class PaDTForConditionalGeneration:
             return owner.generate_launch(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, do_sample, schedule, sync_every,
                                          use_graph, lane, decode_stream, group, n_slots, repetition_penalty, eos_token_id, temperature, top_k, top_p,
                                          seed, vit_stream, inputs_ready, keep_scores, hooks, keep_logits, no_repeat_ngram_size, bad_words_ids,
-                                         suppress_tokens, begin_suppress_tokens, image_index, output_token_logprobs)
+                                         suppress_tokens, begin_suppress_tokens, image_index, output_token_logprobs, top_logprobs,
+                                         output_patch_logprobs)
+        top_logprobs = check_top_logprobs(top_logprobs)
         self._batches_seen += 1
         gc = self.generation_config
         do_sample = gc.do_sample if do_sample is None else do_sample
@@ -484,7 +524,8 @@ class PaDTForConditionalGeneration:
         # under sampling the scores are the warped rows (sample_token writes them back), so output_logits needs a stash of its own
         # output_token_logprobs changes the step's kernels (LSE head / row kernel): part of the key, so batches that disagree never share a session
         gen_key = (float(repetition_penalty), tuple(eos_list), samp, bool(keep_scores), bool(keep_logits) and samp is not None, rules,
-                   bool(output_token_logprobs))
+                   bool(output_token_logprobs), top_logprobs, bool(output_patch_logprobs))      # ... and so are top_logprobs / output_patch_logprobs
+        want_rows = bool(top_logprobs or output_patch_logprobs)    # the selection reads the row: under sampling it must be the warped one (write_back)
         grid = image_grid_thw.detach().cpu().long()
         B = input_ids.shape[0]
         T_max = int(max_new_tokens)
@@ -497,6 +538,7 @@ class PaDTForConditionalGeneration:
             plan = plan_prompt_shared(cfg, input_ids, attention_mask, grid, image_index, dev, row0=row0, proto_row0=proto_row0)
         sh = plan.shared
         n_proto = plan.vrt_off[-1]
+        p_max = max(plan.vrt_off[i + 1] - plan.vrt_off[i] for i in range(B))      # output_patch_logprobs: the widest sample of this batch
         need_s = max(plan.lens) + T_max
         if rules is not None:
             need_s = max(need_s, plan.L_pad)                      # the session's history rows hold the padded prompt row
@@ -510,11 +552,12 @@ class PaDTForConditionalGeneration:
             sess.gen_cfg.copy_(ops.gen_cfg_tensor(gen_key[0], gen_key[1], "cpu", do_sample=samp is not None, seed=samp[3] if samp else 0,
                                                   temperature=samp[0] if samp else 1.0, top_k=samp[1] if samp else 0,
                                                   top_p=samp[2] if samp else 1.0,
-                                                  write_back=samp is not None and bool(keep_scores or output_token_logprobs)).to(dev, non_blocking=True))
+                                                  write_back=samp is not None and bool(keep_scores or output_token_logprobs or want_rows)).to(dev, non_blocking=True))
             sess.do_sample = samp is not None
             sess.keep_scores = bool(keep_scores)
             sess.keep_logits = gen_key[4]
             sess.want_logprobs(gen_key[6])
+            sess.want_top(gen_key[7], gen_key[8], p_max)
             sess.rules_on = rules is not None
             if rules is not None:
                 sess.rules.copy_(ops.gen_rules_tensor(key=rules).to(dev, non_blocking=True))
@@ -551,7 +594,7 @@ class PaDTForConditionalGeneration:
             sess = group["sess"]
             if (group["launched"] or k >= group["n_slots"] or B != group["B"] or T_max != group["T_max"]
                     or schedule != group["schedule"] or gen_key != group["gen_key"] or sess.s_max < need_s
-                    or sess.np_max < proto_row0 + n_proto):
+                    or sess.np_max < proto_row0 + n_proto or (gen_key[8] and sess.p_cap < p_max)):
                 return None
         if sh is not None:
             check_shared_destinations(sh, sess.B, sess.s_max)
@@ -621,7 +664,7 @@ class PaDTForConditionalGeneration:
             hn_all = self.lm.prefill(plan, low, sess, nf=nf)
             ops.gather_rows(hn_all, plan.last_idx, out=sess.hn_first[rows])
         group["subs"].append(dict(plan=plan, low=low, high=high, pe=pe, proto=proto, hn_all=hn_all, input_ids=input_ids,
-                                  n_proto=n_proto, row0=row0, proto_row0=proto_row0, nf=nf,
+                                  n_proto=n_proto, row0=row0, proto_row0=proto_row0, nf=nf, p_max=p_max,
                                   inputs=(attention_mask, pixel_values, image_grid_thw, image_index)))       # what a re-run on the bf16 twin needs
         group["proto_rows"] = proto_row0 + n_proto
         if len(group["subs"]) == group["n_slots"]:
@@ -719,10 +762,19 @@ class PaDTForConditionalGeneration:
                 return tuple(torch.cat([rows_t[t, :, :V], rows_t[t, :, V + p0: V + p0 + sub["n_proto"]]], dim=1) for t in range(n_steps))
             scores = per_step(sess.scores) if output_scores or output_logits else None
             logits = (per_step(sess.raw_scores) if sess.keep_logits else scores) if output_logits else None
+            top_ids = top_lp = patch_lp = None
+            if group["gen_key"][7]:                               # session columns → this batch's own VRT numbering, as assemble_sequences does
+                top_ids = sess.top_idx[row0: row0 + B, :n_steps].to(torch.int64)
+                if sub["proto_row0"]:
+                    top_ids = torch.where(top_ids >= cfg.vocab_size, top_ids - sub["proto_row0"], top_ids)
+                top_lp = sess.top_val[row0: row0 + B, :n_steps].clone()
+            if group["gen_key"][8]:
+                patch_lp = sess.patch_lp[row0: row0 + B, :n_steps, :sub["p_max"]].clone()
             out = CustomGenerateDecoderOnlyOutput(
                 sequences=sequences, scores=scores if output_scores else None, logits=logits, attentions=None,
                 hidden_states=hidden if output_hidden_states else None, past_key_values=sess,
                 token_logprobs=sess.logprobs[row0: row0 + B, :n_steps].clone() if group["gen_key"][6] else None,
+                top_token_ids=top_ids, top_logprobs=top_lp, patch_logprobs=patch_lp,
                 past_image_embeds=sub["proto"].clone(),
                 past_logit_mask=ops.logit_mask(sess.vrt_off[row0: row0 + B + 1], cfg.vocab_size, table_rows, sub["proto_row0"], B),
                 past_high_res_image_embeds=sub["high"], past_visual_pe=sub["pe"])
@@ -763,7 +815,8 @@ class PaDTForConditionalGeneration:
                            schedule=group["schedule"], sync_every=group["sync_every"], use_graph=group["use_graph"], lane=("fb", group["lane"]),
                            repetition_penalty=pen, eos_token_id=list(eos), output_hidden_states=output_hidden_states,
                            return_dict_in_generate=return_dict_in_generate, image_index=image_index,
-                           output_token_logprobs=bool(group["gen_key"][6]), output_scores=bool(group["gen_key"][3]) and (group.get("hooks") is None or group["hooks"]["pass_scores"]), **kw_rules, **kw)
+                           output_token_logprobs=bool(group["gen_key"][6]), top_logprobs=group["gen_key"][7],
+                           output_patch_logprobs=bool(group["gen_key"][8]), output_scores=bool(group["gen_key"][3]) and (group.get("hooks") is None or group["hooks"]["pass_scores"]), **kw_rules, **kw)
 
     # ------------------------------------------------------------------ vl_decode (padt.py:342-412)
     @torch.no_grad()

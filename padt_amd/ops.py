@@ -895,6 +895,52 @@ def token_logprob_rows(rows, n_cols, part_idx, unfinished, step, logprobs, batch
                                                        _p(logprobs), logprobs.shape[1], int(batch)), "padt_token_logprob_rows_f32")
 
 
+TOPK_ROWS_MAX_K = 32
+
+
+def __getattr__(name):
+    # TOPK_ROWS_CHUNK: columns per stage-1 block of padt_topk_logprob_rows_f32 — the kernel file's constant, read from the library on first use
+    if name == "TOPK_ROWS_CHUNK":
+        globals()[name] = int(_lib.load().padt_topk_rows_chunk())      # cached: this hook is not entered for it again
+        return globals()[name]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def topk_rows_workspace(n_cols, k, batch):
+    """Bytes of the workspace topk_logprob_rows needs for `batch` rows of `n_cols` columns and `k` candidates (padt_topk_rows_workspace)."""
+    return int(_lib.load().padt_topk_rows_workspace(int(n_cols), int(k), int(batch)))
+
+
+def topk_logprob_rows(rows, n_cols, unfinished, step, workspace, batch, top_idx=None, top_val=None, vrt_off=None, vocab=0, patch_lp=None):
+    """At t = *step, per row b < batch of the fp32 score rows (padt_topk_logprob_rows_f32; between the selection kernel and greedy_step):
+    top_idx[b, t, j] / top_val[b, t, j] (int32 / fp32 (>= batch, t_max, k), both or neither) = the column with the j-th largest value of
+    rows[b, :n_cols] (equal values: the lower column first) and its log_softmax; -1 / -inf once the finite columns run out.
+    patch_lp[b, t, j] (fp32 (>= batch, t_max, p_cap), with vrt_off int32 [>= batch + 1] and vocab) = log_softmax(row)[vocab + vrt_off[b] + j] for
+    the row's own vrt_off[b + 1] - vrt_off[b] patches, -inf beyond.  Finished rows get -1 / -inf everywhere; the rows are only read.
+    workspace: a uint8 tensor of at least topk_rows_workspace(n_cols, k, batch) bytes."""
+    assert rows.dtype == torch.float32 and rows.is_cuda and rows.dim() == 2 and rows.stride(1) == 1 and rows.shape[0] >= batch and rows.shape[1] >= n_cols
+    assert unfinished.dtype == torch.int32 and unfinished.numel() >= batch and step.dtype == torch.int32 and step.numel() >= 1
+    assert (top_idx is None) == (top_val is None), "topk_logprob_rows: top_idx and top_val go together"
+    k, t_max = 0, None
+    if top_idx is not None:
+        assert top_idx.dtype == torch.int32 and top_val.dtype == torch.float32 and top_idx.is_cuda and top_val.is_cuda
+        assert top_idx.dim() == 3 and top_idx.shape == top_val.shape and top_idx.is_contiguous() and top_val.is_contiguous() and top_idx.shape[0] >= batch
+        t_max, k = int(top_idx.shape[1]), int(top_idx.shape[2])
+    p_cap = 0
+    if patch_lp is not None:
+        assert patch_lp.dtype == torch.float32 and patch_lp.is_cuda and patch_lp.dim() == 3 and patch_lp.is_contiguous() and patch_lp.shape[0] >= batch
+        assert t_max is None or patch_lp.shape[1] == t_max, "topk_logprob_rows: top_idx and patch_lp disagree on t_max"
+        assert vrt_off is not None and vrt_off.dtype == torch.int32 and vrt_off.is_cuda and vrt_off.is_contiguous() and vrt_off.numel() >= batch + 1
+        t_max, p_cap = int(patch_lp.shape[1]), int(patch_lp.shape[2])
+    assert t_max is not None, "topk_logprob_rows: nothing asked (no top_idx / top_val and no patch_lp)"
+    assert workspace.dtype == torch.uint8 and workspace.is_cuda and workspace.is_contiguous()
+    lib = _lib.load()
+    assert k > TOPK_ROWS_MAX_K or workspace.numel() >= lib.padt_topk_rows_workspace(int(n_cols), k, int(batch)), "topk_logprob_rows: workspace too small"
+    _lib.check(lib.padt_topk_logprob_rows_f32(_stream(), _p(rows), rows.stride(0), int(n_cols), k, _p(unfinished), _p(step), t_max,
+                                                      _p(top_idx), _p(top_val), _p(vrt_off) if patch_lp is not None else 0, int(vocab),
+                                                      _p(patch_lp), p_cap, _p(workspace), int(batch)), "padt_topk_logprob_rows_f32")
+
+
 def greedy_step(part_val, part_idx, nblk, hidden, hidden_buf, unfinished, tokens_out, cur_tok, step, slot, lens, pos3,
                 eos, pad, advance=True, gen_cfg=None, seen=None, part_sum=None, logprobs=None):
     """part_sum / logprobs (both or neither): vrt_head(part_sum=)'s block sums and the fp32 (B, T_max) buffer that gets the selected token's

@@ -41,6 +41,9 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
     decoded = model.vl_decode(feats, out.past_image_embeds, out.past_high_res_image_embeds, image_grid_thw, out.past_visual_pe)
     if out.token_logprobs is not None:                            # generate(output_token_logprobs=True) through **gen_kw
         decoded["token_logprobs"] = out.token_logprobs
+    for name in ("top_token_ids", "top_logprobs", "patch_logprobs"):      # generate(top_logprobs=k, output_patch_logprobs=True), likewise
+        if out[name] is not None:
+            decoded[name] = out[name]
     return decoded, completions, labels, vrts
 
 
@@ -97,7 +100,9 @@ class PipelinedRunner:
     def submit(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens=1024, schedule=None,
                need_thinking_mask=None, sync_every=None, repetition_penalty=None, eos_token_id=None, no_repeat_ngram_size=None,
                bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None, **sampling):
-        """image_index: see generate(); the batch's results are those of the expanded batch."""
+        """image_index: see generate(); the batch's results are those of the expanded batch.
+        output_token_logprobs / top_logprobs / output_patch_logprobs (through **sampling, see generate()): the decoded dict of the batch carries
+        "token_logprobs" / "top_token_ids" + "top_logprobs" / "patch_logprobs" when asked; batches that disagree on them do not share a decode group."""
         done = []
         bid = self.n_batches
         self.n_batches += 1
@@ -167,6 +172,9 @@ class PipelinedRunner:
                 self._mark(bid, "vl_end", self.decode_streams[lane])
                 if out.token_logprobs is not None:                # submit(output_token_logprobs=True)
                     decoded["token_logprobs"] = out.token_logprobs
+                for name in ("top_token_ids", "top_logprobs", "patch_logprobs"):      # submit(top_logprobs=k, output_patch_logprobs=True)
+                    if out[name] is not None:
+                        decoded[name] = out[name]
                 res.append((decoded, completions, labels, vrts))
         self.decode_streams[lane].synchronize()
         return res
@@ -193,7 +201,9 @@ def _record_words(cap: int, mask_hw: int) -> int:
 def pack_results(decoded: dict, cap: int, mask_hw: int, device, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """vl_decode output → one int32 record (floats bit-cast) of fixed size, so every rank contributes the same shape.
     On the GPU this is ONE kernel launch (padt_pack_results: no host round trip, no H2D copy); host tensors (the protocol tests) are
-    packed with the equivalent indexing statements below."""
+    packed with the equivalent indexing statements below.
+    The record holds vl_decode's fields only: "token_logprobs", "top_token_ids", "top_logprobs" and "patch_logprobs" of a decoded dict
+    (generate's optional per-step outputs) are not carried through the exchange and are absent from what unpack_results returns."""
     n = decoded["pred_boxes"].shape[0]
     if n > cap:
         raise ValueError(f"{n} objects exceed the exchange capacity {cap}")
