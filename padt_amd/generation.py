@@ -1,0 +1,215 @@
+"""What a ``generate()`` call asks for, as host logic that imports without a GPU: the drop-in surface's argument policy (which HF / reference
+arguments are ignored, refused or unknown), ``GenOptions`` — the ONE named, hashable value a call's arguments and the checkpoint's
+generation_config.json resolve to, carried from ``generate_launch`` through the decode session to a re-run on the bf16 twin — and
+``StepMode``, the part of it that selects the decode step's kernel sequence (one captured graph per value)."""
+import numbers
+from dataclasses import dataclass
+from typing import NamedTuple, Optional
+
+import torch
+
+from . import ops
+
+
+# ------------------------------------------------------------------------------------------------ generate() argument policy
+# HF / reference generate() arguments that cannot change what this path returns: accepted when they hold one of the listed values
+# (None = any value), otherwise NotImplementedError.
+_GENERATE_IGNORED = {
+    "attn_implementation": None, "tokenizer": None, "assistant_tokenizer": None, "cache_implementation": None, "logits_to_keep": None,
+    "generation_config": (None,), "output_attentions": (False, None),
+    # GenerationConfig fields callers pass routinely and the reference's generate() accepts without effect on this path:
+    "bos_token_id": None, "decoder_start_token_id": None, "return_legacy_cache": None,
+    "num_beams": (1, None), "num_beam_groups": (1, None), "num_return_sequences": (1, None), "penalty_alpha": (None,), "min_new_tokens": (0, None),
+    "min_length": (0, None), "force_words_ids": (None,), "token_healing": (False, None),
+    "length_penalty": (1.0, None), "early_stopping": (False, None), "typical_p": (1.0, None), "min_p": (None,), "epsilon_cutoff": (0.0, None),
+    "eta_cutoff": (0.0, None), "encoder_repetition_penalty": (1.0, None), "guidance_scale": (None, 1.0), "renormalize_logits": (False, None),
+}
+# arguments the reference honours (padt.py:418-424,445,511-533,570-580,719-737) and this path does not implement
+# ... and, through generate()'s NAMED parameters only, the four pure-ban processors: as a stray keyword of check_generate_kwargs they stay refused
+_GENERATE_NAMED_ONLY = ("no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens")
+_GENERATE_REJECTED = ("inputs", "prefix_allowed_tokens_fn", "assistant_model", "streamer",
+                      "negative_prompt_ids", "negative_prompt_attention_mask", "pixel_values_videos", "video_grid_thw", "second_per_grid_ts",
+                      "inputs_embeds", "past_key_values", "position_ids", "cache_position", "rope_deltas", "stop_strings", "max_time",
+                      "sequence_bias", "forced_bos_token_id", "forced_eos_token_id",
+                      "exponential_decay_length_penalty", "prompt_lookup_num_tokens", "dola_layers", "labels")
+
+
+def check_generate_kwargs(kwargs: dict, max_new_tokens, max_length, prompt_len) -> int:
+    """The drop-in surface's argument policy (see generate()): → the effective max_new_tokens.  Raises NotImplementedError naming an
+    argument the reference honours and this path does not, ValueError (HF's _validate_model_kwargs wording) for an unknown one."""
+    for k in list(kwargs):
+        v = kwargs[k]
+        if k in _GENERATE_REJECTED or k in _GENERATE_NAMED_ONLY:
+            if v is None:
+                continue                                              # the reference's own default
+            raise NotImplementedError(f"generate({k}=...) is not implemented on the MI355X path (the reference honours it, padt.py:414-580): "
+                                      "remove the argument or run the reference for this call")
+        if k in _GENERATE_IGNORED:
+            ok = _GENERATE_IGNORED[k]
+            if ok is None or any(v is o or (not isinstance(v, (torch.Tensor, list, tuple, dict)) and v == o) for o in ok):
+                continue
+            raise NotImplementedError(f"generate({k}={v!r}) is not implemented on the MI355X path (supported: {ok})")
+        raise ValueError(f"The following `model_kwargs` are not used by the model: ['{k}'] (note: typos in the generate arguments will also "
+                         "show up in this list)")
+    if max_new_tokens is None:
+        if max_length is not None:
+            if prompt_len is None or int(max_length) <= int(prompt_len):
+                raise ValueError(f"Input length of input_ids is {prompt_len}, but `max_length` is set to {max_length}. This can lead to unexpected "
+                                 "behavior. You should consider increasing `max_length` or, better yet, setting `max_new_tokens`.")
+            return int(max_length) - int(prompt_len)
+        return 1024
+    return int(max_new_tokens)
+
+
+TOP_LOGPROBS_MAX = ops.TOPK_ROWS_MAX_K
+
+
+def check_top_logprobs(top_logprobs) -> int:
+    """generate(top_logprobs=...) → k: None / 0 is off (0), 1 <= k <= 32 asks for the k best candidates of every step; a negative or
+    non-integer value raises ValueError, a larger one NotImplementedError naming the argument and the cap."""
+    if top_logprobs is None:
+        return 0
+    if isinstance(top_logprobs, bool) or not isinstance(top_logprobs, numbers.Integral) or int(top_logprobs) < 0:
+        raise ValueError(f"generate(top_logprobs={top_logprobs!r}): a non-negative integer (or None) is required")
+    if int(top_logprobs) > TOP_LOGPROBS_MAX:
+        raise NotImplementedError(f"generate(top_logprobs={int(top_logprobs)}): at most top_logprobs={TOP_LOGPROBS_MAX} candidates per step are "
+                                  "selected on the device — ask for output_scores=True and reduce the rows yourself beyond that")
+    return int(top_logprobs)
+
+
+# generate()'s named parameters a generation_config may carry: an explicit argument (not None) wins, as in HF (padt.py:436)
+_GENERATE_CONFIG_NAMED = ("max_new_tokens", "max_length", "do_sample", "repetition_penalty", "eos_token_id", "pad_token_id", "temperature", "top_k",
+                          "top_p", "no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens")
+# ... and those whose value is this path's own default either way (hidden states and the dict output are what its callers consume)
+_GENERATE_CONFIG_OWN = ("use_cache", "output_hidden_states", "return_dict_in_generate")
+
+
+def generation_config_fields(generation_config) -> dict:
+    """generate(generation_config=): the fields a ``transformers.GenerationConfig`` sets to something other than its default (to_diff_dict),
+    or the entries of a dict; bookkeeping entries (``transformers_version``, ``_from_model_config`` …) are dropped.  Anything else is not a
+    generation config: NotImplementedError naming the argument."""
+    if generation_config is None:
+        return {}
+    if isinstance(generation_config, dict):
+        d = dict(generation_config)
+    else:
+        try:
+            from transformers import GenerationConfig
+        except ImportError:                                           # no transformers: only dicts can be configs
+            GenerationConfig = ()
+        if not (GenerationConfig and isinstance(generation_config, GenerationConfig)):
+            raise NotImplementedError(f"generate(generation_config={generation_config!r}) is not implemented on the MI355X path: pass a "
+                                      "transformers.GenerationConfig or a dict of its fields")
+        d = generation_config.to_diff_dict()
+    return {k: v for k, v in d.items() if not k.startswith("_") and k != "transformers_version" and v is not None}
+
+
+# ------------------------------------------------------------------------------------------------ what a generate() resolved to
+class Sampling(NamedTuple):
+    """do_sample=True: HF's Temperature → TopK → TopP warpers and the key of the device's counter-based generator."""
+    temperature: float
+    top_k: int
+    top_p: float
+    seed: int
+
+
+class StepMode(NamedTuple):
+    """What selects the decode step's kernel sequence and output buffers (DecodeSession.head_and_select): run_steps keeps one captured graph
+    per value.  Penalty, EOS ids, warper settings, seed and the rules' contents are not part of it: the captured step reads them from device memory."""
+    sampling: bool = False           # the sampling kernel instead of the arg-max over the head's partials
+    keep_scores: bool = False        # every step's processed fp32 rows are filed in `scores`
+    keep_logits: bool = False        # ... and the rows before the warpers in `raw_scores`
+    rules: bool = False              # the ban-bitmap kernel runs and the head writes -inf where it says
+    token_logprobs: bool = False     # the LSE head + padt_greedy_step_lp, or the row kernel when the token is not the head's arg-max
+    top_k: int = 0                   # padt_topk_logprob_rows_f32 over the step's row: k candidates ...
+    patches: bool = False            # ... and / or the sample's own patch columns
+    processors: bool = False         # the caller's logits_processor rewrites the rows (hooked loop: never captured)
+    reference: bool = False          # precision="reference": reference.ReferencePath.step instead of step_kernels
+
+
+@dataclass(frozen=True)
+class GenOptions:
+    """What one generate() resolved to (resolve_options).  Equality is decode-group compatibility: batches share a session only when equal."""
+    repetition_penalty: float = 1.0
+    eos_ids: tuple = ()
+    sampling: Optional[Sampling] = None          # None: greedy
+    rules: Optional[tuple] = None                # the four pure bans as ops.gen_rules_key returns them; None: nothing banned
+    keep_scores: bool = False                    # output_scores, output_logits or a hooked loop: the processed rows of every step are kept
+    keep_logits: bool = False                    # output_logits under sampling only: there the scores are the warped rows, so the raw ones get a stash of their own
+    token_logprobs: bool = False
+    top_logprobs: int = 0                        # k; 0: off
+    patch_logprobs: bool = False
+
+    @property
+    def want_rows(self) -> bool:
+        """top_logprobs / output_patch_logprobs select from the whole processed row."""
+        return bool(self.top_logprobs or self.patch_logprobs)
+
+    @property
+    def write_back(self) -> bool:
+        """The sampling kernel overwrites its rows with the warped scores: whoever reads the row after it must see what was sampled from."""
+        return self.sampling is not None and bool(self.keep_scores or self.token_logprobs or self.want_rows)
+
+    @property
+    def reads_prompt(self) -> bool:
+        """A ban or the repetition penalty is active: the built-in processors see the caller's full (B, L) input_ids."""
+        return self.repetition_penalty != 1.0 or self.rules is not None
+
+    def gen_cfg(self) -> torch.Tensor:
+        """The generation-config slots the head / selection kernels read (ops.gen_cfg_tensor), on the host."""
+        s = self.sampling or Sampling(1.0, 0, 1.0, 0)
+        return ops.gen_cfg_tensor(self.repetition_penalty, self.eos_ids, "cpu", do_sample=self.sampling is not None, seed=s.seed,
+                                  temperature=s.temperature, top_k=s.top_k, top_p=s.top_p, write_back=self.write_back)
+
+    def step_mode(self, processors: bool = False, reference: bool = False) -> StepMode:
+        return StepMode(sampling=self.sampling is not None, keep_scores=self.keep_scores, keep_logits=self.keep_logits, rules=self.rules is not None,
+                        token_logprobs=self.token_logprobs, top_k=self.top_logprobs, patches=self.patch_logprobs, processors=bool(processors),
+                        reference=bool(reference))
+
+    def generate_kwargs(self) -> dict:
+        """Explicit generate() arguments that resolve back to these options under ANY generation_config: what is off is spelled as off (0, [],
+        False), never as None, so that a checkpoint default cannot switch it back on; the 1-token bad words travel as suppress_tokens.
+        output_scores / output_logits are the caller's to pass: they also decide what is returned, which the options do not record."""
+        n_gram, static, begin, words = self.rules or (0, (), (), ())
+        kw = dict(do_sample=False) if self.sampling is None else dict(do_sample=True, **self.sampling._asdict())
+        return dict(kw, repetition_penalty=self.repetition_penalty, eos_token_id=list(self.eos_ids), no_repeat_ngram_size=n_gram,
+                    bad_words_ids=[list(wd) for wd in words], suppress_tokens=list(static), begin_suppress_tokens=list(begin),
+                    output_token_logprobs=self.token_logprobs, top_logprobs=self.top_logprobs, output_patch_logprobs=self.patch_logprobs)
+
+
+def resolve_options(gc, config_eos_id, vocab_size, do_sample=None, repetition_penalty=None, eos_token_id=None, temperature=None, top_k=None,
+                    top_p=None, seed=None, keep_scores=False, keep_logits=False, no_repeat_ngram_size=None, bad_words_ids=None,
+                    suppress_tokens=None, begin_suppress_tokens=None, output_token_logprobs=False, top_logprobs=None,
+                    output_patch_logprobs=False) -> GenOptions:
+    """generate_launch's arguments (same names) → GenOptions.  gc: the model's generation_config, whose field applies where the argument is
+    None (HF: padt.py:436); config_eos_id / vocab_size: the model config's.  Pure but for the seed, which is drawn from torch's global
+    generator when sampling without one (so torch.manual_seed makes runs repeatable) — and only then."""
+    top_logprobs = check_top_logprobs(top_logprobs)
+    dflt = lambda name, v: getattr(gc, name, None) if v is None else v
+    do_sample = dflt("do_sample", do_sample)
+    temperature, top_k, top_p = float(dflt("temperature", temperature)), int(dflt("top_k", top_k)), float(dflt("top_p", top_p))
+    if do_sample and top_k == 1:
+        do_sample = False                                         # sampling among the single best token IS the arg-max
+    samp = None
+    if do_sample:
+        if temperature <= 0:
+            raise ValueError("temperature must be strictly positive (HF TemperatureLogitsWarper)")
+        if top_p < 1.0 and not (0 < top_k <= 1024):
+            raise NotImplementedError("top_p < 1 is supported together with 0 < top_k <= 1024 (the nucleus is taken over the top-k survivors)")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        samp = Sampling(temperature, top_k, top_p, int(seed))
+    eos = dflt("eos_token_id", eos_token_id)
+    eos = (int(eos),) if isinstance(eos, int) else tuple(int(e) for e in eos)
+    if config_eos_id not in eos or len(eos) > 4:
+        raise NotImplementedError("eos_token_id must contain config.eos_token_id and hold at most 4 ids")
+    # the four pure bans in canonical form (None: nothing banned — then no kernel is added and the head gets no bitmap)
+    rules = ops.gen_rules_key(dflt("no_repeat_ngram_size", no_repeat_ngram_size), dflt("bad_words_ids", bad_words_ids),
+                              dflt("suppress_tokens", suppress_tokens), dflt("begin_suppress_tokens", begin_suppress_tokens),
+                              eos_ids=eos, vocab_size=vocab_size)
+    if keep_logits and rules is not None and samp is None:
+        raise NotImplementedError("generate(output_logits=True) with a logits processor active (no_repeat_ngram_size, bad_words_ids, suppress_tokens "
+                                  "or begin_suppress_tokens): only the processed rows are kept on this path — ask for output_scores=True")
+    return GenOptions(repetition_penalty=float(dflt("repetition_penalty", repetition_penalty)), eos_ids=eos, sampling=samp, rules=rules,
+                      keep_scores=bool(keep_scores), keep_logits=bool(keep_logits) and samp is not None, token_logprobs=bool(output_token_logprobs),
+                      top_logprobs=top_logprobs, patch_logprobs=bool(output_patch_logprobs))

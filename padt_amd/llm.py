@@ -19,6 +19,7 @@ import torch
 
 from . import ops
 from .config import PaDTConfig
+from .generation import GenOptions, StepMode
 
 I32 = torch.int32
 
@@ -343,7 +344,6 @@ class DecodeSession:
         # HF's pure-ban processors (no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens): the packed rule table, each
         # row's prompt ids as the caller passed them (padding included: what HF's processors see) and the per-step ban bitmap ops.gen_rules
         # rebuilds from them and `tokens` — all device memory at fixed addresses, read by the captured step
-        self.rules_on = False
         self.rules = z(ops.GEN_RULES_INTS, dt=I32)
         self.hist = z(B, s_max, dt=I32)
         self.hist_len = z(B, dt=I32)
@@ -354,24 +354,20 @@ class DecodeSession:
         # generate_collect's ONE read-back per chunk (ops.collect_summary): [err, any unfinished, nf rows, nf batches, first EOS step per row]
         self.summary = z(2 + 3 * B, dt=I32)
         self.summary_host = torch.zeros(2 + 3 * B, dtype=I32).pin_memory() if torch.device(device).type == "cuda" else torch.zeros(2 + 3 * B, dtype=I32)
-        self.keep_scores = False         # output_scores=True: every step's masked fp32 logit rows are filed in `scores` [t_max][B][W]
-        self.scores = None
-        self.keep_logits = False         # output_logits=True under sampling: the rows before the warpers, in `raw_scores` [t_max][B][W]
-        self.raw_scores = None
-        self.keep_lp = False             # output_token_logprobs=True: log p of every selected token in `logprobs` [B][t_max], no logit row kept
-        self.part_sum = None             # ... from the head's per-block Σ exp(logit - block max) [nblk][B] (fused path), allocated on first use
-        self.logprobs = None
-        self.top_k = 0                   # top_logprobs=k: the k best columns of every step's score row in `top_idx` / `top_val` [B][t_max][k] (per k, on first use)
-        self.top_idx = self.top_val = None
+        # what this generate's step launches and keeps (generation.StepMode, set by begin()); the buffers below are allocated on first use
+        self.mode = StepMode()
+        self.scores = None               # mode.keep_scores (output_scores=True): every step's masked fp32 logit rows [t_max][B][W]
+        self.raw_scores = None           # mode.keep_logits (output_logits=True under sampling): the rows before the warpers [t_max][B][W]
+        self.part_sum = None             # mode.token_logprobs: the head's per-block Σ exp(logit - block max) [nblk][B] (fused path) ...
+        self.logprobs = None             # ... and log p of every selected token [B][t_max], no logit row kept
+        self.top_idx = self.top_val = None   # mode.top_k (top_logprobs=k): the k best columns of every step's score row [B][t_max][k] ...
         self.top_flat = None             # ... views of ONE flat pair sized for k = 32
-        self.keep_patch = False          # output_patch_logprobs=True: every sample's own patch columns in `patch_lp` [B][t_max][p_cap]
-        self.p_cap = 0
+        self.p_cap = 0                   # mode.patches (output_patch_logprobs=True): every sample's own patch columns in `patch_lp` [B][t_max][p_cap]
         self.patch_lp = None
         self.topk_ws = None              # padt_topk_logprob_rows_f32's chunk workspace, sized for k = 32
         self.rope_cs = z(B, hd // 2, 2, dt=torch.float32)
         self.n_qkv = (cfg.num_attention_heads + 2 * Hkv) * hd
-        self.graphs = {}                 # captured decode-step graph per mode (greedy / sampling: different kernel sequences)
-        self.do_sample = False
+        self.graphs = {}                 # captured decode-step graph per mode (different kernel sequences and output buffers)
         self.logits = None               # fp32 [B][V + np_max] rows for the sampling kernel, allocated on first use
         self.np_cur = np_max
         self.step_fn = None              # precision="reference": the eager split-precision decode step (reference.ReferencePath.step) instead of step_kernels
@@ -414,111 +410,105 @@ class DecodeSession:
         ops.check_finite(self.hn, self.nf, rows_per_flag=1, rows=B)      # sticky per-row flag, read once per generate (modeling.generate_collect)
         self.head_and_select(self.hn, advance=True)
 
-    def want_logprobs(self, on: bool):
-        """Start of a generate: output_token_logprobs on / off; the buffers are allocated on first use and zeroed for every generate that asks."""
-        self.keep_lp = bool(on)
-        if not on:
-            return
-        if self.logprobs is None:
-            dev = self.part_val.device
-            self.part_sum = torch.zeros(self.nblk * self.B, device=dev, dtype=torch.float32)
-            self.logprobs = torch.zeros((self.B, self.t_max), device=dev, dtype=torch.float32)
-        else:
-            self.part_sum.zero_()
-            self.logprobs.zero_()
-
-    GKEY_PATCH = 7                       # position of keep_patch in run_steps' graph key (want_top drops the graphs captured over an outgrown patch buffer)
-
-    def want_top(self, k: int, patches: bool, p_cap: int = 0):
-        """Start of a generate: top_logprobs=k (0: off) and output_patch_logprobs (p_cap: the largest patch count of one sample).  The
-        buffers are allocated on first use — ONE flat (ids, values) pair sized for k = 32, of which a generate uses the leading B * t_max * k
-        elements as [B][t_max][k], so a captured step keeps its addresses and memory does not grow with the k values asked; the patch buffer
-        grows, and the graphs captured over the smaller one go with it — and set to the finished-row values (-1 / -inf) for every generate that asks."""
-        self.top_k, self.keep_patch = int(k), bool(patches)
-        self.top_idx = self.top_val = None
-        if not (self.top_k or self.keep_patch):
-            return
+    def begin(self, opts: GenOptions, p_max: int = 0, processors: bool = False, step_fn=None):
+        """Start of a generate with these options (p_max: the largest patch count of one sample; processors: the caller's logits_processor runs in
+        the hooked loop; step_fn: precision="reference"'s step): the gen_cfg slots and the rule table the captured step reads, the step mode,
+        and the log-prob buffers, allocated on first use and set to their finished-row values (0 / -1 / -inf) for every generate that asks.
+        top_logprobs uses the leading B * t_max * k elements of ONE flat (ids, values) pair sized for k = 32 as [B][t_max][k], so a captured
+        step keeps its addresses and memory does not grow with the k values asked; the patch buffer grows, and the graphs captured over the
+        smaller one go with it."""
         dev = self.part_val.device
-        if self.topk_ws is None:
+        self.gen_cfg.copy_(opts.gen_cfg().to(dev, non_blocking=True))
+        self.mode, self.step_fn, self.hooks = opts.step_mode(processors, step_fn is not None), step_fn, None
+        if opts.token_logprobs:
+            if self.logprobs is None:
+                self.part_sum = torch.zeros(self.nblk * self.B, device=dev, dtype=torch.float32)
+                self.logprobs = torch.zeros((self.B, self.t_max), device=dev, dtype=torch.float32)
+            else:
+                self.part_sum.zero_()
+                self.logprobs.zero_()
+        self.top_idx = self.top_val = None
+        if opts.want_rows and self.topk_ws is None:
             nbytes = ops.topk_rows_workspace(self.cfg.vocab_size + self.np_max, ops.TOPK_ROWS_MAX_K, self.B)
             self.topk_ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        if self.top_k:
+        if opts.top_logprobs:
             if self.top_flat is None:
                 n = self.B * self.t_max * ops.TOPK_ROWS_MAX_K
                 self.top_flat = (torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=torch.float32))
-            n = self.B * self.t_max * self.top_k
-            self.top_idx, self.top_val = (f[:n].view(self.B, self.t_max, self.top_k) for f in self.top_flat)
+            n = self.B * self.t_max * opts.top_logprobs
+            self.top_idx, self.top_val = (f[:n].view(self.B, self.t_max, opts.top_logprobs) for f in self.top_flat)
             self.top_idx.fill_(-1)
             self.top_val.fill_(float("-inf"))
-        if self.keep_patch:
-            if self.patch_lp is None or self.p_cap < p_cap:
-                self.graphs = {g: v for g, v in self.graphs.items() if not g[self.GKEY_PATCH]}      # their launches hold the old buffer's address
-                self.p_cap = max(int(p_cap), 1)
+        if opts.patch_logprobs:
+            if self.patch_lp is None or self.p_cap < p_max:
+                self.graphs = {m: g for m, g in self.graphs.items() if not m.patches}      # their launches hold the old buffer's address
+                self.p_cap = max(int(p_max), 1)
                 self.patch_lp = torch.empty((self.B, self.t_max, self.p_cap), device=dev, dtype=torch.float32)
             self.patch_lp.fill_(float("-inf"))
+        if opts.rules is not None:
+            self.rules.copy_(ops.gen_rules_tensor(key=opts.rules).to(dev, non_blocking=True))
+            self.hist_len.zero_()                                # rows no batch of the group fills: an empty prompt
 
     def head_and_select(self, hn, advance: bool):
         cfg, W = self.cfg, self.W
         hp = W.get("llm.head.wp")
         lg = None
-        hk = self.hooks
+        hk, m = self.hooks, self.mode
         # token log-probs: from the head's partials (the LSE head + padt_greedy_step_lp, no logit row) when the token is their arg-max; from
         # the fp32 row the selection kernel read when it is not (sampling, caller processors rewrote the row)
-        lp_rows = self.keep_lp and (self.do_sample or (hk is not None and bool(hk["processors"])))
-        psum = self.part_sum if (self.keep_lp and not lp_rows) else None
-        top_on = bool(self.top_k or self.keep_patch)          # top_logprobs / output_patch_logprobs read the whole processed row too
-        if self.do_sample or self.keep_scores or top_on:     # the sampling kernel / output_scores need the whole masked / penalised logit row
+        lp_rows = m.token_logprobs and (m.sampling or m.processors)
+        psum, lp_out = (self.part_sum, self.logprobs) if (m.token_logprobs and not lp_rows) else (None, None)
+        top_on = bool(m.top_k or m.patches)                  # top_logprobs / output_patch_logprobs read the whole processed row too
+        if m.sampling or m.keep_scores or top_on:            # the sampling kernel / output_scores need the whole masked / penalised logit row
             if self.logits is None:
                 self.logits = torch.empty((self.B, (cfg.vocab_size + self.np_max + 3) // 4 * 4), device=hn.device, dtype=torch.float32)
             lg = self.logits
         ban = None
-        if self.rules_on:                                    # this step's ban bitmap from the rows' histories; the head then writes -inf there
+        if m.rules:                                          # this step's ban bitmap from the rows' histories; the head then writes -inf there
             ban = ops.gen_rules(self.rules, self.hist, self.hist_len, self.tokens, self.step, self.ban, cfg.vocab_size + self.np_max)
         if hp is not None:                                   # packed table + packed hidden rows: 1 KiB contiguous wave loads
             ops.pack_rows(hn, self.hn_pk, self.B, to_packed=True)
             ops.vrt_head(self.hn_pk, W["llm.head"], self.proto, self.vrt_off, self.part_val, self.part_idx, cfg.eos_token_id,
                          mode_table=self.mode_table, step=self.step, table_packed=hp, rows=self.B, gen_cfg=self.gen_cfg,
-                         seen=self.seen, logits=lg, ban=ban, **({} if psum is None else {"part_sum": psum}))
+                         seen=self.seen, logits=lg, ban=ban, part_sum=psum)
         else:
             ops.vrt_head(hn, W["llm.head"], self.proto, self.vrt_off, self.part_val, self.part_idx, cfg.eos_token_id,
-                         mode_table=self.mode_table, step=self.step, gen_cfg=self.gen_cfg, seen=self.seen, logits=lg, ban=ban,
-                         **({} if psum is None else {"part_sum": psum}))
-        if hk is not None and hk["processors"]:
+                         mode_table=self.mode_table, step=self.step, gen_cfg=self.gen_cfg, seen=self.seen, logits=lg, ban=ban, part_sum=psum)
+        if m.processors:
             # padt.py:717 `next_token_scores = logits_processor(input_ids, next_token_logits)` with the CALLER's processors: they see the rows the head
             # wrote (logit mask + the built-in processors applied) and the sequences so far, and what they return is what is scored / selected / kept
             view = lg[: hk["B"], : hk["table_rows"]]
             new = _call_hooks(hk["processors"], hk["sequences"](), view, chain=True)
             if new is not view:
                 view.copy_(new.to(torch.float32))
-        if self.keep_scores and self.scores is None:
+        if m.keep_scores and self.scores is None:
             self.scores = torch.zeros((self.t_max,) + tuple(self.logits.shape), device=hn.device, dtype=torch.float32)
-        if self.keep_logits:                                 # padt.py:721-722: raw_logits += (next_token_logits,) — differ from the scores under sampling
+        if m.keep_logits:                                    # padt.py:721-722: raw_logits += (next_token_logits,) — differ from the scores under sampling
             if self.raw_scores is None:
                 self.raw_scores = torch.zeros((self.t_max,) + tuple(self.logits.shape), device=hn.device, dtype=torch.float32)
             ops.stash_step_f32(lg, self.step, self.raw_scores)
-        if self.keep_scores and not self.do_sample:          # padt.py:719-720: scores += (next_token_scores,) — filed under the device step counter
+        if m.keep_scores and not m.sampling:                 # padt.py:719-720: scores += (next_token_scores,) — filed under the device step counter
             ops.stash_step_f32(lg, self.step, self.scores)
         nblk = self.nblk
-        if self.do_sample:                                   # padt.py:740-743: multinomial over softmax of the warped scores
-            # with keep_scores (or keep_lp) the session's gen_cfg has write_back set: lg then holds the warped rows (l / T, -inf outside top-k / top-p),
+        if m.sampling:                                       # padt.py:740-743: multinomial over softmax of the warped scores
+            # with keep_scores (or token_logprobs) the session's gen_cfg has write_back set: lg then holds the warped rows (l / T, -inf outside top-k / top-p),
             # HF's next_token_scores — the warpers are part of its logits_processor (padt.py:717)
             ops.sample_token(lg, cfg.vocab_size + self.np_max, self.gen_cfg, self.step, self.part_val, self.part_idx, self.B)
-            if self.keep_scores:
+            if m.keep_scores:
                 ops.stash_step_f32(lg, self.step, self.scores)
             nblk = 1
-        elif hk is not None and hk["processors"]:            # the head's fused arg-max partials describe the rows BEFORE the caller's processors
+        elif m.processors:                                   # the head's fused arg-max partials describe the rows BEFORE the caller's processors
             ops.argmax_rows(lg, cfg.vocab_size + self.np_max, self.part_val, self.part_idx, self.B)
             nblk = 1
         if lp_rows:                                          # before greedy_step clears `unfinished` and bumps the step counter
             ops.token_logprob_rows(lg, cfg.vocab_size + self.np_max, self.part_idx, self.unfinished, self.step, self.logprobs, self.B)
         if top_on:                                           # the row as selected from (warped under sampling: write_back), `unfinished` as on entry
             ops.topk_logprob_rows(lg, cfg.vocab_size + self.np_max, self.unfinished, self.step, self.topk_ws, self.B, top_idx=self.top_idx,
-                                  top_val=self.top_val, vrt_off=self.vrt_off if self.keep_patch else None, vocab=cfg.vocab_size,
-                                  patch_lp=self.patch_lp if self.keep_patch else None)
+                                  top_val=self.top_val, vrt_off=self.vrt_off if m.patches else None, vocab=cfg.vocab_size,
+                                  patch_lp=self.patch_lp if m.patches else None)
         ops.greedy_step(self.part_val, self.part_idx, nblk, hn, self.hidden_buf, self.unfinished, self.tokens,
                         self.cur_tok, self.step, self.slot, self.lens, self.pos3, cfg.eos_token_id, cfg.pad_token_id,
-                        advance=advance, gen_cfg=self.gen_cfg, seen=self.seen,
-                        **({} if psum is None else {"part_sum": psum, "logprobs": self.logprobs}))
+                        advance=advance, gen_cfg=self.gen_cfg, seen=self.seen, part_sum=psum, logprobs=lp_out)
         if hk is not None:
             hk["t"] += 1
             if hk["criteria"]:
@@ -538,8 +528,7 @@ class DecodeSession:
             for _ in range(n):
                 one_step()
             return
-        gkey = (self.do_sample, self.keep_scores, self.keep_logits, self.step_fn is not None, self.rules_on, self.keep_lp, self.top_k,
-                self.keep_patch)   # keep_patch sits at GKEY_PATCH; different kernel sequences (and output buffers) → one captured graph per mode
+        gkey = self.mode                                     # different kernel sequences (and output buffers) → one captured graph per mode
         if gkey not in self.graphs:
             one_step()                                       # real step; also pays every one-time kernel attribute call
             n -= 1

@@ -11,7 +11,6 @@ There is no HuggingFace modeling code and no PyTorch compute on this path: the m
 libpadt_hip.so (see vision.py / llm.py / decoder.py) and fail loudly if that library is missing.
 """
 import json
-import numbers
 import os
 from types import SimpleNamespace
 from typing import Optional, Sequence
@@ -21,6 +20,8 @@ import torch
 from . import _lib, ops
 from .config import PaDTConfig
 from .decoder import PaDTDecoder
+from .generation import (_GENERATE_CONFIG_NAMED, _GENERATE_CONFIG_OWN, check_generate_kwargs, check_top_logprobs,  # noqa: F401
+                         generation_config_fields, resolve_options)
 from .llm import MODE, LanguageModel, check_shared_destinations, plan_prompt, plan_prompt_shared
 from .vision import VisionEncoder
 from .weights import Fp16RangeError, load_checkpoint_state_dict, prepare_weights, synthetic_state_dict
@@ -84,99 +85,6 @@ class CustomGenerateDecoderOnlyOutput(dict):
             return self[k]
         except KeyError as e:
             raise AttributeError(k) from e
-
-
-# ------------------------------------------------------------------------------------------------ generate() argument policy
-# HF / reference generate() arguments that cannot change what this path returns: accepted when they hold one of the listed values
-# (None = any value), otherwise NotImplementedError.
-_GENERATE_IGNORED = {
-    "attn_implementation": None, "tokenizer": None, "assistant_tokenizer": None, "cache_implementation": None, "logits_to_keep": None,
-    "generation_config": (None,), "output_attentions": (False, None),
-    # GenerationConfig fields callers pass routinely and the reference's generate() accepts without effect on this path:
-    "bos_token_id": None, "decoder_start_token_id": None, "return_legacy_cache": None,
-    "num_beams": (1, None), "num_beam_groups": (1, None), "num_return_sequences": (1, None), "penalty_alpha": (None,), "min_new_tokens": (0, None),
-    "min_length": (0, None), "force_words_ids": (None,), "token_healing": (False, None),
-    "length_penalty": (1.0, None), "early_stopping": (False, None), "typical_p": (1.0, None), "min_p": (None,), "epsilon_cutoff": (0.0, None),
-    "eta_cutoff": (0.0, None), "encoder_repetition_penalty": (1.0, None), "guidance_scale": (None, 1.0), "renormalize_logits": (False, None),
-}
-# arguments the reference honours (padt.py:418-424,445,511-533,570-580,719-737) and this path does not implement
-# ... and, through generate()'s NAMED parameters only, the four pure-ban processors: as a stray keyword of check_generate_kwargs they stay refused
-_GENERATE_NAMED_ONLY = ("no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens")
-_GENERATE_REJECTED = ("inputs", "prefix_allowed_tokens_fn", "assistant_model", "streamer",
-                      "negative_prompt_ids", "negative_prompt_attention_mask", "pixel_values_videos", "video_grid_thw", "second_per_grid_ts",
-                      "inputs_embeds", "past_key_values", "position_ids", "cache_position", "rope_deltas", "stop_strings", "max_time",
-                      "sequence_bias", "forced_bos_token_id", "forced_eos_token_id",
-                      "exponential_decay_length_penalty", "prompt_lookup_num_tokens", "dola_layers", "labels")
-
-
-def check_generate_kwargs(kwargs: dict, max_new_tokens, max_length, prompt_len) -> int:
-    """The drop-in surface's argument policy (see generate()): → the effective max_new_tokens.  Raises NotImplementedError naming an
-    argument the reference honours and this path does not, ValueError (HF's _validate_model_kwargs wording) for an unknown one."""
-    for k in list(kwargs):
-        v = kwargs[k]
-        if k in _GENERATE_REJECTED or k in _GENERATE_NAMED_ONLY:
-            if v is None:
-                continue                                              # the reference's own default
-            raise NotImplementedError(f"generate({k}=...) is not implemented on the MI355X path (the reference honours it, padt.py:414-580): "
-                                      "remove the argument or run the reference for this call")
-        if k in _GENERATE_IGNORED:
-            ok = _GENERATE_IGNORED[k]
-            if ok is None or any(v is o or (not isinstance(v, (torch.Tensor, list, tuple, dict)) and v == o) for o in ok):
-                continue
-            raise NotImplementedError(f"generate({k}={v!r}) is not implemented on the MI355X path (supported: {ok})")
-        raise ValueError(f"The following `model_kwargs` are not used by the model: ['{k}'] (note: typos in the generate arguments will also "
-                         "show up in this list)")
-    if max_new_tokens is None:
-        if max_length is not None:
-            if prompt_len is None or int(max_length) <= int(prompt_len):
-                raise ValueError(f"Input length of input_ids is {prompt_len}, but `max_length` is set to {max_length}. This can lead to unexpected "
-                                 "behavior. You should consider increasing `max_length` or, better yet, setting `max_new_tokens`.")
-            return int(max_length) - int(prompt_len)
-        return 1024
-    return int(max_new_tokens)
-
-
-TOP_LOGPROBS_MAX = ops.TOPK_ROWS_MAX_K
-
-
-def check_top_logprobs(top_logprobs) -> int:
-    """generate(top_logprobs=...) → k: None / 0 is off (0), 1 <= k <= 32 asks for the k best candidates of every step; a negative or
-    non-integer value raises ValueError, a larger one NotImplementedError naming the argument and the cap."""
-    if top_logprobs is None:
-        return 0
-    if isinstance(top_logprobs, bool) or not isinstance(top_logprobs, numbers.Integral) or int(top_logprobs) < 0:
-        raise ValueError(f"generate(top_logprobs={top_logprobs!r}): a non-negative integer (or None) is required")
-    if int(top_logprobs) > TOP_LOGPROBS_MAX:
-        raise NotImplementedError(f"generate(top_logprobs={int(top_logprobs)}): at most top_logprobs={TOP_LOGPROBS_MAX} candidates per step are "
-                                  "selected on the device — ask for output_scores=True and reduce the rows yourself beyond that")
-    return int(top_logprobs)
-
-
-# generate()'s named parameters a generation_config may carry: an explicit argument (not None) wins, as in HF (padt.py:436)
-_GENERATE_CONFIG_NAMED = ("max_new_tokens", "max_length", "do_sample", "repetition_penalty", "eos_token_id", "pad_token_id", "temperature", "top_k",
-                          "top_p", "no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens")
-# ... and those whose value is this path's own default either way (hidden states and the dict output are what its callers consume)
-_GENERATE_CONFIG_OWN = ("use_cache", "output_hidden_states", "return_dict_in_generate")
-
-
-def generation_config_fields(generation_config) -> dict:
-    """generate(generation_config=): the fields a ``transformers.GenerationConfig`` sets to something other than its default (to_diff_dict),
-    or the entries of a dict; bookkeeping entries (``transformers_version``, ``_from_model_config`` …) are dropped.  Anything else is not a
-    generation config: NotImplementedError naming the argument."""
-    if generation_config is None:
-        return {}
-    if isinstance(generation_config, dict):
-        d = dict(generation_config)
-    else:
-        try:
-            from transformers import GenerationConfig
-        except ImportError:                                           # no transformers: only dicts can be configs
-            GenerationConfig = ()
-        if not (GenerationConfig and isinstance(generation_config, GenerationConfig)):
-            raise NotImplementedError(f"generate(generation_config={generation_config!r}) is not implemented on the MI355X path: pass a "
-                                      "transformers.GenerationConfig or a dict of its fields")
-        d = generation_config.to_diff_dict()
-    return {k: v for k, v in d.items() if not k.startswith("_") and k != "transformers_version" and v is not None}
 
 
 class PaDTForConditionalGeneration:
@@ -480,52 +388,26 @@ class PaDTForConditionalGeneration:
         if image_index is not None and getattr(self, "precision", "default") == "reference":
             raise NotImplementedError("generate(image_index=...) is not implemented with precision='reference' (its prompt pass is its own: "
                                       "reference.ReferencePath.prefill): expand the inputs or use precision='default'")
-        # operands="auto" whose checkpoint keeps overflowing fp16: new decode groups start on the bf16 twin (a group stays with its owner)
+        # operands="auto" whose checkpoint keeps overflowing fp16: new decode groups start on the bf16 twin (a group stays with its owner).  The
+        # options resolve the same on either: the twin shares this model's generation_config and config
         owner = group["owner"] if group is not None else (self.fallback_model() if self.prefers_bf16 else self)
-        if owner is not self:
-            return owner.generate_launch(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, do_sample, schedule, sync_every,
-                                         use_graph, lane, decode_stream, group, n_slots, repetition_penalty, eos_token_id, temperature, top_k, top_p,
-                                         seed, vit_stream, inputs_ready, keep_scores, hooks, keep_logits, no_repeat_ngram_size, bad_words_ids,
-                                         suppress_tokens, begin_suppress_tokens, image_index, output_token_logprobs, top_logprobs,
-                                         output_patch_logprobs)
-        top_logprobs = check_top_logprobs(top_logprobs)
+        opts = resolve_options(self.generation_config, self.config.eos_token_id, self.config.vocab_size, do_sample=do_sample,
+                               repetition_penalty=repetition_penalty, eos_token_id=eos_token_id, temperature=temperature, top_k=top_k, top_p=top_p,
+                               seed=seed, keep_scores=keep_scores, keep_logits=keep_logits, no_repeat_ngram_size=no_repeat_ngram_size,
+                               bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
+                               output_token_logprobs=output_token_logprobs, top_logprobs=top_logprobs, output_patch_logprobs=output_patch_logprobs)
+        return owner._launch(opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, max_new_tokens=max_new_tokens,
+                             schedule=schedule, hooks=hooks, sync_every=sync_every, use_graph=use_graph, lane=lane, decode_stream=decode_stream,
+                             group=group, n_slots=n_slots, vit_stream=vit_stream, inputs_ready=inputs_ready)
+
+    def _launch(self, opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, *, max_new_tokens, schedule, hooks, sync_every,
+                use_graph, lane, decode_stream, group, n_slots, vit_stream, inputs_ready):
+        """generate_launch on the group's owner, with the call's options resolved (generation.GenOptions)."""
         self._batches_seen += 1
-        gc = self.generation_config
-        do_sample = gc.do_sample if do_sample is None else do_sample
-        repetition_penalty = gc.repetition_penalty if repetition_penalty is None else repetition_penalty
-        temperature = gc.temperature if temperature is None else float(temperature)
-        top_k = gc.top_k if top_k is None else int(top_k)
-        top_p = gc.top_p if top_p is None else float(top_p)
-        if do_sample and top_k == 1:
-            do_sample = False                                     # sampling among the single best token IS the arg-max
-        if do_sample:
-            if temperature <= 0:
-                raise ValueError("temperature must be strictly positive (HF TemperatureLogitsWarper)")
-            if top_p < 1.0 and not (0 < top_k <= 1024):
-                raise NotImplementedError("top_p < 1 is supported together with 0 < top_k <= 1024 (the nucleus is taken over the top-k survivors)")
-            if seed is None:
-                seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
         if pixel_values is None or image_grid_thw is None:
             raise ValueError("pixel_values and image_grid_thw are required (text-only input crashes in the reference too, "
                              "padt.py:292 with image_prototypes unbound)")
         cfg, dev = self.config, self.device
-        eos_list = list(gc.eos_token_id) if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
-        if cfg.eos_token_id not in eos_list or len(eos_list) > 4:
-            raise NotImplementedError("eos_token_id must contain config.eos_token_id and hold at most 4 ids")
-        samp = (float(temperature), int(top_k), float(top_p), int(seed)) if do_sample else None
-        # the four pure bans in canonical form (None: nothing banned — then no kernel is added and the head gets no bitmap)
-        dflt = lambda name, v: getattr(gc, name, None) if v is None else v
-        rules = ops.gen_rules_key(dflt("no_repeat_ngram_size", no_repeat_ngram_size), dflt("bad_words_ids", bad_words_ids),
-                                  dflt("suppress_tokens", suppress_tokens), dflt("begin_suppress_tokens", begin_suppress_tokens),
-                                  eos_ids=eos_list, vocab_size=cfg.vocab_size)
-        if keep_logits and rules is not None and samp is None:
-            raise NotImplementedError("generate(output_logits=True) with a logits processor active (no_repeat_ngram_size, bad_words_ids, suppress_tokens "
-                                      "or begin_suppress_tokens): only the processed rows are kept on this path — ask for output_scores=True")
-        # under sampling the scores are the warped rows (sample_token writes them back), so output_logits needs a stash of its own
-        # output_token_logprobs changes the step's kernels (LSE head / row kernel): part of the key, so batches that disagree never share a session
-        gen_key = (float(repetition_penalty), tuple(eos_list), samp, bool(keep_scores), bool(keep_logits) and samp is not None, rules,
-                   bool(output_token_logprobs), top_logprobs, bool(output_patch_logprobs))      # ... and so are top_logprobs / output_patch_logprobs
-        want_rows = bool(top_logprobs or output_patch_logprobs)    # the selection reads the row: under sampling it must be the warped one (write_back)
         grid = image_grid_thw.detach().cpu().long()
         B = input_ids.shape[0]
         T_max = int(max_new_tokens)
@@ -540,7 +422,7 @@ class PaDTForConditionalGeneration:
         n_proto = plan.vrt_off[-1]
         p_max = max(plan.vrt_off[i + 1] - plan.vrt_off[i] for i in range(B))      # output_patch_logprobs: the widest sample of this batch
         need_s = max(plan.lens) + T_max
-        if rules is not None:
+        if opts.rules is not None:
             need_s = max(need_s, plan.L_pad)                      # the session's history rows hold the padded prompt row
         if hooks is not None and (group is not None or n_slots != 1):
             raise NotImplementedError("logits_processor / stopping_criteria run on generate()'s own (un-merged) decode loop, not inside a merged decode group")
@@ -548,21 +430,9 @@ class PaDTForConditionalGeneration:
             sess = self.lm.session(B * n_slots, need_s, n_proto * n_slots, T_max, lane=lane)
             group = dict(sess=sess, subs=[], proto_rows=0, B=B, n_slots=n_slots, T_max=T_max, sync_every=sync_every,
                          use_graph=use_graph, decode_stream=decode_stream, done=0, launched=False, schedule=schedule,
-                         gen_key=gen_key, eos_list=eos_list, lane=lane, owner=self)
-            sess.gen_cfg.copy_(ops.gen_cfg_tensor(gen_key[0], gen_key[1], "cpu", do_sample=samp is not None, seed=samp[3] if samp else 0,
-                                                  temperature=samp[0] if samp else 1.0, top_k=samp[1] if samp else 0,
-                                                  top_p=samp[2] if samp else 1.0,
-                                                  write_back=samp is not None and bool(keep_scores or output_token_logprobs or want_rows)).to(dev, non_blocking=True))
-            sess.do_sample = samp is not None
-            sess.keep_scores = bool(keep_scores)
-            sess.keep_logits = gen_key[4]
-            sess.want_logprobs(gen_key[6])
-            sess.want_top(gen_key[7], gen_key[8], p_max)
-            sess.rules_on = rules is not None
-            if rules is not None:
-                sess.rules.copy_(ops.gen_rules_tensor(key=rules).to(dev, non_blocking=True))
-                sess.hist_len.zero_()                             # rows no batch of the group fills: an empty prompt
-            sess.hooks = None
+                         opts=opts, lane=lane, owner=self)
+            # reference precision: eager split-precision steps (+ fp32 hidden rows, below)
+            sess.begin(opts, p_max, processors=bool(hooks and hooks["processors"]), step_fn=self.ref.step if self.ref is not None else None)
             if hooks is not None:
                 ids_dev = input_ids.detach().to(dev).long().contiguous()
                 hk = dict(hooks, B=B, table_rows=cfg.vocab_size + n_proto, t=0)
@@ -570,7 +440,7 @@ class PaDTForConditionalGeneration:
                 hk["sequences"] = lambda hk=hk, s=sess: ops.assemble_sequences(ids_dev, s.tokens[:B], hk["t"], cfg.vocab_size, 0)
                 sess.hooks = hk
                 group["hooks"] = hooks
-            if gen_key[0] != 1.0:
+            if opts.repetition_penalty != 1.0:
                 sess.seen.zero_()
             # neutral state for every row; the batches overwrite their own rows (unused rows stay finished / empty)
             st = torch.zeros(T_max + 1, dtype=torch.int32)
@@ -586,15 +456,13 @@ class PaDTForConditionalGeneration:
             sess.pos3.zero_()
             sess.cur_tok.fill_(cfg.pad_token_id)
             sess.vrt_off.zero_()
-            if self.ref is not None:                              # reference precision: eager split-precision steps + fp32 hidden rows
-                sess.step_fn = self.ref.step
-                if sess.hid32 is None or sess.hid32.shape[0] < T_max:
-                    sess.hid32 = torch.zeros((sess.t_max, sess.B, cfg.hidden_size), device=dev, dtype=torch.float32)
+            if self.ref is not None and (sess.hid32 is None or sess.hid32.shape[0] < T_max):
+                sess.hid32 = torch.zeros((sess.t_max, sess.B, cfg.hidden_size), device=dev, dtype=torch.float32)
         else:
             sess = group["sess"]
             if (group["launched"] or k >= group["n_slots"] or B != group["B"] or T_max != group["T_max"]
-                    or schedule != group["schedule"] or gen_key != group["gen_key"] or sess.s_max < need_s
-                    or sess.np_max < proto_row0 + n_proto or (gen_key[8] and sess.p_cap < p_max)):
+                    or schedule != group["schedule"] or opts != group["opts"] or sess.s_max < need_s
+                    or sess.np_max < proto_row0 + n_proto or (opts.patch_logprobs and sess.p_cap < p_max)):
                 return None
         if sh is not None:
             check_shared_destinations(sh, sess.B, sess.s_max)
@@ -643,15 +511,15 @@ class PaDTForConditionalGeneration:
         sess.lens[rows].copy_((lens_t + 1).to(dev, non_blocking=True))  # keys visible to the next token
         sess.pos3[:, rows].copy_(torch.tensor([plan.next_pos] * 3, dtype=torch.int32).to(dev, non_blocking=True))
         self.rope_deltas = plan.rope_deltas
-        if gen_key[0] != 1.0 or rules is not None:
+        if opts.reads_prompt:
             # HF's logits processors see the caller's full (B, L) input_ids, padding included
             ids_full = input_ids.detach().to(dev).long()
             if proto_row0:
                 ids_full = torch.where(ids_full >= cfg.vocab_size, ids_full + proto_row0, ids_full)
-        if gen_key[0] != 1.0:
+        if opts.repetition_penalty != 1.0:
             rws = (torch.arange(B, device=dev, dtype=torch.int32) + row0)[:, None].expand(B, ids_full.shape[1]).contiguous()
             ops.seen_init(ids_full.reshape(-1).contiguous(), rws.reshape(-1), sess.seen)
-        if rules is not None:
+        if opts.rules is not None:
             sess.hist[rows, : plan.L_pad].copy_(ids_full)         # int64 → int32 (ids are table rows)
             sess.hist_len[rows].fill_(plan.L_pad)
 
@@ -717,7 +585,7 @@ class PaDTForConditionalGeneration:
             return group["owner"].generate_collect(group, output_hidden_states, return_dict_in_generate, all_batches, output_scores, output_logits)
         cfg, dev = self.config, self.device
         self.launch_decode(group)
-        sess, T_max = group["sess"], group["T_max"]
+        sess, T_max, opts = group["sess"], group["T_max"], group["opts"]
         n_rows, n_sub = sess.B, len(group["subs"])
 
         def summary(done):
@@ -741,7 +609,7 @@ class PaDTForConditionalGeneration:
         for k_sub, sub in enumerate(group["subs"]):
             plan, row0, B = sub["plan"], sub["row0"], group["B"]
             if nf_batch[k_sub] != 0 or any(nf_rows[row0: row0 + B]):
-                outs.append(self._non_finite_batch(group, sub, output_hidden_states, return_dict_in_generate))
+                outs.append(self._non_finite_batch(group, sub, output_hidden_states, return_dict_in_generate, output_scores, output_logits))
                 continue
             # the reference stops right after the step in which the last sequence finished (padt.py:756-757); any id of the EOS list finishes a row
             fe = first_eos[row0: row0 + B]
@@ -761,19 +629,19 @@ class PaDTForConditionalGeneration:
                     return tuple(rows_t[t, :, :table_rows].clone() for t in range(n_steps))
                 return tuple(torch.cat([rows_t[t, :, :V], rows_t[t, :, V + p0: V + p0 + sub["n_proto"]]], dim=1) for t in range(n_steps))
             scores = per_step(sess.scores) if output_scores or output_logits else None
-            logits = (per_step(sess.raw_scores) if sess.keep_logits else scores) if output_logits else None
+            logits = (per_step(sess.raw_scores) if opts.keep_logits else scores) if output_logits else None
             top_ids = top_lp = patch_lp = None
-            if group["gen_key"][7]:                               # session columns → this batch's own VRT numbering, as assemble_sequences does
+            if opts.top_logprobs:                                 # session columns → this batch's own VRT numbering, as assemble_sequences does
                 top_ids = sess.top_idx[row0: row0 + B, :n_steps].to(torch.int64)
                 if sub["proto_row0"]:
                     top_ids = torch.where(top_ids >= cfg.vocab_size, top_ids - sub["proto_row0"], top_ids)
                 top_lp = sess.top_val[row0: row0 + B, :n_steps].clone()
-            if group["gen_key"][8]:
+            if opts.patch_logprobs:
                 patch_lp = sess.patch_lp[row0: row0 + B, :n_steps, :sub["p_max"]].clone()
             out = CustomGenerateDecoderOnlyOutput(
                 sequences=sequences, scores=scores if output_scores else None, logits=logits, attentions=None,
                 hidden_states=hidden if output_hidden_states else None, past_key_values=sess,
-                token_logprobs=sess.logprobs[row0: row0 + B, :n_steps].clone() if group["gen_key"][6] else None,
+                token_logprobs=sess.logprobs[row0: row0 + B, :n_steps].clone() if opts.token_logprobs else None,
                 top_token_ids=top_ids, top_logprobs=top_lp, patch_logprobs=patch_lp,
                 past_image_embeds=sub["proto"].clone(),
                 past_logit_mask=ops.logit_mask(sess.vrt_off[row0: row0 + B + 1], cfg.vocab_size, table_rows, sub["proto_row0"], B),
@@ -781,7 +649,7 @@ class PaDTForConditionalGeneration:
             outs.append(out if return_dict_in_generate else sequences)
         return outs if all_batches else outs[0]
 
-    def _non_finite_batch(self, group, sub, output_hidden_states, return_dict_in_generate):
+    def _non_finite_batch(self, group, sub, output_hidden_states, return_dict_in_generate, output_scores, output_logits):
         """A batch whose range guard fired: inf / NaN reached its ViT output, prototypes or hidden rows.  With fp16 operands that is an
         overflow of an un-normalised 16-bit tensor (65504); operands="auto" answers it with the SAME batch on the bf16 instantiation."""
         what = ("a non-finite value reached the ViT output / prototypes / post-norm hidden rows of a batch (%s MFMA operands)"
@@ -801,22 +669,13 @@ class PaDTForConditionalGeneration:
             warnings.warn("padt_amd: %d of %d batches exceeded fp16's range — operands='auto' now starts every new decode group on the bf16 "
                           "instantiation" % (self.overflow_reruns, self._batches_seen), RuntimeWarning, stacklevel=3)
         am, pix, grid, image_index = sub["inputs"]
-        pen, eos, samp = group["gen_key"][:3]
-        n_gram, static, begin, words = group["gen_key"][5] or (0, (), (), ())
-        # the canonical rules, explicit (an empty list is "off", not "the default"): the 1-token bad words travel as suppress_tokens
-        kw_rules = dict(no_repeat_ngram_size=n_gram, bad_words_ids=[list(wd) for wd in words], suppress_tokens=list(static),
-                        begin_suppress_tokens=list(begin))
-        kw = dict(do_sample=False)
-        if samp is not None:
-            kw = dict(do_sample=True, temperature=samp[0], top_k=samp[1], top_p=samp[2], seed=samp[3])
+        # the group's options spelled as explicit arguments (an "off" is 0 / [], never the default), and what this collect was asked to return
+        kw = dict(group["opts"].generate_kwargs(), output_scores=output_scores, output_logits=output_logits)
         if group.get("hooks") is not None:
             kw.update(logits_processor=group["hooks"]["processors"], stopping_criteria=group["hooks"]["criteria"])
         return fb.generate(input_ids=sub["input_ids"], attention_mask=am, pixel_values=pix, image_grid_thw=grid, max_new_tokens=group["T_max"],
                            schedule=group["schedule"], sync_every=group["sync_every"], use_graph=group["use_graph"], lane=("fb", group["lane"]),
-                           repetition_penalty=pen, eos_token_id=list(eos), output_hidden_states=output_hidden_states,
-                           return_dict_in_generate=return_dict_in_generate, image_index=image_index,
-                           output_token_logprobs=bool(group["gen_key"][6]), top_logprobs=group["gen_key"][7],
-                           output_patch_logprobs=bool(group["gen_key"][8]), output_scores=bool(group["gen_key"][3]) and (group.get("hooks") is None or group["hooks"]["pass_scores"]), **kw_rules, **kw)
+                           output_hidden_states=output_hidden_states, return_dict_in_generate=return_dict_in_generate, image_index=image_index, **kw)
 
     # ------------------------------------------------------------------ vl_decode (padt.py:342-412)
     @torch.no_grad()

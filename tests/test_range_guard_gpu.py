@@ -254,6 +254,36 @@ def test_auto_stops_paying_twice_when_most_batches_overflow():
         assert torch.equal(o.sequences, ref.sequences) and torch.equal(o.hidden_states.last_layer_rows(), ref.hidden_states.last_layer_rows())
 
 
+@pytest.fixture(scope="module")
+def rerun_models():
+    """the weights whose layer-1 SwiGLU hidden exceeds fp16's range on every batch: an operands="auto" model, the bf16 model it must agree with,
+    and a two-image batch"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from padt_amd.modeling import PaDTForConditionalGeneration
+    cfg, w, U = _weights("llm_swiglu")
+    grid, pix, ids, am = U.synthetic_batch(cfg, [[1, 8, 8], [1, 10, 12]], n_pre=5, n_post=8, ragged=True, seed=41)
+    kw = dict(input_ids=ids.cuda(), attention_mask=am.cuda(), pixel_values=pix.cuda(), image_grid_thw=grid, max_new_tokens=4)
+    return (PaDTForConditionalGeneration(cfg, w, device="cuda", operands="auto"), PaDTForConditionalGeneration(cfg, w, device="cuda", operands="bf16"), kw)
+
+
+@pytest.mark.parametrize("gen", [dict(), dict(do_sample=True, seed=1234, top_k=20)], ids=["greedy", "sampling"])
+def test_the_rerun_on_the_bf16_twin_returns_the_logits_that_were_asked_for(rerun_models, gen):
+    """generate(output_logits=True) on a batch the range guard flags: the re-run is derived from the call's resolved options and from what the
+    caller asked generate_collect to return, so `.logits` comes back (it used to be None) and, under greedy decoding, no `.scores` nobody asked for."""
+    auto, bf, kw = rerun_models
+    before = auto.overflow_reruns
+    with pytest.warns(RuntimeWarning, match="re-run on the bf16"):
+        got = auto.generate(output_logits=True, **gen, **kw)
+    assert auto.overflow_reruns == before + 1 and not auto.prefers_bf16
+    ref = bf.generate(output_logits=True, **gen, **kw)
+    assert ref.logits is not None and len(ref.logits) == ref.sequences.shape[1] - kw["input_ids"].shape[1] > 0
+    assert got.logits is not None and len(got.logits) == len(ref.logits)
+    assert all(torch.equal(a, b) for a, b in zip(got.logits, ref.logits))
+    assert torch.equal(got.sequences, ref.sequences)
+    assert got.scores is None and ref.scores is None
+
+
 def test_checkpoint_value_outside_fp16_is_caught_at_load():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")

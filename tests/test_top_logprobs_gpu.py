@@ -459,6 +459,47 @@ def test_generate_launch_collect_all_batches_carry_the_fields(setup):
     assert torch.equal(keep[0], alone.top_logprobs) and torch.equal(keep[1], alone.top_token_ids) and torch.equal(keep[2], alone.patch_logprobs)
 
 
+def same_output(a, b):
+    """every returned field of two generate() results is bit-equal (the session itself aside)"""
+    assert a.keys() == b.keys()
+    for name in a:
+        x, y = a[name], b[name]
+        if name == "past_key_values":
+            continue
+        if name == "hidden_states":
+            x, y = x.last_layer_rows(), y.last_layer_rows()
+        if isinstance(x, (tuple, list)):
+            assert len(x) == len(y) and all(torch.equal(p, q) for p, q in zip(x, y)), name
+        else:
+            assert (x is None and y is None) or torch.equal(x, y), name
+
+
+def test_mode_changes_on_one_lane_replay_what_the_eager_steps_compute(setup):
+    """One lane's session goes through plain → top_logprobs → output_patch_logprobs on a small image → on a larger one (the patch buffer grows:
+    the graphs captured over the outgrown one must go) → the small one again → plain, with captured steps; every result equals the same call
+    with eager steps on another lane.  The first call sizes the session for the larger image, so all six share ONE session and its graphs."""
+    cfg, U, model, _ = setup
+    def batch(g, seed):
+        grid, pix, ids, am = U.synthetic_batch(cfg, [g], n_pre=6, n_post=9, seed=seed)
+        return dict(input_ids=ids.cuda(), attention_mask=am.cuda(), pixel_values=pix.cuda(), image_grid_thw=grid)
+    small, large = batch([1, 4, 4], 71), batch([1, 8, 8], 72)
+    calls = [(large, dict()), (large, dict(top_logprobs=3)), (small, dict(output_patch_logprobs=True)), (large, dict(output_patch_logprobs=True)),
+             (small, dict(output_patch_logprobs=True)), (large, dict())]
+    sessions, p_caps, n_graphs = [], [], []
+    for kw, gen in calls:
+        got = model.generate(max_new_tokens=5, sync_every=2, use_graph=True, lane=11, **gen, **kw)
+        sess = got.past_key_values
+        sessions.append(sess)
+        p_caps.append(sess.p_cap)
+        n_graphs.append(len(sess.graphs))
+        same_output(got, model.generate(max_new_tokens=5, sync_every=2, use_graph=False, lane=12, **gen, **kw))
+        if "output_patch_logprobs" in gen:
+            assert bool(torch.isfinite(got.patch_logprobs[:, 0]).any())
+    assert all(s is sessions[0] for s in sessions), "the lane's session was replaced: the patch buffer did not grow inside one session"
+    assert p_caps[2] < p_caps[3] == p_caps[4], p_caps                # the buffer grew once ...
+    assert n_graphs == [1, 2, 3, 3, 3, 3], n_graphs                  # ... and took the graph captured over the smaller one with it
+
+
 def test_range_guard_rerun_on_the_bf16_twin_carries_the_fields():
     """operands="auto": the batch whose SwiGLU hidden exceeds fp16's range is answered by the bf16 twin — with the new fields, equal to the
     reference of the bf16 model's own scores (the weights of test_token_logprobs_gpu.py's re-run test)"""

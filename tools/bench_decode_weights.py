@@ -25,6 +25,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from padt_amd import config, ops  # noqa: E402
+from padt_amd.generation import GenOptions  # noqa: E402
 from padt_amd.llm import DecodeSession  # noqa: E402
 from padt_amd.weights import PreparedWeights, _pad_to  # noqa: E402
 
@@ -76,10 +77,9 @@ def time_case(cfg, mode, rows, op16, args, device):
     first = torch.randint(0, cfg.vocab_size, (rows,), generator=g, device=device)
     if args.rules:
         ids = torch.randint(0, cfg.vocab_size, (40,), generator=g, device=device).tolist()
-        sess.rules.copy_(ops.gen_rules_tensor(3, [ids[2 * i: 2 * i + 2] for i in range(8)], ids[16: 32], vocab_size=cfg.vocab_size))
+        sess.begin(GenOptions(rules=ops.gen_rules_key(3, [ids[2 * i: 2 * i + 2] for i in range(8)], ids[16: 32], vocab_size=cfg.vocab_size)))
         sess.hist[:, : args.context] = torch.randint(0, cfg.vocab_size, (rows, args.context), generator=g, device=device).to(torch.int32)
         sess.hist_len.fill_(args.context)
-        sess.rules_on = True
 
     def reset():
         """`context` cached tokens per row, step counter at zero: every window replays the same steps (a window never runs past s_max / t_max)."""

@@ -9,7 +9,7 @@ One DecodeSession (padt_amd/llm.py) per row count at the PaDT_Pro_3B LLM shape, 
 
 Timing: `--warmup` replays per mode, then `--repeats` rounds; a round times one window of `--steps` replays between two device events for EVERY
 mode in turn (the modes alternate, so drift of the machine hits them alike).  Per mode the median window is reported with the extremes and every
-window's value.  A library without the feature (the parent commit) runs the modes it has.  Prints one JSON line per (rows, mode).
+window's value.  Prints one JSON line per (rows, mode).
 
 usage: python tools/bench_token_logprobs.py [--rows 8,64] [--modes plain,logprobs,scores] [--operands fp16|bf16] [--steps 64] [--repeats 9]"""
 import argparse
@@ -23,15 +23,14 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from padt_amd import config  # noqa: E402
+from padt_amd.generation import GenOptions  # noqa: E402
 from padt_amd.llm import DecodeSession  # noqa: E402
 from padt_amd.weights import _pad_to  # noqa: E402
 from bench_decode_weights import build_weights  # noqa: E402
 
 
 def set_mode(sess, mode):
-    sess.keep_scores = mode == "scores"
-    if hasattr(sess, "want_logprobs"):
-        sess.want_logprobs(mode == "logprobs")
+    sess.begin(GenOptions(keep_scores=mode == "scores", token_logprobs=mode == "logprobs"))
 
 
 def time_rows(cfg, rows, op16, modes, args, device):
@@ -98,9 +97,6 @@ def main():
             raise SystemExit(f"unknown mode '{m}'")
     if not torch.cuda.is_available():
         raise SystemExit("bench_token_logprobs.py times kernels on an MI355X: no GPU found")
-    if "logprobs" in modes and not hasattr(DecodeSession, "want_logprobs"):
-        print("this library has no output_token_logprobs: the logprobs mode is left out", file=sys.stderr)
-        modes = [m for m in modes if m != "logprobs"]
     device = torch.device("cuda:0")
     op16 = torch.float16 if args.operands == "fp16" else torch.bfloat16
     cfg = config.padt_pro_3b()

@@ -17,8 +17,7 @@ Timing: `--warmup` replays per mode, then `--repeats` rounds; a round times one 
 mode in turn (the modes alternate, so drift of the machine hits them alike).  Per mode the median window is reported with the extremes and every
 window's value.  For the flagged modes the launch pair is also timed alone (`pair_us`, back-to-back launches over the session's row buffer) with
 the rate at which it reads the rows (`pair_read_GBps`: the rows are cache-resident there, so this is no HBM bandwidth); `extra_bytes_per_step` is
-a count of what the mode moves, not a measurement.  A library without the feature (the parent commit) runs plain and scores.  Prints one JSON
-line per (rows, mode).
+a count of what the mode moves, not a measurement.  Prints one JSON line per (rows, mode).
 
 usage: python tools/bench_top_logprobs.py [--rows 8,64] [--modes plain,top5,top32,patches,both,scores] [--operands fp16|bf16] [--patches 256]"""
 import argparse
@@ -32,6 +31,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from padt_amd import config  # noqa: E402
+from padt_amd.generation import GenOptions  # noqa: E402
 from padt_amd.llm import DecodeSession  # noqa: E402
 from padt_amd.weights import _pad_to  # noqa: E402
 from bench_decode_weights import build_weights  # noqa: E402
@@ -40,9 +40,7 @@ MODES = {"plain": (0, False), "top5": (5, False), "top32": (32, False), "patches
 
 
 def set_mode(sess, mode, patches):
-    sess.keep_scores = mode == "scores"
-    if hasattr(sess, "want_top"):
-        sess.want_top(MODES[mode][0], MODES[mode][1], patches)
+    sess.begin(GenOptions(keep_scores=mode == "scores", top_logprobs=MODES[mode][0], patch_logprobs=MODES[mode][1]), patches)
 
 
 def time_rows(cfg, rows, op16, modes, args, device):
@@ -101,8 +99,8 @@ def time_rows(cfg, rows, op16, modes, args, device):
             e0.record()
             for _ in range(n):
                 ops.topk_logprob_rows(sess.logits, width, sess.unfinished, sess.step, sess.topk_ws, rows, top_idx=sess.top_idx, top_val=sess.top_val,
-                                      vrt_off=sess.vrt_off if sess.keep_patch else None, vocab=cfg.vocab_size,
-                                      patch_lp=sess.patch_lp if sess.keep_patch else None)
+                                      vrt_off=sess.vrt_off if sess.mode.patches else None, vocab=cfg.vocab_size,
+                                      patch_lp=sess.patch_lp if sess.mode.patches else None)
             e1.record()
             torch.cuda.synchronize()
             t.append(e0.elapsed_time(e1) * 1e3 / n)
@@ -140,9 +138,6 @@ def main():
             raise SystemExit(f"unknown mode '{m}'")
     if not torch.cuda.is_available():
         raise SystemExit("bench_top_logprobs.py times kernels on an MI355X: no GPU found")
-    if not hasattr(DecodeSession, "want_top"):
-        print("this library has no top_logprobs / output_patch_logprobs: plain and scores only", file=sys.stderr)
-        modes = [m for m in modes if m in ("plain", "scores")]
     device = torch.device("cuda:0")
     op16 = torch.float16 if args.operands == "fp16" else torch.bfloat16
     cfg = config.padt_pro_3b()
