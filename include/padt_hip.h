@@ -356,13 +356,27 @@ int  padt_greedy_step_lp(void* stream, const void* part_val, const void* part_id
 /* Sampling branch (padt.py:740-743 multinomial over softmax of the warped scores): one token per row drawn from the fp32 logits
  * padt_vrt_head wrote (logits_f32), after HF's Temperature → TopK → TopP warpers (generation/logits_process.py) with the
  * parameters in gen_cfg (DEVICE: {float penalty; int eos[4]; int do_sample; unsigned seed; float temperature; int top_k;
- * float top_p; int write_back; int pad}); exact top-k by radix select, nucleus over the sorted survivors (top_p < 1 needs
+ * float top_p; int write_back; int pad}, followed by the four floats of padt_warp_sample_rows_f32, which this call ignores); exact top-k by radix select, nucleus over the sorted survivors (top_p < 1 needs
  * 0 < top_k <= 1024; entries tied at the k-th value: the lowest indices stay), Gumbel-max draw keyed by (seed, *step, row, index) so a
  * captured decode graph draws fresh numbers every replay.  Writes one (value, index) pair per row in padt_greedy_step's partial layout
  * (nblk = 1).  write_back != 0: logits_f32[b][0..n_rows_table) is then overwritten with the warped scores (l / T on the kept entries,
  * -inf elsewhere: HF's `scores` under sampling, padt.py:717-720). */
 int  padt_sample_token(void* stream, void* logits_f32, long ld_logits, long n_rows_table, const void* gen_cfg, const int* step,
                        void* part_val, void* part_idx, long batch);
+/* The rest of HF's warper chain and the draw (generate(min_p=, typical_p=, epsilon_cutoff=, eta_cutoff=)): MinP → Typical → Epsilon → Eta
+ * (generation/logits_process.py, min_tokens_to_keep = 1; each takes the softmax over the survivors of the stage before it) over fp32 rows that
+ * hold the scores after temperature / top-k / top-p — what padt_sample_token leaves with write_back, whose own draw is then ignored.
+ * gen_cfg (DEVICE) continues after `pad` with {float min_p; float typical_p; float epsilon_cutoff; float eta_cutoff} (16 words in all); a
+ * warper is active for 0 < min_p <= 1, 0 < typical_p < 1, 0 < cutoff < 1, so 0 / 1 / 0 / 0 switch all four off and one captured graph
+ * serves every setting.  rows_f32[b][0..n_cols) is warped in place: dropped columns become -inf, kept ones keep their bits, columns >= n_cols
+ * are not touched.  The typical-p cut is exact (a radix select over the key |-log p - H| whose histograms hold probability mass) and keeps
+ * every entry with the cut's key.  Writes one (value, index) pair per row in padt_greedy_step's partial layout (nblk = 1): a Gumbel-max
+ * draw from softmax of the final survivors, keyed by (seed, *step, row, index) like padt_sample_token's; (-inf, 0x7fffffff) for a row
+ * without a finite entry.  row_base (nullable; then vrt_off [batch + 1] and vocab are required): row_base[b] = the first row of b's own batch
+ * inside a merged decode group; the draw is keyed by (b - row_base[b], column in the batch's own numbering: a column >= vocab minus
+ * vrt_off[row_base[b]]), so a batch draws inside a group what it draws alone.  Null: (b, column). */
+int  padt_warp_sample_rows_f32(void* stream, void* rows_f32, long ld, long n_cols, const void* gen_cfg, const int* step,
+                               void* part_val, void* part_idx, long batch, long vocab, const int* vrt_off, const int* row_base);
 /* Arg-max of fp32 score rows → one (value, index) pair per row in padt_greedy_step's partial layout (nblk = 1), ties → lowest index
  * (torch.argmax, padt.py:745): the selection of the HOOKED decode loop, where caller-supplied logits processors (padt.py:717) have rewritten
  * the rows padt_vrt_head wrote. */

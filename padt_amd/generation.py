@@ -79,7 +79,8 @@ def check_top_logprobs(top_logprobs) -> int:
 
 # generate()'s named parameters a generation_config may carry: an explicit argument (not None) wins, as in HF (padt.py:436)
 _GENERATE_CONFIG_NAMED = ("max_new_tokens", "max_length", "do_sample", "repetition_penalty", "eos_token_id", "pad_token_id", "temperature", "top_k",
-                          "top_p", "no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens")
+                          "top_p", "no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens", "min_p", "typical_p",
+                          "epsilon_cutoff", "eta_cutoff")
 # ... and those whose value is this path's own default either way (hidden states and the dict output are what its callers consume)
 _GENERATE_CONFIG_OWN = ("use_cache", "output_hidden_states", "return_dict_in_generate")
 
@@ -106,11 +107,47 @@ def generation_config_fields(generation_config) -> dict:
 
 # ------------------------------------------------------------------------------------------------ what a generate() resolved to
 class Sampling(NamedTuple):
-    """do_sample=True: HF's Temperature → TopK → TopP warpers and the key of the device's counter-based generator."""
+    """do_sample=True: HF's Temperature → TopK → TopP → MinP → Typical → Epsilon → Eta warpers and the key of the device's counter-based
+    generator.  The last four hold their "off" value unless HF would build the warper (resolve_options), so equal behaviour is equal options."""
     temperature: float
     top_k: int
     top_p: float
     seed: int
+    min_p: float = 0.0               # MinPLogitsWarper: 0 < min_p <= 1
+    typical_p: float = 1.0           # TypicalLogitsWarper: 0 < typical_p < 1
+    epsilon_cutoff: float = 0.0      # EpsilonLogitsWarper: 0 < epsilon_cutoff < 1
+    eta_cutoff: float = 0.0          # EtaLogitsWarper: 0 < eta_cutoff < 1
+
+    @property
+    def warpers(self) -> bool:
+        """One of the four warpers after top-p is active: padt_warp_sample_rows_f32 runs after the sampling kernel."""
+        return self.min_p > 0.0 or self.typical_p < 1.0 or self.epsilon_cutoff > 0.0 or self.eta_cutoff > 0.0
+
+
+_SAMPLING_OFF = dict(min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0)
+WARPER_NAMES = tuple(_SAMPLING_OFF)
+
+
+class _ConfigOverlay:
+    """A generation config whose listed fields are a call's own values (with_warpers)."""
+
+    def __init__(self, base, over):
+        self.__dict__.update(_base=base, _over=over)
+
+    def __getattr__(self, name):
+        over = self.__dict__["_over"]
+        return over[name] if name in over else getattr(self.__dict__["_base"], name)
+
+
+def with_warpers(gc, values):
+    """The generation config `gc` with the call's min_p / typical_p / epsilon_cutoff / eta_cutoff in front of its own: `values` maps the names
+    to what the caller passed, None = not passed.  resolve_options reads the four from the config it is given — that is how a call's values
+    reach it from generate(), PipelinedRunner.submit and rec_batch."""
+    over = {k: v for k, v in (values or {}).items() if v is not None}
+    unknown = set(over) - set(WARPER_NAMES)
+    if unknown:
+        raise ValueError(f"not a sampling warper: {sorted(unknown)}")
+    return _ConfigOverlay(gc, over) if over else gc
 
 
 class StepMode(NamedTuple):
@@ -125,6 +162,7 @@ class StepMode(NamedTuple):
     patches: bool = False            # ... and / or the sample's own patch columns
     processors: bool = False         # the caller's logits_processor rewrites the rows (hooked loop: never captured)
     reference: bool = False          # precision="reference": reference.ReferencePath.step instead of step_kernels
+    warpers: bool = False            # min_p / typical_p / epsilon_cutoff / eta_cutoff: padt_warp_sample_rows_f32 warps the row and draws
 
 
 @dataclass(frozen=True)
@@ -148,7 +186,7 @@ class GenOptions:
     @property
     def write_back(self) -> bool:
         """The sampling kernel overwrites its rows with the warped scores: whoever reads the row after it must see what was sampled from."""
-        return self.sampling is not None and bool(self.keep_scores or self.token_logprobs or self.want_rows)
+        return self.sampling is not None and bool(self.keep_scores or self.token_logprobs or self.want_rows or self.sampling.warpers)
 
     @property
     def reads_prompt(self) -> bool:
@@ -159,12 +197,19 @@ class GenOptions:
         """The generation-config slots the head / selection kernels read (ops.gen_cfg_tensor), on the host."""
         s = self.sampling or Sampling(1.0, 0, 1.0, 0)
         return ops.gen_cfg_tensor(self.repetition_penalty, self.eos_ids, "cpu", do_sample=self.sampling is not None, seed=s.seed,
-                                  temperature=s.temperature, top_k=s.top_k, top_p=s.top_p, write_back=self.write_back)
+                                  temperature=s.temperature, top_k=s.top_k, top_p=s.top_p, write_back=self.write_back, min_p=s.min_p,
+                                  typical_p=s.typical_p, epsilon_cutoff=s.epsilon_cutoff, eta_cutoff=s.eta_cutoff)
 
     def step_mode(self, processors: bool = False, reference: bool = False) -> StepMode:
         return StepMode(sampling=self.sampling is not None, keep_scores=self.keep_scores, keep_logits=self.keep_logits, rules=self.rules is not None,
                         token_logprobs=self.token_logprobs, top_k=self.top_logprobs, patches=self.patch_logprobs, processors=bool(processors),
-                        reference=bool(reference))
+                        reference=bool(reference), warpers=self.sampling is not None and self.sampling.warpers)
+
+    def warper_kwargs(self) -> dict:
+        """min_p / typical_p / epsilon_cutoff / eta_cutoff as explicit generate() keywords (with_warpers values), next to generate_kwargs():
+        off is spelled 0.0 / 1.0, never None, so that no generation_config can switch a warper back on."""
+        s = self.sampling
+        return dict(_SAMPLING_OFF) if s is None else {name: getattr(s, name) for name in WARPER_NAMES}
 
     def generate_kwargs(self) -> dict:
         """Explicit generate() arguments that resolve back to these options under ANY generation_config: what is off is spelled as off (0, [],
@@ -172,6 +217,8 @@ class GenOptions:
         output_scores / output_logits are the caller's to pass: they also decide what is returned, which the options do not record."""
         n_gram, static, begin, words = self.rules or (0, (), (), ())
         kw = dict(do_sample=False) if self.sampling is None else dict(do_sample=True, **self.sampling._asdict())
+        for name in WARPER_NAMES:                                 # not arguments of generate_launch: warper_kwargs()
+            kw.pop(name, None)
         return dict(kw, repetition_penalty=self.repetition_penalty, eos_token_id=list(self.eos_ids), no_repeat_ngram_size=n_gram,
                     bad_words_ids=[list(wd) for wd in words], suppress_tokens=list(static), begin_suppress_tokens=list(begin),
                     output_token_logprobs=self.token_logprobs, top_logprobs=self.top_logprobs, output_patch_logprobs=self.patch_logprobs)
@@ -182,12 +229,23 @@ def resolve_options(gc, config_eos_id, vocab_size, do_sample=None, repetition_pe
                     suppress_tokens=None, begin_suppress_tokens=None, output_token_logprobs=False, top_logprobs=None,
                     output_patch_logprobs=False) -> GenOptions:
     """generate_launch's arguments (same names) → GenOptions.  gc: the model's generation_config, whose field applies where the argument is
-    None (HF: padt.py:436); config_eos_id / vocab_size: the model config's.  Pure but for the seed, which is drawn from torch's global
+    None (HF: padt.py:436) — and, through with_warpers, the call's min_p / typical_p / epsilon_cutoff / eta_cutoff; config_eos_id / vocab_size: the model config's.  Pure but for the seed, which is drawn from torch's global
     generator when sampling without one (so torch.manual_seed makes runs repeatable) — and only then."""
     top_logprobs = check_top_logprobs(top_logprobs)
     dflt = lambda name, v: getattr(gc, name, None) if v is None else v
     do_sample = dflt("do_sample", do_sample)
     temperature, top_k, top_p = float(dflt("temperature", temperature)), int(dflt("top_k", top_k)), float(dflt("top_p", top_p))
+    # the four warpers after top-p come from gc alone (a call's own values: with_warpers): validated as HF's classes validate them, whatever
+    # the mode; a gc without the attribute means off
+    warp = {}
+    for name, (lo, hi, lo_open, hi_open) in (("min_p", (0.0, 1.0, False, False)), ("typical_p", (0.0, 1.0, True, False)),
+                                             ("epsilon_cutoff", (0.0, 1.0, False, True)), ("eta_cutoff", (0.0, 1.0, False, True))):
+        v = getattr(gc, name, None)
+        v = _SAMPLING_OFF[name] if v is None else v
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not ((lo < v or (not lo_open and v == lo)) and (v < hi or (not hi_open and v == hi))):
+            raise ValueError(f"generate({name}={v!r}): a number in {'(' if lo_open else '['}{lo:g}, {hi:g}{')' if hi_open else ']'} is required "
+                             f"(HF's {name} warper)")
+        warp[name] = float(v)
     if do_sample and top_k == 1:
         do_sample = False                                         # sampling among the single best token IS the arg-max
     samp = None
@@ -198,7 +256,7 @@ def resolve_options(gc, config_eos_id, vocab_size, do_sample=None, repetition_pe
             raise NotImplementedError("top_p < 1 is supported together with 0 < top_k <= 1024 (the nucleus is taken over the top-k survivors)")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-        samp = Sampling(temperature, top_k, top_p, int(seed))
+        samp = Sampling(temperature, top_k, top_p, int(seed), **warp)      # a value HF builds no warper for IS its off value (0 / 1 / 0 / 0)
     eos = dflt("eos_token_id", eos_token_id)
     eos = (int(eos),) if isinstance(eos, int) else tuple(int(e) for e in eos)
     if config_eos_id not in eos or len(eos) > 4:

@@ -303,6 +303,7 @@ class DecodeSession:
         self.vtc = [z(B, Hkv, hd, s_max) for _ in range(nl)]
         self.proto = z(np_max, D)
         self.vrt_off = z(B + 1, dt=I32)
+        self.batch_row0 = z(B, dt=I32)     # per row: the first row of its batch in a merged decode group (the warper kernel's generator key)
         self.mode_table = z(t_max + 1, dt=I32)
         self.step = z(1, dt=I32)
         self.unfinished = z(B, dt=I32)
@@ -494,6 +495,12 @@ class DecodeSession:
             # with keep_scores (or token_logprobs) the session's gen_cfg has write_back set: lg then holds the warped rows (l / T, -inf outside top-k / top-p),
             # HF's next_token_scores — the warpers are part of its logits_processor (padt.py:717)
             ops.sample_token(lg, cfg.vocab_size + self.np_max, self.gen_cfg, self.step, self.part_val, self.part_idx, self.B)
+            if m.warpers:
+                # min_p / typical_p / epsilon_cutoff / eta_cutoff (HF's warpers after top-p): write_back is set, so lg holds the row after
+                # temperature / top-k / top-p; the kernel warps it further in place and draws from what stays, replacing sample_token's draw —
+                # every reader below (scores stash, token / top-k log-probs, the caller's criteria) then sees HF's next_token_scores
+                ops.warp_sample_rows(lg, cfg.vocab_size + self.np_max, self.gen_cfg, self.step, self.part_val, self.part_idx, self.B,
+                                     vocab=cfg.vocab_size, vrt_off=self.vrt_off, row_base=self.batch_row0)
             if m.keep_scores:
                 ops.stash_step_f32(lg, self.step, self.scores)
             nblk = 1

@@ -21,7 +21,7 @@ from . import _lib, ops
 from .config import PaDTConfig
 from .decoder import PaDTDecoder
 from .generation import (_GENERATE_CONFIG_NAMED, _GENERATE_CONFIG_OWN, check_generate_kwargs, check_top_logprobs,  # noqa: F401
-                         generation_config_fields, resolve_options)
+                         generation_config_fields, resolve_options, with_warpers, WARPER_NAMES)
 from .llm import MODE, LanguageModel, check_shared_destinations, plan_prompt, plan_prompt_shared
 from .vision import VisionEncoder
 from .weights import Fp16RangeError, load_checkpoint_state_dict, prepare_weights, synthetic_state_dict
@@ -180,7 +180,7 @@ class PaDTForConditionalGeneration:
     def load_generation_config(self, d: dict):
         """generation_config.json → defaults of generate(), as HF's GenerationMixin applies them (padt.py:436): repetition_penalty,
         eos_token_id (int or list), pad_token_id, do_sample / temperature / top_k / top_p, and the pure-ban processors no_repeat_ngram_size /
-        bad_words_ids / suppress_tokens / begin_suppress_tokens."""
+        bad_words_ids / suppress_tokens / begin_suppress_tokens, and the warpers after top-p: min_p / typical_p / epsilon_cutoff / eta_cutoff."""
         g = self.generation_config
         if d.get("repetition_penalty") is not None:
             g.repetition_penalty = float(d["repetition_penalty"])
@@ -199,6 +199,9 @@ class PaDTForConditionalGeneration:
         for k in ("suppress_tokens", "begin_suppress_tokens"):
             if d.get(k) is not None:
                 setattr(g, k, [int(i) for i in d[k]])
+        for k in ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff"):      # validated where they are used (generation.resolve_options)
+            if d.get(k) is not None:
+                setattr(g, k, float(d[k]))
         return g
 
     @classmethod
@@ -310,15 +313,24 @@ class PaDTForConditionalGeneration:
         ``top_p``, defaults from generation_config, HF's own defaults 1.0 / 50 / 1.0) on a device counter-based generator keyed
         by ``seed`` (default: drawn from torch's global generator, so torch.manual_seed makes runs repeatable).  The draws are
         not torch.multinomial's; the distribution is.
+        Keywords ``min_p`` (in [0, 1]; 0: off) / ``typical_p`` (in (0, 1]; 1: off) / ``epsilon_cutoff`` / ``eta_cutoff`` (in [0, 1); 0: off): the rest of
+        HF's warper list, in its order (MinP → Typical → Epsilon → Eta after top-p, ``min_tokens_to_keep = 1``, each over the softmax of
+        what the stage before it kept), on the device inside the captured step (``padt_warp_sample_rows_f32``); defaults from
+        generation_config / ``generation_config=``, ``ValueError`` naming the argument outside the range, ignored under greedy decoding as
+        in HF.  ``.scores``, ``token_logprobs``, ``top_logprobs`` / ``patch_logprobs`` and stopping criteria see the fully warped row.  A value
+        HF builds no warper for is the same call as without the argument: same kernels, same decode group.
         """
         if synced_gpus:
             raise NotImplementedError("generate(synced_gpus=True) is the ZeRO-3 / FSDP lock-step loop (padt.py:445,670): every rank holds a full "
                                       "replica on this path — pass synced_gpus=False")
+        # HF's warpers after top-p are keywords of this call (not named parameters: the parameter list is frozen)
+        min_p, typical_p, epsilon_cutoff, eta_cutoff = (kwargs.pop(k, None) for k in WARPER_NAMES)
         if generation_config is not None:
             named = dict(max_new_tokens=max_new_tokens, max_length=max_length, do_sample=do_sample, repetition_penalty=repetition_penalty,
                          eos_token_id=eos_token_id, pad_token_id=pad_token_id, temperature=temperature, top_k=top_k, top_p=top_p,
                          no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens,
-                         begin_suppress_tokens=begin_suppress_tokens)
+                         begin_suppress_tokens=begin_suppress_tokens, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff,
+                         eta_cutoff=eta_cutoff)
             for k, v in generation_config_fields(generation_config).items():
                 if k in _GENERATE_CONFIG_NAMED:
                     if named[k] is None:
@@ -334,7 +346,8 @@ class PaDTForConditionalGeneration:
                 elif k not in _GENERATE_CONFIG_OWN:
                     kwargs.setdefault(k, v)                           # the keyword policy below names what this path does not implement
             (max_new_tokens, max_length, do_sample, repetition_penalty, eos_token_id, pad_token_id, temperature, top_k, top_p, no_repeat_ngram_size,
-             bad_words_ids, suppress_tokens, begin_suppress_tokens) = (named[k] for k in _GENERATE_CONFIG_NAMED)
+             bad_words_ids, suppress_tokens, begin_suppress_tokens, min_p, typical_p, epsilon_cutoff, eta_cutoff) = (
+                named[k] for k in _GENERATE_CONFIG_NAMED)
         max_new_tokens = check_generate_kwargs(kwargs, max_new_tokens, max_length, None if input_ids is None else input_ids.shape[1])
         top_logprobs = check_top_logprobs(top_logprobs)
         if pad_token_id is not None and int(pad_token_id) != int(self.generation_config.pad_token_id):
@@ -346,6 +359,10 @@ class PaDTForConditionalGeneration:
         if processors is not None or criteria is not None:
             hooks = dict(processors=processors, criteria=criteria, pass_scores=bool(output_scores))
             use_graph, sync_every = False, 1                          # host callables between the kernels of every step
+        hooked = hooks is not None
+        warpers = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
+        if any(v is not None for v in warpers.values()):
+            hooks = dict(hooks or {}, warpers=warpers)                # generate_launch's channel for them (see there)
         if output_logits:
             pen = self.generation_config.repetition_penalty if repetition_penalty is None else repetition_penalty
             if float(pen) != 1.0 or schedule is not None or processors is not None:
@@ -355,7 +372,7 @@ class PaDTForConditionalGeneration:
         ctx = self.generate_launch(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, do_sample,
                                    schedule, sync_every, use_graph, lane, repetition_penalty=repetition_penalty,
                                    eos_token_id=eos_token_id, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
-                                   keep_scores=bool(output_scores or output_logits or hooks is not None), hooks=hooks,
+                                   keep_scores=bool(output_scores or output_logits or hooked), hooks=hooks,
                                    keep_logits=bool(output_logits), no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                                    suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens, image_index=image_index,
                                    output_token_logprobs=bool(output_token_logprobs), top_logprobs=top_logprobs,
@@ -384,14 +401,24 @@ class PaDTForConditionalGeneration:
         ``image_index`` (see generate()): the ViT and the prototype projection run on the N unique images and their rows are expanded per
         sample on the device; the prompt pass runs llm.plan_prompt_shared's token set.  Only THIS batch's prompt pass changes: the decode
         steps, and the rows of other batches of a merged group, are what they are without an index.
+
+        ``hooks``: generate()'s caller processors / stopping criteria (``processors``, ``criteria``, ``pass_scores``) and / or the call's warpers
+        after top-p, ``hooks=dict(warpers=dict(min_p=..., typical_p=..., epsilon_cutoff=..., eta_cutoff=...))`` (None entries: the
+        generation config decides); warpers alone keep the captured step and merged groups.
         """
+        # a call's min_p / typical_p / epsilon_cutoff / eta_cutoff arrive as hooks["warpers"] (this method's parameter list is frozen) and are put
+        # in front of the generation config's; what is left of `hooks` is the caller's processors / criteria, or nothing
+        gen_cfg = self.generation_config
+        if hooks is not None and "warpers" in hooks:
+            gen_cfg = with_warpers(gen_cfg, hooks["warpers"])
+            hooks = {k: v for k, v in hooks.items() if k != "warpers"} or None
         if image_index is not None and getattr(self, "precision", "default") == "reference":
             raise NotImplementedError("generate(image_index=...) is not implemented with precision='reference' (its prompt pass is its own: "
                                       "reference.ReferencePath.prefill): expand the inputs or use precision='default'")
         # operands="auto" whose checkpoint keeps overflowing fp16: new decode groups start on the bf16 twin (a group stays with its owner).  The
         # options resolve the same on either: the twin shares this model's generation_config and config
         owner = group["owner"] if group is not None else (self.fallback_model() if self.prefers_bf16 else self)
-        opts = resolve_options(self.generation_config, self.config.eos_token_id, self.config.vocab_size, do_sample=do_sample,
+        opts = resolve_options(gen_cfg, self.config.eos_token_id, self.config.vocab_size, do_sample=do_sample,
                                repetition_penalty=repetition_penalty, eos_token_id=eos_token_id, temperature=temperature, top_k=top_k, top_p=top_p,
                                seed=seed, keep_scores=keep_scores, keep_logits=keep_logits, no_repeat_ngram_size=no_repeat_ngram_size,
                                bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
@@ -456,6 +483,8 @@ class PaDTForConditionalGeneration:
             sess.pos3.zero_()
             sess.cur_tok.fill_(cfg.pad_token_id)
             sess.vrt_off.zero_()
+            if opts.sampling is not None and opts.sampling.warpers:
+                sess.batch_row0.zero_()                           # read by the warper kernel alone
             if self.ref is not None and (sess.hid32 is None or sess.hid32.shape[0] < T_max):
                 sess.hid32 = torch.zeros((sess.t_max, sess.B, cfg.hidden_size), device=dev, dtype=torch.float32)
         else:
@@ -505,6 +534,8 @@ class PaDTForConditionalGeneration:
         sess.vrt_off[row0: row0 + B + 1].copy_(off.to(dev, non_blocking=True))
         if row0 + B + 1 < sess.vrt_off.numel():
             sess.vrt_off[row0 + B + 1:].fill_(proto_row0 + n_proto)     # rows not (yet) in use: empty VRT range
+        if opts.sampling is not None and opts.sampling.warpers:
+            sess.batch_row0[rows].fill_(row0)
         sess.unfinished[rows].fill_(1)
         lens_t = torch.tensor(plan.lens, dtype=torch.int32)
         sess.slot[rows].copy_(lens_t.to(dev, non_blocking=True))        # next append index
@@ -670,7 +701,7 @@ class PaDTForConditionalGeneration:
                           "instantiation" % (self.overflow_reruns, self._batches_seen), RuntimeWarning, stacklevel=3)
         am, pix, grid, image_index = sub["inputs"]
         # the group's options spelled as explicit arguments (an "off" is 0 / [], never the default), and what this collect was asked to return
-        kw = dict(group["opts"].generate_kwargs(), output_scores=output_scores, output_logits=output_logits)
+        kw = dict(group["opts"].generate_kwargs(), **group["opts"].warper_kwargs(), output_scores=output_scores, output_logits=output_logits)
         if group.get("hooks") is not None:
             kw.update(logits_processor=group["hooks"]["processors"], stopping_criteria=group["hooks"]["criteria"])
         return fb.generate(input_ids=sub["input_ids"], attention_mask=am, pixel_values=pix, image_grid_thw=grid, max_new_tokens=group["T_max"],

@@ -859,15 +859,20 @@ def gen_rules(rules, hist, hist_len, tokens, step, ban, n_cols):
 
 
 def gen_cfg_tensor(repetition_penalty=1.0, eos_ids=(), device="cuda", do_sample=False, seed=0, temperature=1.0, top_k=0, top_p=1.0,
-                   write_back=False):
+                   write_back=False, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
     """Device copy of the generation-config slots the head / greedy / sampling kernels read:
-    {float penalty; int eos[4]; int do_sample; unsigned seed; float temperature; int top_k; float top_p; int write_back; int pad}.
+    {float penalty; int eos[4]; int do_sample; unsigned seed; float temperature; int top_k; float top_p; int write_back; int pad;
+    float min_p; float typical_p; float epsilon_cutoff; float eta_cutoff} — the last four read by warp_sample_rows alone, off at 0 / 1 / 0 / 0.
     write_back: sample_token overwrites its rows with the warped scores (output_scores / stopping criteria under sampling)."""
     import struct
     eos = list(eos_ids)[:4] + [-1] * (4 - min(4, len(eos_ids)))
-    raw = struct.pack("<f4iiIfifii", float(repetition_penalty), *eos, 1 if do_sample else 0, int(seed) & 0xFFFFFFFF, float(temperature),
-                      int(top_k), float(top_p), 1 if write_back else 0, 0)
+    raw = struct.pack("<f4iiIfifii4f", float(repetition_penalty), *eos, 1 if do_sample else 0, int(seed) & 0xFFFFFFFF, float(temperature),
+                      int(top_k), float(top_p), 1 if write_back else 0, 0, float(min_p), float(typical_p), float(epsilon_cutoff),
+                      float(eta_cutoff))
     return torch.frombuffer(bytearray(raw), dtype=torch.int32).clone().to(device)
+
+
+GEN_CFG_INTS = 16
 
 
 def sample_token(logits, n_rows_table, gen_cfg, step, part_val, part_idx, batch):
@@ -876,6 +881,23 @@ def sample_token(logits, n_rows_table, gen_cfg, step, part_val, part_idx, batch)
     assert logits.dtype == torch.float32 and logits.stride(-1) == 1
     _lib.check(_lib.load().padt_sample_token(_stream(), _p(logits), logits.stride(0), int(n_rows_table), _p(gen_cfg), _p(step), _p(part_val),
                                              _p(part_idx), int(batch)), "padt_sample_token")
+
+
+def warp_sample_rows(rows, n_cols, gen_cfg, step, part_val, part_idx, batch, vocab=0, vrt_off=None, row_base=None):
+    """HF's MinP → Typical → Epsilon → Eta warpers, in place, over the fp32 rows sample_token left with write_back (dropped columns of
+    [0, n_cols) become -inf, kept ones keep their bits), and one multinomial draw per row from what stays into the (value, index) partial
+    layout (padt_warp_sample_rows_f32); the four values are gen_cfg's last slots (gen_cfg_tensor).  row_base int32 [>= batch] (with vrt_off
+    int32 [>= batch + 1] and vocab): the first row of each row's own batch in a merged decode group — the generator is then keyed by the row
+    and column numbers the batch has alone."""
+    assert rows.dtype == torch.float32 and rows.is_cuda and rows.dim() == 2 and rows.stride(1) == 1 and rows.shape[0] >= batch and rows.shape[1] >= n_cols
+    assert gen_cfg.dtype == torch.int32 and gen_cfg.is_contiguous() and gen_cfg.numel() >= GEN_CFG_INTS
+    assert part_val.dtype == torch.float32 and part_val.numel() >= batch and part_idx.dtype == torch.int32 and part_idx.numel() >= batch
+    if row_base is not None:
+        assert row_base.dtype == torch.int32 and row_base.is_contiguous() and row_base.numel() >= batch
+        assert vrt_off is not None and vrt_off.dtype == torch.int32 and vrt_off.is_contiguous() and vrt_off.numel() >= batch + 1
+    _lib.check(_lib.load().padt_warp_sample_rows_f32(_stream(), _p(rows), rows.stride(0), int(n_cols), _p(gen_cfg), _p(step), _p(part_val),
+                                                     _p(part_idx), int(batch), int(vocab), _p(vrt_off) if row_base is not None else None,
+                                                     _p(row_base)), "padt_warp_sample_rows_f32")
 
 
 def argmax_rows(scores, n_cols, part_val, part_idx, batch):

@@ -19,11 +19,14 @@ def sample_grids(image_grid_thw, image_index):
 
 
 def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens=1024,
-              schedule: Optional[Sequence] = None, need_thinking_mask=None, image_index=None, **gen_kw):
+              schedule: Optional[Sequence] = None, need_thinking_mask=None, image_index=None, do_sample=False, min_p=None, typical_p=None,
+              epsilon_cutoff=None, eta_cutoff=None, **gen_kw):
     """→ (decoded dict of vl_decode, completions, labels, vrts).  ``input_ids`` carries LOCAL VRT ids (as a processor
     emits them) and is updated in place exactly like the reference's callers do.
     ``image_index``: sample b asks about image image_index[b] of the N <= B images given (generate(image_index=)); everything per sample
-    (VRT id ranges, vl_decode) then follows ``image_grid_thw[image_index]``."""
+    (VRT id ranges, vl_decode) then follows ``image_grid_thw[image_index]``.
+    ``do_sample`` (default: greedy, whatever the checkpoint's generation_config says) with ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` /
+    ``eta_cutoff`` and, through ``**gen_kw``, ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: see generate()."""
     B = input_ids.shape[0]
     grid_in = image_grid_thw
     if image_index is not None:
@@ -31,8 +34,9 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
         image_grid_thw = sample_grids(image_grid_thw, image_index)
     ids = processor.assign_to_global_vrt_id(input_ids, image_grid_thw)
     out = model.generate(input_ids=ids, attention_mask=attention_mask, pixel_values=pixel_values,
-                         image_grid_thw=grid_in, use_cache=True, max_new_tokens=max_new_tokens, do_sample=False,
-                         output_hidden_states=True, return_dict_in_generate=True, schedule=schedule, **gen_kw)
+                         image_grid_thw=grid_in, use_cache=True, max_new_tokens=max_new_tokens, do_sample=do_sample,
+                         output_hidden_states=True, return_dict_in_generate=True, schedule=schedule, min_p=min_p, typical_p=typical_p,
+                         epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, **gen_kw)
     L = input_ids.shape[1]
     seq_local = processor.assign_to_local_vrt_id(out["sequences"].cpu(), image_grid_thw.cpu())
     completion_ids = seq_local[:, L:]
@@ -99,8 +103,11 @@ class PipelinedRunner:
 
     def submit(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens=1024, schedule=None,
                need_thinking_mask=None, sync_every=None, repetition_penalty=None, eos_token_id=None, no_repeat_ngram_size=None,
-               bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None, **sampling):
+               bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None, do_sample=False, min_p=None,
+               typical_p=None, epsilon_cutoff=None, eta_cutoff=None, **sampling):
         """image_index: see generate(); the batch's results are those of the expanded batch.
+        do_sample (default: greedy) with min_p / typical_p / epsilon_cutoff / eta_cutoff and, through **sampling, temperature / top_k / top_p /
+        seed: see generate(); batches whose resolved options differ in any of them (the seed included) do not share a decode group.
         output_token_logprobs / top_logprobs / output_patch_logprobs (through **sampling, see generate()): the decoded dict of the batch carries
         "token_logprobs" / "top_token_ids" + "top_logprobs" / "patch_logprobs" when asked; batches that disagree on them do not share a decode group."""
         done = []
@@ -111,6 +118,7 @@ class PipelinedRunner:
             image_grid_thw = sample_grids(image_grid_thw, image_index)
         ids = self.processor.assign_to_global_vrt_id(input_ids, image_grid_thw)
         sched = tuple(schedule) if schedule is not None else None
+        warpers = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
         for attempt in range(2):
             if self.cur is None:
                 while len(self.pending) > self.depth - 1:         # the lane about to be reused must have been collected
@@ -133,13 +141,15 @@ class PipelinedRunner:
                         t.record_stream(self.vit_stream)
             self._mark(bid, "prefill_begin", pre)
             with torch.cuda.stream(pre):
-                ctx = self.model.generate_launch(ids, attention_mask, pixel_values, grid_in, max_new_tokens, False,
+                ctx = self.model.generate_launch(ids, attention_mask, pixel_values, grid_in, max_new_tokens, do_sample,
                                                  sched, sync_every or max_new_tokens, self.use_graph, g["lane"],
                                                  self.decode_streams[g["lane"]], group=g["ctx"], n_slots=self.merge,
                                                  repetition_penalty=repetition_penalty, eos_token_id=eos_token_id,
                                                  no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                                                  suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
-                                                 vit_stream=self.vit_stream, inputs_ready=ev_in, image_index=image_index, **sampling)
+                                                 vit_stream=self.vit_stream, inputs_ready=ev_in, image_index=image_index,
+                                                 hooks=dict(warpers=warpers) if any(v is not None for v in warpers.values()) else None,
+                                                 **sampling)
             if ctx is not None:
                 break
             self._close_cur()                                     # batch does not fit this group's session: start a new one
