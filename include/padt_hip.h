@@ -353,6 +353,32 @@ int  padt_greedy_step_lp(void* stream, const void* part_val, const void* part_id
                          int pad, long t_max, int* unfinished, long* tokens_out, long* cur_tok, int* step, int* slot,
                          int* lens, int* pos3, const void* hidden, void* hidden_buf, int advance, const void* gen_cfg,
                          void* seen, long seen_words, const void* part_sum, void* logprobs);
+/* generate(forced_tokens=): the caller's tokens, forced inside the decode step.  forced: int32 [batch][t_forced] table columns (0 <= id <
+ * vocab + n_proto, ids >= vocab in the session's prototype numbering), a negative entry = a free step; read at *step, a step outside
+ * [0, t_forced) is free.
+ * padt_vrt_head_probe: padt_vrt_head_lse that also writes probe_val[b] (fp32 [batch]) = the processed logit — what `logits_f32` gets: masked,
+ * penalised, ban-filtered — of column forced[b][*step]; rows with a free step write nothing.  Partials, part_sum and written logits are those
+ * of padt_vrt_head_lse, bit for bit. */
+int  padt_vrt_head_probe(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab, const void* proto,
+                         long n_proto, const int* vrt_off, const int* mode_table, const int* step, void* logits_f32,
+                         long ld_logits, void* part_val, void* part_idx, long batch, long D, int eos,
+                         const void* embed_table_packed, const void* gen_cfg, const void* seen, long seen_words,
+                         const void* ban, long ban_words, void* part_sum, const int* forced, long t_forced, void* probe_val);
+/* padt_greedy_step(_lp) with the forced table: after the arg-max (and the LSE fold) an unfinished row with a forced entry in [0, n_cols) takes
+ * it as its token — appended, fed to the next step, entered in `seen`, an EOS id finishes the row — even where its score is -inf (the
+ * no-candidate → pad branch applies to free rows only).  part_sum / logprobs / probe_val: all three (then logprobs[b][*step] =
+ * probe == -inf ? -inf : (probe - max) - log Σ on a forced row, padt_greedy_step_lp's value on every other) or all null (no log-probs: the
+ * partials of plain padt_vrt_head / padt_vrt_head_ban). */
+int  padt_forced_step(void* stream, const void* part_val, const void* part_idx, long nblk, long batch, long D, int eos,
+                      int pad, long t_max, int* unfinished, long* tokens_out, long* cur_tok, int* step, int* slot,
+                      int* lens, int* pos3, const void* hidden, void* hidden_buf, int advance, const void* gen_cfg,
+                      void* seen, long seen_words, const void* part_sum, void* logprobs, const int* forced, long t_forced,
+                      const void* probe_val, long n_cols);
+/* Row path (the token comes from padt_sample_token / padt_warp_sample_rows_f32 / padt_argmax_rows_f32): part_idx[b] = forced[b][*step] for
+ * every unfinished row with a forced entry in [0, n_cols), between the selection kernel and padt_token_logprob_rows_f32 / padt_forced_step;
+ * free and finished rows keep their index. */
+int  padt_forced_override(void* stream, void* part_idx, const int* forced, long t_forced, const int* step, const int* unfinished,
+                          long n_cols, long batch);
 /* Sampling branch (padt.py:740-743 multinomial over softmax of the warped scores): one token per row drawn from the fp32 logits
  * padt_vrt_head wrote (logits_f32), after HF's Temperature → TopK → TopP warpers (generation/logits_process.py) with the
  * parameters in gen_cfg (DEVICE: {float penalty; int eos[4]; int do_sample; unsigned seed; float temperature; int top_k;

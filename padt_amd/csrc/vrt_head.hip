@@ -54,6 +54,8 @@ struct HeadArgs {
     const unsigned* seen; long seen_words;
     const unsigned* ban; long ban_words;   // optional per-sample bitmap of banned table rows (gen_rules_kernel): bit set → the logit is -inf
     float* part_sum;                   // LSE kernels: [nblk][B] Σ exp(v - block max) over the block's 16 masked logits (token log-probs)
+    const int* forced; int t_forced;   // PROBE kernels: [B][t_forced] table columns the caller forces (generate(forced_tokens=)), < 0 = free step
+    float* probe_val;                  // PROBE kernels: [B] the processed logit at forced[m][*step]
 };
 
 // PACKED: text rows come from a fragment-packed copy of the table ([V/16][D/32][64 lanes][8], ops.pack_weight — every wave
@@ -66,7 +68,9 @@ struct HeadArgs {
 // ban-filtered logits of a sample — greedy_step_kernel<true> folds the (best, s) pairs into log p(token) without any logit row in memory.
 // exp is v_exp_f32 on (v - best)·log2e: the argument is <= 0, so nothing overflows however large the logits are; a block without an allowed
 // row (best = -inf) yields s = 0.  MFMA order, cross-wave sum and the (best, idx) partials are those of LSE = false, bit for bit.
-template <int MT, int NT, bool PACKED, bool LSE = false>
+// PROBE (padt_vrt_head_probe, an LSE kernel plus one store): the lane that owns column forced[m][*step] of sample m also writes the value v it
+// writes to `logits` — masked, penalised, ban-filtered — to probe_val[m]; a negative entry, or a step outside [0, t_forced), writes nothing.
+template <int MT, int NT, bool PACKED, bool LSE = false, bool PROBE = false>
 __global__ __launch_bounds__(256) void vrt_head_kernel(HeadArgs p) {
     extern __shared__ __attribute__((aligned(16))) float red_raw[];
     typedef float RedT[NT * MT][64][4];
@@ -149,6 +153,11 @@ __global__ __launch_bounds__(256) void vrt_head_kernel(HeadArgs p) {
         int bidx = 0x7fffffff;
         int lo = 0, hi = 0;
         if (m < p.B) { lo = p.vrt_off[m]; hi = p.vrt_off[m + 1]; }
+        int fcol = -1;                                            // PROBE: the column forced on sample m at this step
+        if constexpr (PROBE) {
+            const int st = *p.step;
+            if (m < p.B && st >= 0 && st < p.t_forced) fcol = p.forced[(long)m * p.t_forced + st];
+        }
         float vr[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -163,6 +172,9 @@ __global__ __launch_bounds__(256) void vrt_head_kernel(HeadArgs p) {
             if (pen != 1.0f && ok && ((p.seen[(long)m * p.seen_words + (row >> 5)] >> (row & 31)) & 1u)) sc = sc < 0.f ? sc * pen : sc / pen;
             const float v = ok ? sc : -INFINITY;
             if (p.logits && m < p.B && row < NTOT) p.logits[(long)m * p.ldl + row] = v;
+            if constexpr (PROBE) {
+                if (row == fcol && row < NTOT) p.probe_val[m] = v;   // fcol >= 0 only for m < B; one lane owns the column
+            }
             if (v > best) { best = v; bidx = row; }               // rows ascend with r → first max wins
             vr[r] = v;
         }
@@ -206,12 +218,18 @@ struct GreedyArgs {
     unsigned* seen; long seen_words;   // optional: bitmap of ids present in each row (repetition penalty), updated here
     const float* part_sum;    // LP: [nblk][B] Σ exp(v - block max) of the LSE head kernels
     float* logprobs;          // LP: [B][T_max] log-prob of the token each step selected
+    const int* forced; int t_forced;   // FORCED: [B][t_forced] the caller's tokens (table columns; < 0 = free step), read at *step
+    const float* probe;       // FORCED + LP: [B] the processed logit of the forced column (padt_vrt_head_probe)
+    int n_cols;               // FORCED: table columns; an entry outside [0, n_cols) is a free step
 };
 
 // LP (padt_greedy_step_lp): next to the arg-max, S = Σ_blk part_sum · exp(part_val - M) with M the global max — the row's Σ exp(logit - M) —
 // in a fixed order (the arg-max's strided block → thread map and LDS tree; an all-masked block adds an exact 0).  The selection IS the arg-max,
 // so log p(token) = -log S.  Rows finished on entry hold 0 (a completion's log-prob is then the row sum), a row without any candidate -inf.
-template <bool LP>
+// FORCED (padt_forced_step): an unfinished row whose entry forced[b][*step] is a table column takes it as its token whatever the scores say, a
+// -inf column included (the "no candidate → pad" branch is for free rows); with LP its log-prob is (probe - M) - log S, -inf for a -inf column —
+// when the forced column is the arg-max, probe == M, the difference is an exact 0 and the bits are those of the free step.
+template <bool LP, bool FORCED = false>
 __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyArgs p) {
     __shared__ float sv[256];
     __shared__ int si[256];
@@ -262,9 +280,20 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyArgs p) {
         // arg-max — bidx is still the sentinel; continue with the pad token so that every later index stays inside its table
         const bool no_choice = si[0] == 0x7fffffff || next < 0 || (p.seen && (next >> 5) >= p.seen_words);
         if (no_choice) next = (long)p.pad;
+        bool is_forced = false;
+        if constexpr (FORCED) {
+            if (unf && step >= 0 && step < p.t_forced) {
+                const int f = p.forced[(long)b * p.t_forced + step];
+                if (f >= 0 && f < p.n_cols) { is_forced = true; next = (long)f; }
+            }
+        }
         if (step < p.T_max) p.tokens_out[(long)b * p.T_max + step] = next;
         if constexpr (LP) {
-            if (step >= 0 && step < p.T_max) p.logprobs[(long)b * p.T_max + step] = !unf ? 0.f : no_choice ? -INFINITY : 0.f - logf(ss[0]);
+            float lp = !unf ? 0.f : no_choice ? -INFINITY : 0.f - logf(ss[0]);
+            if constexpr (FORCED) {
+                if (is_forced) { const float pr = p.probe[b]; lp = pr == -INFINITY ? -INFINITY : (pr - sv[0]) - logf(ss[0]); }
+            }
+            if (step >= 0 && step < p.T_max) p.logprobs[(long)b * p.T_max + step] = lp;
         }
         p.cur_tok[b] = next;
         bool is_eos = next == p.eos;
@@ -356,35 +385,36 @@ extern "C" int padt_gen_rules(void* stream, const int* rules, const int* hist, l
 }
 #endif
 
-template <int MT, int NT, bool PACKED, bool LSE>
+template <int MT, int NT, bool PACKED, bool LSE, bool PROBE>
 static void launch_head(const HeadArgs& a, int nblk, hipStream_t s) {
     constexpr int lds = 4 * NT * MT * 64 * 16;
     if constexpr (lds > 64 * 1024) {
         static PerDeviceOnce once;
-        once.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vrt_head_kernel<MT, NT, PACKED, LSE>),
+        once.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vrt_head_kernel<MT, NT, PACKED, LSE, PROBE>),
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
     }
-    hipLaunchKernelGGL((vrt_head_kernel<MT, NT, PACKED, LSE>), dim3((nblk + NT - 1) / NT), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((vrt_head_kernel<MT, NT, PACKED, LSE, PROBE>), dim3((nblk + NT - 1) / NT), dim3(256), lds, s, a);
 }
 
-template <bool LSE>
+template <bool LSE, bool PROBE = false>
 static void dispatch_head(const HeadArgs& a, int nblk, hipStream_t s) {
     if (a.Ep) {                                                 // NT = 4 table blocks per thread block (2 at 128 rows): profiles/r03_head_nt_ab.log
-        if (a.B <= 16) launch_head<1, 4, true, LSE>(a, nblk, s);
-        else if (a.B <= 32) launch_head<2, 4, true, LSE>(a, nblk, s);
-        else if (a.B <= 64) launch_head<4, 4, true, LSE>(a, nblk, s);
-        else launch_head<8, 2, true, LSE>(a, nblk, s);
-    } else if (a.B <= 16) launch_head<1, 1, false, LSE>(a, nblk, s);
-    else if (a.B <= 32) launch_head<2, 1, false, LSE>(a, nblk, s);
-    else if (a.B <= 64) launch_head<4, 1, false, LSE>(a, nblk, s);
-    else launch_head<8, 1, false, LSE>(a, nblk, s);
+        if (a.B <= 16) launch_head<1, 4, true, LSE, PROBE>(a, nblk, s);
+        else if (a.B <= 32) launch_head<2, 4, true, LSE, PROBE>(a, nblk, s);
+        else if (a.B <= 64) launch_head<4, 4, true, LSE, PROBE>(a, nblk, s);
+        else launch_head<8, 2, true, LSE, PROBE>(a, nblk, s);
+    } else if (a.B <= 16) launch_head<1, 1, false, LSE, PROBE>(a, nblk, s);
+    else if (a.B <= 32) launch_head<2, 1, false, LSE, PROBE>(a, nblk, s);
+    else if (a.B <= 64) launch_head<4, 1, false, LSE, PROBE>(a, nblk, s);
+    else launch_head<8, 1, false, LSE, PROBE>(a, nblk, s);
 }
 
 static int vrt_head_impl(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab,
                          const void* proto, long n_proto, const int* vrt_off, const int* mode_table,
                          const int* step, void* logits_f32, long ld_logits, void* part_val, void* part_idx,
                          long batch, long D, int eos, const void* embed_table_packed, const void* gen_cfg,
-                         const void* seen, long seen_words, const void* ban, long ban_words, void* part_sum = nullptr) {
+                         const void* seen, long seen_words, const void* ban, long ban_words, void* part_sum = nullptr,
+                         const int* forced = nullptr, long t_forced = 0, void* probe_val = nullptr) {
     if (batch <= 0) return 0;
     if (batch > 128 || (D & 7) || (ldh & 7)) { padt_set_error("padt_vrt_head: batch <= 128, D % 8 == 0 required"); return -1; }
     if (embed_table_packed && ((D & 31) || (vocab & 15) || ((uintptr_t)embed_table_packed & 15) || ((uintptr_t)hidden & 15))) {
@@ -394,12 +424,13 @@ static int vrt_head_impl(void* stream, const void* hidden, long ldh, const void*
     HeadArgs a{(const x16_t*)hidden, ldh, (const x16_t*)embed_table, (int)vocab, (const x16_t*)proto, (int)n_proto,
                vrt_off, mode_table, step, (float*)logits_f32, ld_logits, (float*)part_val, (int*)part_idx, (int)batch,
                (int)D, eos, (const x16_t*)embed_table_packed, (const GenCfg*)gen_cfg, (const unsigned*)seen, seen_words,
-               (const unsigned*)ban, ban_words, (float*)part_sum};
+               (const unsigned*)ban, ban_words, (float*)part_sum, forced, (int)t_forced, (float*)probe_val};
     if (seen && seen_words * 32 < vocab + n_proto) { padt_set_error("padt_vrt_head: seen bitmap narrower than the table"); return -1; }
     if (ban && ban_words * 32 < vocab + n_proto) { padt_set_error("padt_vrt_head_ban: ban bitmap narrower than the table"); return -1; }
     const int nblk = (int)padt_vrt_head_nblk(vocab, n_proto);
     hipStream_t s = (hipStream_t)stream;
-    if (part_sum) dispatch_head<true>(a, nblk, s);
+    if (forced) dispatch_head<true, true>(a, nblk, s);
+    else if (part_sum) dispatch_head<true>(a, nblk, s);
     else dispatch_head<false>(a, nblk, s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
@@ -437,6 +468,25 @@ extern "C" int PADT_TWIN(padt_vrt_head_lse)(void* stream, const void* hidden, lo
     if (batch > 0 && part_sum == nullptr) { padt_set_error("padt_vrt_head_lse: part_sum is required"); return -1; }
     return vrt_head_impl(stream, hidden, ldh, embed_table, vocab, proto, n_proto, vrt_off, mode_table, step, logits_f32, ld_logits, part_val,
                          part_idx, batch, D, eos, embed_table_packed, gen_cfg, seen, seen_words, ban, ban_words, part_sum);
+}
+
+// padt_vrt_head_lse that also writes probe_val[b] = the processed logit (what `logits` gets: masked, penalised, ban-filtered) of column
+// forced[b][*step] of the int32 table forced [batch][t_forced] — generate(forced_tokens=): with padt_forced_step, the log-prob of a token the
+// caller chose.  A negative entry, or *step outside [0, t_forced), writes nothing; entries must be < vocab + n_proto.  Partials, part_sum and any
+// written logits are those of padt_vrt_head_lse, bit for bit.
+extern "C" int PADT_TWIN(padt_vrt_head_probe)(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab,
+                             const void* proto, long n_proto, const int* vrt_off, const int* mode_table,
+                             const int* step, void* logits_f32, long ld_logits, void* part_val, void* part_idx,
+                             long batch, long D, int eos, const void* embed_table_packed, const void* gen_cfg,
+                             const void* seen, long seen_words, const void* ban, long ban_words, void* part_sum,
+                             const int* forced, long t_forced, void* probe_val) {
+    if (batch <= 0) return 0;
+    if (part_sum == nullptr || forced == nullptr || probe_val == nullptr || step == nullptr || t_forced <= 0 || t_forced > 0x7fffffffL) {
+        padt_set_error("padt_vrt_head_probe: part_sum, the step counter, the forced table [batch][t_forced] and probe_val are required"); return -1;
+    }
+    return vrt_head_impl(stream, hidden, ldh, embed_table, vocab, proto, n_proto, vrt_off, mode_table, step, logits_f32, ld_logits, part_val,
+                         part_idx, batch, D, eos, embed_table_packed, gen_cfg, seen, seen_words, ban, ban_words, part_sum, forced, t_forced,
+                         probe_val);
 }
 
 #if !PADT_OP16_F16   // type-independent: compiled once
@@ -477,6 +527,65 @@ extern "C" int padt_greedy_step_lp(void* stream, const void* part_val, const voi
     return 0;
 }
 
+// padt_greedy_step / padt_greedy_step_lp with a table of tokens the caller forces (generate(forced_tokens=)): forced int32 [batch][t_forced] in
+// table columns.  After the arg-max (and the LSE fold), an unfinished row b with 0 <= forced[b][*step] < n_cols and 0 <= *step < t_forced takes
+// that column as its token — appended, fed to the next step, entered in `seen`, checked against the EOS ids — even where its score is -inf; every
+// other row is the free step.  part_sum / logprobs / probe_val (padt_vrt_head_probe's; all three or none): logprobs[b][*step] =
+// probe == -inf ? -inf : (probe - max) - log Σ for a forced row, padt_greedy_step_lp's value elsewhere.
+extern "C" int padt_forced_step(void* stream, const void* part_val, const void* part_idx, long nblk, long batch, long D,
+                                int eos, int pad, long t_max, int* unfinished, long* tokens_out, long* cur_tok,
+                                int* step, int* slot, int* lens, int* pos3, const void* hidden, void* hidden_buf,
+                                int advance, const void* gen_cfg, void* seen, long seen_words, const void* part_sum, void* logprobs,
+                                const int* forced, long t_forced, const void* probe_val, long n_cols) {
+    if (batch <= 0) return 0;
+    if (D & 7) { padt_set_error("padt_forced_step: D % 8 == 0 required"); return -1; }
+    if (forced == nullptr || t_forced <= 0 || t_forced > 0x7fffffffL || n_cols <= 0 || n_cols > 0x7fffffffL || step == nullptr) {
+        padt_set_error("padt_forced_step: the forced table [batch][t_forced], the step counter and the table's column count are required"); return -1;
+    }
+    const bool lp = part_sum != nullptr || logprobs != nullptr || probe_val != nullptr;
+    if (lp && (part_sum == nullptr || logprobs == nullptr || probe_val == nullptr)) {
+        padt_set_error("padt_forced_step: part_sum, logprobs and probe_val go together"); return -1;
+    }
+    if (seen && seen_words * 32 < n_cols) { padt_set_error("padt_forced_step: seen bitmap narrower than the table"); return -1; }
+    GreedyArgs a{(const float*)part_val, (const int*)part_idx, (int)nblk, (int)batch, (int)D, eos, pad, (int)t_max,
+                 unfinished, tokens_out, cur_tok, step, slot, lens, pos3, (const x16_t*)hidden, (x16_t*)hidden_buf,
+                 advance, (const GenCfg*)gen_cfg, (unsigned*)seen, seen_words, (const float*)part_sum, (float*)logprobs,
+                 forced, (int)t_forced, (const float*)probe_val, (int)n_cols};
+    hipStream_t s = (hipStream_t)stream;
+    if (lp) hipLaunchKernelGGL((greedy_step_kernel<true, true>), dim3((unsigned)batch), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((greedy_step_kernel<false, true>), dim3((unsigned)batch), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, s, step);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    return 0;
+}
+
+// Row path of generate(forced_tokens=) (the token comes from padt_sample_token / padt_warp_sample_rows_f32 / padt_argmax_rows_f32, not from the
+// head's partials): part_idx[b] = forced[b][*step] for every unfinished row whose entry is a table column, so that padt_token_logprob_rows_f32
+// scores the forced column; free and finished rows keep their draw / arg-max.
+__global__ void forced_override_kernel(int* __restrict__ part_idx, const int* __restrict__ forced, int t_forced, const int* __restrict__ step,
+                                       const int* __restrict__ unfinished, int n_cols, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    const int st = *step;
+    if (b >= B || st < 0 || st >= t_forced || !unfinished[b]) return;
+    const int f = forced[(long)b * t_forced + st];
+    if (f >= 0 && f < n_cols) part_idx[b] = f;
+}
+
+extern "C" int padt_forced_override(void* stream, void* part_idx, const int* forced, long t_forced, const int* step, const int* unfinished,
+                                    long n_cols, long batch) {
+    if (batch <= 0) return 0;
+    if (part_idx == nullptr || forced == nullptr || step == nullptr || unfinished == nullptr || t_forced <= 0 || t_forced > 0x7fffffffL ||
+        n_cols <= 0 || n_cols > 0x7fffffffL || batch > 0x7fffffffL) {
+        padt_set_error("padt_forced_override: the selection, the forced table [batch][t_forced], the step counter, the unfinished flags and the "
+                       "table's column count are required"); return -1;
+    }
+    hipLaunchKernelGGL(forced_override_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int*)part_idx, forced,
+                       (int)t_forced, step, unfinished, (int)n_cols, (int)batch);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    return 0;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Sampling branch of the loop (padt.py:740-743: probs = softmax(next_token_scores); next = multinomial(probs, 1)) with HF's

@@ -3,7 +3,7 @@ arguments are ignored, refused or unknown), ``GenOptions`` — the ONE named, ha
 generation_config.json resolve to, carried from ``generate_launch`` through the decode session to a re-run on the bf16 twin — and
 ``StepMode``, the part of it that selects the decode step's kernel sequence (one captured graph per value)."""
 import numbers
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass, fields
 from typing import NamedTuple, Optional
 
 import torch
@@ -75,6 +75,80 @@ def check_top_logprobs(top_logprobs) -> int:
         raise NotImplementedError(f"generate(top_logprobs={int(top_logprobs)}): at most top_logprobs={TOP_LOGPROBS_MAX} candidates per step are "
                                   "selected on the device — ask for output_scores=True and reduce the rows yourself beyond that")
     return int(top_logprobs)
+
+
+# ------------------------------------------------------------------------------------------------ generate(forced_tokens=)
+def check_forced_tokens(forced_tokens, B, max_new_tokens, vocab_size, patches_per_row=None) -> torch.Tensor:
+    """generate(forced_tokens=F) → the table in its one normal form: an int32 CPU tensor (B, n), n <= max_new_tokens, every free entry -1.
+    F: a (B, n) integer tensor or a list of B lists of ints (ragged rows are padded with -1); ids are numbered like ``sequences[:, L:]``
+    (text ids < vocab_size, sample b's own VRT ids vocab_size + its patch offset in the batch).  ValueError naming ``forced_tokens`` for a
+    wrong batch size, n > max_new_tokens, a non-integer dtype, or an id >= vocab_size + patches_per_row[b] (patches_per_row: the table rows
+    past the text vocabulary that row b may name, i.e. the batch's prototype count; None skips that bound) — so the device never sees an id
+    outside the table."""
+    name = "generate(forced_tokens=...)"
+    if isinstance(forced_tokens, torch.Tensor):
+        t = forced_tokens.detach().cpu()
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+            raise ValueError(f"{name}: an integer tensor is required, got dtype {t.dtype}")
+        if t.dim() != 2:
+            raise ValueError(f"{name}: a (batch, n) tensor is required, got shape {tuple(t.shape)}")
+        t = t.to(torch.int64)
+    else:
+        try:
+            rows = [list(r) for r in forced_tokens]
+        except TypeError:
+            raise ValueError(f"{name}: a (batch, n) integer tensor or a list of per-row id lists is required, got {forced_tokens!r}") from None
+        n = max((len(r) for r in rows), default=0)
+        t = torch.full((len(rows), n), -1, dtype=torch.int64)
+        for b, r in enumerate(rows):
+            for j, v in enumerate(r):
+                if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                    if isinstance(v, torch.Tensor) and v.numel() == 1 and not (v.dtype.is_floating_point or v.dtype == torch.bool):
+                        v = int(v)
+                    else:
+                        raise ValueError(f"{name}: token ids must be integers, got {v!r} (row {b})")
+                t[b, j] = int(v)
+    if t.shape[0] != int(B):
+        raise ValueError(f"{name}: {t.shape[0]} rows for a batch of {int(B)} samples")
+    if t.shape[1] > int(max_new_tokens):
+        raise ValueError(f"{name}: {t.shape[1]} steps but max_new_tokens={int(max_new_tokens)}")
+    t = torch.where(t < 0, torch.full_like(t, -1), t)
+    if patches_per_row is None:
+        limit = torch.full((t.shape[0], 1), 2 ** 31 - 1, dtype=torch.int64)
+    else:
+        if len(patches_per_row) != t.shape[0]:
+            raise ValueError(f"{name}: patches_per_row has {len(patches_per_row)} entries for {t.shape[0]} rows")
+        limit = (torch.as_tensor([int(p) for p in patches_per_row], dtype=torch.int64) + int(vocab_size))[:, None]
+    bad = (t >= limit).nonzero()
+    if bad.numel():
+        b, j = (int(x) for x in bad[0])
+        raise ValueError(f"{name}: id {int(t[b, j])} at row {b}, step {j} is outside the table ({int(limit[b if limit.shape[0] > 1 else 0, 0])} rows: "
+                         "the text vocabulary and the batch's patches)")
+    return t.to(torch.int32)
+
+
+def forced_tokens_active(table) -> bool:
+    """False for an absent, empty or all-free (-1) table: such a call IS the call without the argument — same options, same captured graph."""
+    return table is not None and table.numel() > 0 and bool((table >= 0).any())
+
+
+def completion_logprobs(token_logprobs: torch.Tensor, tokens: torch.Tensor, forced: torch.Tensor, eos_ids):
+    """score_completions' masking, pure: → (completion_token_logprobs, completion_logprobs).  token_logprobs / tokens (B, n_steps): a forced
+    generate's fields (tokens = sequences[:, L:]); forced: the normalised table (B, n) of check_forced_tokens.  An entry keeps its value where
+    the step was forced (forced[b, t] >= 0, t < n) and no earlier token of the row is one of eos_ids (the EOS step itself counts); every other
+    entry is 0.0.  The sums are over the kept entries, so a -inf log-prob makes the completion's -inf."""
+    B, T = token_logprobs.shape
+    f = torch.full((B, T), -1, dtype=torch.int64)
+    n = min(T, forced.shape[1])
+    f[:, :n] = forced[:, :n].to(torch.int64).cpu()
+    tok = tokens.detach().cpu().to(torch.int64)
+    is_eos = torch.zeros_like(tok, dtype=torch.bool)
+    for e in eos_ids:
+        is_eos |= tok == int(e)
+    after = (is_eos.long().cumsum(1) - is_eos.long()) > 0
+    keep = ((f >= 0) & ~after).to(token_logprobs.device)
+    per = torch.where(keep, token_logprobs, torch.zeros_like(token_logprobs))
+    return per, per.sum(1)
 
 
 # generate()'s named parameters a generation_config may carry: an explicit argument (not None) wins, as in HF (padt.py:436)
@@ -163,6 +237,7 @@ class StepMode(NamedTuple):
     processors: bool = False         # the caller's logits_processor rewrites the rows (hooked loop: never captured)
     reference: bool = False          # precision="reference": reference.ReferencePath.step instead of step_kernels
     warpers: bool = False            # min_p / typical_p / epsilon_cutoff / eta_cutoff: padt_warp_sample_rows_f32 warps the row and draws
+    forced: bool = False             # generate(forced_tokens=): the probe head / padt_forced_step / padt_forced_override read the session's table
 
 
 @dataclass(frozen=True)
@@ -177,6 +252,27 @@ class GenOptions:
     token_logprobs: bool = False
     top_logprobs: int = 0                        # k; 0: off
     patch_logprobs: bool = False
+    # generate(forced_tokens=): the batch forces tokens.  The table itself is per-batch data like the prompt history; this only says that the
+    # step reads one.  Set with dataclasses.replace after resolve_options; part of equality (batches share a decode group only when both force
+    # or neither does) but deliberately NOT a dataclass field: the fields are the options generate_kwargs() spells as generate() arguments for a
+    # re-run, and the table travels with its batch instead (modeling._non_finite_batch).
+    forced: InitVar[bool] = False
+
+    def __post_init__(self, forced):
+        object.__setattr__(self, "forced", bool(forced))
+
+    def _key(self):
+        return tuple(getattr(self, f.name) for f in fields(self)) + (self.forced,)      # every field, whatever is added later, and the flag
+
+    def __eq__(self, other):
+        return self._key() == other._key() if isinstance(other, GenOptions) else NotImplemented
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        args = [f"{f.name}={getattr(self, f.name)!r}" for f in fields(self)] + [f"forced={self.forced!r}"]
+        return f"GenOptions({', '.join(args)})"
 
     @property
     def want_rows(self) -> bool:
@@ -203,7 +299,7 @@ class GenOptions:
     def step_mode(self, processors: bool = False, reference: bool = False) -> StepMode:
         return StepMode(sampling=self.sampling is not None, keep_scores=self.keep_scores, keep_logits=self.keep_logits, rules=self.rules is not None,
                         token_logprobs=self.token_logprobs, top_k=self.top_logprobs, patches=self.patch_logprobs, processors=bool(processors),
-                        reference=bool(reference), warpers=self.sampling is not None and self.sampling.warpers)
+                        reference=bool(reference), warpers=self.sampling is not None and self.sampling.warpers, forced=self.forced)
 
     def warper_kwargs(self) -> dict:
         """min_p / typical_p / epsilon_cutoff / eta_cutoff as explicit generate() keywords (with_warpers values), next to generate_kwargs():

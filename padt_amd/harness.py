@@ -8,7 +8,8 @@ post-processing (utils.py:252-266) and the two JSONL files with the reference's 
 Tokenisation / chat templating is the caller's (`prepare`): it needs the checkpoint's tokenizer files, which are not part of
 this repository.  `prepare(samples) -> dict(input_ids (local VRT ids), attention_mask, pixel_values, image_grid_thw,
 image_sizes [(w, h)], ids [image_id])`; optionally `image_index` (several samples on one image: generate(image_index=), with
-`pixel_values` / `image_grid_thw` holding each image once).
+`pixel_values` / `image_grid_thw` holding each image once) and `forced_tokens` (the batch's completion tokens to force:
+generate(forced_tokens=)).
 """
 import json
 import os
@@ -52,6 +53,7 @@ def infer_dataset(model, processor, dataset: Sequence, prepare: Callable, output
         b = prepare(dataset[idx: idx + batch_size])
         meta.append({"ids": list(b["ids"]), "image_sizes": list(b["image_sizes"])})
         extra = {"image_index": b["image_index"]} if b.get("image_index") is not None else {}
+        extra["forced_tokens"] = b.get("forced_tokens")           # None: nothing forced
         drain(runner.submit(b["input_ids"], b["attention_mask"], b["pixel_values"], b["image_grid_thw"],
                             max_new_tokens=max_new_tokens, schedule=schedule, repetition_penalty=repetition_penalty,
                             eos_token_id=eos_token_id, **extra))

@@ -357,6 +357,7 @@ class DecodeSession:
         self.summary_host = torch.zeros(2 + 3 * B, dtype=I32).pin_memory() if torch.device(device).type == "cuda" else torch.zeros(2 + 3 * B, dtype=I32)
         # what this generate's step launches and keeps (generation.StepMode, set by begin()); the buffers below are allocated on first use
         self.mode = StepMode()
+        self.eos_ids = (int(cfg.eos_token_id),)   # the ids that finish a row in this generate: the config's and the resolved options' (begin())
         self.scores = None               # mode.keep_scores (output_scores=True): every step's masked fp32 logit rows [t_max][B][W]
         self.raw_scores = None           # mode.keep_logits (output_logits=True under sampling): the rows before the warpers [t_max][B][W]
         self.part_sum = None             # mode.token_logprobs: the head's per-block Σ exp(logit - block max) [nblk][B] (fused path) ...
@@ -366,6 +367,8 @@ class DecodeSession:
         self.p_cap = 0                   # mode.patches (output_patch_logprobs=True): every sample's own patch columns in `patch_lp` [B][t_max][p_cap]
         self.patch_lp = None
         self.topk_ws = None              # padt_topk_logprob_rows_f32's chunk workspace, sized for k = 32
+        self.forced = None               # mode.forced (generate(forced_tokens=)): [B][t_max] int32 table columns in session numbering, -1 = free ...
+        self.probe_val = None            # ... and the probe head's processed logit of each row's forced column [B]
         self.rope_cs = z(B, hd // 2, 2, dt=torch.float32)
         self.n_qkv = (cfg.num_attention_heads + 2 * Hkv) * hd
         self.graphs = {}                 # captured decode-step graph per mode (different kernel sequences and output buffers)
@@ -421,6 +424,7 @@ class DecodeSession:
         dev = self.part_val.device
         self.gen_cfg.copy_(opts.gen_cfg().to(dev, non_blocking=True))
         self.mode, self.step_fn, self.hooks = opts.step_mode(processors, step_fn is not None), step_fn, None
+        self.eos_ids = tuple(dict.fromkeys((int(self.cfg.eos_token_id),) + tuple(opts.eos_ids)))      # every id that finishes a row on the device
         if opts.token_logprobs:
             if self.logprobs is None:
                 self.part_sum = torch.zeros(self.nblk * self.B, device=dev, dtype=torch.float32)
@@ -446,6 +450,11 @@ class DecodeSession:
                 self.p_cap = max(int(p_max), 1)
                 self.patch_lp = torch.empty((self.B, self.t_max, self.p_cap), device=dev, dtype=torch.float32)
             self.patch_lp.fill_(float("-inf"))
+        if opts.forced:                                          # every row free; each batch of the group fills its own rows (modeling._launch)
+            if self.forced is None:
+                self.forced = torch.empty((self.B, self.t_max), device=dev, dtype=I32)
+                self.probe_val = torch.zeros(self.B, device=dev, dtype=torch.float32)
+            self.forced.fill_(-1)
         if opts.rules is not None:
             self.rules.copy_(ops.gen_rules_tensor(key=opts.rules).to(dev, non_blocking=True))
             self.hist_len.zero_()                                # rows no batch of the group fills: an empty prompt
@@ -467,14 +476,19 @@ class DecodeSession:
         ban = None
         if m.rules:                                          # this step's ban bitmap from the rows' histories; the head then writes -inf there
             ban = ops.gen_rules(self.rules, self.hist, self.hist_len, self.tokens, self.step, self.ban, cfg.vocab_size + self.np_max)
+        # forced tokens (generate(forced_tokens=)): the caller's table decides the token of a forced row.  Fused log-probs: the probe head leaves
+        # the processed logit of the forced column next to the LSE partials; without log-probs the plain head runs and only the bookkeeping differs
+        fc = self.forced if m.forced else None
+        probe = self.probe_val if (fc is not None and psum is not None) else None
+        head_in, head_kw = hn, dict(mode_table=self.mode_table, step=self.step, gen_cfg=self.gen_cfg, seen=self.seen, logits=lg, ban=ban)
         if hp is not None:                                   # packed table + packed hidden rows: 1 KiB contiguous wave loads
             ops.pack_rows(hn, self.hn_pk, self.B, to_packed=True)
-            ops.vrt_head(self.hn_pk, W["llm.head"], self.proto, self.vrt_off, self.part_val, self.part_idx, cfg.eos_token_id,
-                         mode_table=self.mode_table, step=self.step, table_packed=hp, rows=self.B, gen_cfg=self.gen_cfg,
-                         seen=self.seen, logits=lg, ban=ban, part_sum=psum)
+            head_in, head_kw = self.hn_pk, dict(head_kw, table_packed=hp, rows=self.B)
+        if probe is not None:
+            ops.vrt_head_probe(head_in, W["llm.head"], self.proto, self.vrt_off, self.part_val, self.part_idx, cfg.eos_token_id, psum, fc, probe,
+                               **head_kw)
         else:
-            ops.vrt_head(hn, W["llm.head"], self.proto, self.vrt_off, self.part_val, self.part_idx, cfg.eos_token_id,
-                         mode_table=self.mode_table, step=self.step, gen_cfg=self.gen_cfg, seen=self.seen, logits=lg, ban=ban, part_sum=psum)
+            ops.vrt_head(head_in, W["llm.head"], self.proto, self.vrt_off, self.part_val, self.part_idx, cfg.eos_token_id, part_sum=psum, **head_kw)
         if m.processors:
             # padt.py:717 `next_token_scores = logits_processor(input_ids, next_token_logits)` with the CALLER's processors: they see the rows the head
             # wrote (logit mask + the built-in processors applied) and the sequences so far, and what they return is what is scored / selected / kept
@@ -507,15 +521,23 @@ class DecodeSession:
         elif m.processors:                                   # the head's fused arg-max partials describe the rows BEFORE the caller's processors
             ops.argmax_rows(lg, cfg.vocab_size + self.np_max, self.part_val, self.part_idx, self.B)
             nblk = 1
+        if fc is not None and (m.sampling or m.processors):                   # the draw / arg-max of a forced row gives way to the caller's token: scored and appended below
+            ops.forced_override(self.part_idx, fc, self.step, self.unfinished, cfg.vocab_size + self.np_max, self.B)
         if lp_rows:                                          # before greedy_step clears `unfinished` and bumps the step counter
             ops.token_logprob_rows(lg, cfg.vocab_size + self.np_max, self.part_idx, self.unfinished, self.step, self.logprobs, self.B)
         if top_on:                                           # the row as selected from (warped under sampling: write_back), `unfinished` as on entry
             ops.topk_logprob_rows(lg, cfg.vocab_size + self.np_max, self.unfinished, self.step, self.topk_ws, self.B, top_idx=self.top_idx,
                                   top_val=self.top_val, vrt_off=self.vrt_off if m.patches else None, vocab=cfg.vocab_size,
                                   patch_lp=self.patch_lp if m.patches else None)
-        ops.greedy_step(self.part_val, self.part_idx, nblk, hn, self.hidden_buf, self.unfinished, self.tokens,
-                        self.cur_tok, self.step, self.slot, self.lens, self.pos3, cfg.eos_token_id, cfg.pad_token_id,
-                        advance=advance, gen_cfg=self.gen_cfg, seen=self.seen, part_sum=psum, logprobs=lp_out)
+        if fc is not None:
+            ops.forced_step(self.part_val, self.part_idx, nblk, hn, self.hidden_buf, self.unfinished, self.tokens,
+                            self.cur_tok, self.step, self.slot, self.lens, self.pos3, cfg.eos_token_id, cfg.pad_token_id, fc,
+                            cfg.vocab_size + self.np_max, advance=advance, gen_cfg=self.gen_cfg, seen=self.seen, part_sum=psum, logprobs=lp_out,
+                            probe_val=probe)
+        else:
+            ops.greedy_step(self.part_val, self.part_idx, nblk, hn, self.hidden_buf, self.unfinished, self.tokens,
+                            self.cur_tok, self.step, self.slot, self.lens, self.pos3, cfg.eos_token_id, cfg.pad_token_id,
+                            advance=advance, gen_cfg=self.gen_cfg, seen=self.seen, part_sum=psum, logprobs=lp_out)
         if hk is not None:
             hk["t"] += 1
             if hk["criteria"]:

@@ -10,6 +10,7 @@ output_hidden_states=True, return_dict_in_generate=True[, synced_gpus=False])`` 
 There is no HuggingFace modeling code and no PyTorch compute on this path: the methods sequence kernels from
 libpadt_hip.so (see vision.py / llm.py / decoder.py) and fail loudly if that library is missing.
 """
+import dataclasses
 import json
 import os
 from types import SimpleNamespace
@@ -20,8 +21,8 @@ import torch
 from . import _lib, ops
 from .config import PaDTConfig
 from .decoder import PaDTDecoder
-from .generation import (_GENERATE_CONFIG_NAMED, _GENERATE_CONFIG_OWN, check_generate_kwargs, check_top_logprobs,  # noqa: F401
-                         generation_config_fields, resolve_options, with_warpers, WARPER_NAMES)
+from .generation import (_GENERATE_CONFIG_NAMED, _GENERATE_CONFIG_OWN, check_forced_tokens, check_generate_kwargs, check_top_logprobs,  # noqa: F401
+                         completion_logprobs, forced_tokens_active, generation_config_fields, resolve_options, with_warpers, WARPER_NAMES)
 from .llm import MODE, LanguageModel, check_shared_destinations, plan_prompt, plan_prompt_shared
 from .vision import VisionEncoder
 from .weights import Fp16RangeError, load_checkpoint_state_dict, prepare_weights, synthetic_state_dict
@@ -319,12 +320,25 @@ class PaDTForConditionalGeneration:
         generation_config / ``generation_config=``, ``ValueError`` naming the argument outside the range, ignored under greedy decoding as
         in HF.  ``.scores``, ``token_logprobs``, ``top_logprobs`` / ``patch_logprobs`` and stopping criteria see the fully warped row.  A value
         HF builds no warper for is the same call as without the argument: same kernels, same decode group.
+        Keyword ``forced_tokens=F`` (a (B, n) integer tensor or a list of B id lists, n <= max_new_tokens; ids numbered like
+        ``sequences[:, L:]``): the caller's completion, forced INSIDE the decode loop.  Where ``F[b, t] >= 0`` and row b is unfinished, step
+        t's token IS ``F[b, t]`` whatever the scores say — appended, fed to the next step, entered into the repetition penalty's and the
+        n-gram ban's history, finishing the row when it is an EOS id; a negative entry, a ragged row's missing entries and every step past n
+        are free steps (the arg-max, or the draw — the generator is counter-based, so free steps draw what they would have drawn).  The scores
+        are untouched: ``.scores``, ``top_token_ids`` / ``top_logprobs`` and ``patch_logprobs`` describe the step's processed row as before,
+        ``token_logprobs[b, t]`` is its log-softmax AT THE FORCED TOKEN (``-inf``, never NaN, for a token the mask, a ban or the ``schedule``
+        removed — it is still forced), and ``hidden_states`` hold the row that predicted each step, so ``parseVRTintoCompletion`` +
+        ``vl_decode`` decode forced VRT tokens.  Forcing a run's own output reproduces it bit for bit.  ``ValueError`` naming the argument for a
+        wrong batch size, n > max_new_tokens, a non-integer dtype or an id outside the table; an all-free table is the call without the
+        argument.  It is NOT HF's ``forced_decoder_ids`` / ``forced_eos_token_id`` and NOT ``labels``: no prompt-pass scorer, no loss
+        (``forward(is_main=True)`` keeps raising).  ``score_completions`` names the scoring use.
         """
         if synced_gpus:
             raise NotImplementedError("generate(synced_gpus=True) is the ZeRO-3 / FSDP lock-step loop (padt.py:445,670): every rank holds a full "
                                       "replica on this path — pass synced_gpus=False")
         # HF's warpers after top-p are keywords of this call (not named parameters: the parameter list is frozen)
         min_p, typical_p, epsilon_cutoff, eta_cutoff = (kwargs.pop(k, None) for k in WARPER_NAMES)
+        forced_tokens = kwargs.pop("forced_tokens", None)             # ... and so is the table of forced completion tokens
         if generation_config is not None:
             named = dict(max_new_tokens=max_new_tokens, max_length=max_length, do_sample=do_sample, repetition_penalty=repetition_penalty,
                          eos_token_id=eos_token_id, pad_token_id=pad_token_id, temperature=temperature, top_k=top_k, top_p=top_p,
@@ -363,6 +377,8 @@ class PaDTForConditionalGeneration:
         warpers = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
         if any(v is not None for v in warpers.values()):
             hooks = dict(hooks or {}, warpers=warpers)                # generate_launch's channel for them (see there)
+        if forced_tokens is not None:
+            hooks = dict(hooks or {}, forced=forced_tokens)           # the same channel
         if output_logits:
             pen = self.generation_config.repetition_penalty if repetition_penalty is None else repetition_penalty
             if float(pen) != 1.0 or schedule is not None or processors is not None:
@@ -404,7 +420,8 @@ class PaDTForConditionalGeneration:
 
         ``hooks``: generate()'s caller processors / stopping criteria (``processors``, ``criteria``, ``pass_scores``) and / or the call's warpers
         after top-p, ``hooks=dict(warpers=dict(min_p=..., typical_p=..., epsilon_cutoff=..., eta_cutoff=...))`` (None entries: the
-        generation config decides); warpers alone keep the captured step and merged groups.
+        generation config decides); warpers alone keep the captured step and merged groups.  ``hooks=dict(forced=F)``: generate()'s
+        ``forced_tokens`` — per-batch data like the prompt; batches share a group only when both force or neither does.
         """
         # a call's min_p / typical_p / epsilon_cutoff / eta_cutoff arrive as hooks["warpers"] (this method's parameter list is frozen) and are put
         # in front of the generation config's; what is left of `hooks` is the caller's processors / criteria, or nothing
@@ -412,6 +429,11 @@ class PaDTForConditionalGeneration:
         if hooks is not None and "warpers" in hooks:
             gen_cfg = with_warpers(gen_cfg, hooks["warpers"])
             hooks = {k: v for k, v in hooks.items() if k != "warpers"} or None
+        forced = None
+        if hooks is not None and "forced" in hooks:
+            if hooks["forced"] is not None:                       # shape / dtype now; the id bound once the batch's patch count is known (_launch)
+                forced = check_forced_tokens(hooks["forced"], input_ids.shape[0], max_new_tokens, self.config.vocab_size)
+            hooks = {k: v for k, v in hooks.items() if k != "forced"} or None
         if image_index is not None and getattr(self, "precision", "default") == "reference":
             raise NotImplementedError("generate(image_index=...) is not implemented with precision='reference' (its prompt pass is its own: "
                                       "reference.ReferencePath.prefill): expand the inputs or use precision='default'")
@@ -423,12 +445,16 @@ class PaDTForConditionalGeneration:
                                seed=seed, keep_scores=keep_scores, keep_logits=keep_logits, no_repeat_ngram_size=no_repeat_ngram_size,
                                bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
                                output_token_logprobs=output_token_logprobs, top_logprobs=top_logprobs, output_patch_logprobs=output_patch_logprobs)
+        if forced_tokens_active(forced):
+            opts = dataclasses.replace(opts, forced=True)
+        else:
+            forced = None                                         # an all-free table: the call without the argument
         return owner._launch(opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, max_new_tokens=max_new_tokens,
                              schedule=schedule, hooks=hooks, sync_every=sync_every, use_graph=use_graph, lane=lane, decode_stream=decode_stream,
-                             group=group, n_slots=n_slots, vit_stream=vit_stream, inputs_ready=inputs_ready)
+                             group=group, n_slots=n_slots, vit_stream=vit_stream, inputs_ready=inputs_ready, forced=forced)
 
     def _launch(self, opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, *, max_new_tokens, schedule, hooks, sync_every,
-                use_graph, lane, decode_stream, group, n_slots, vit_stream, inputs_ready):
+                use_graph, lane, decode_stream, group, n_slots, vit_stream, inputs_ready, forced=None):
         """generate_launch on the group's owner, with the call's options resolved (generation.GenOptions)."""
         self._batches_seen += 1
         if pixel_values is None or image_grid_thw is None:
@@ -449,6 +475,8 @@ class PaDTForConditionalGeneration:
         n_proto = plan.vrt_off[-1]
         p_max = max(plan.vrt_off[i + 1] - plan.vrt_off[i] for i in range(B))      # output_patch_logprobs: the widest sample of this batch
         need_s = max(plan.lens) + T_max
+        if forced is not None:                                    # ids are the batch's own numbering: text ids and its n_proto patch rows
+            forced = check_forced_tokens(forced, B, T_max, cfg.vocab_size, [n_proto] * B)
         if opts.rules is not None:
             need_s = max(need_s, plan.L_pad)                      # the session's history rows hold the padded prompt row
         if hooks is not None and (group is not None or n_slots != 1):
@@ -553,6 +581,10 @@ class PaDTForConditionalGeneration:
         if opts.rules is not None:
             sess.hist[rows, : plan.L_pad].copy_(ids_full)         # int64 → int32 (ids are table rows)
             sess.hist_len[rows].fill_(plan.L_pad)
+        if forced is not None:
+            # this batch's rows of the session's table, in session numbering like the prompt history; the steps past n stay free (-1: begin())
+            tab = torch.where(forced >= cfg.vocab_size, forced + proto_row0, forced) if proto_row0 else forced
+            sess.forced[rows, : tab.shape[1]].copy_(tab.to(dev, non_blocking=True))
 
         # ---- prefill; the first token is selected together with the other batches of the group (launch_decode)
         if self.ref is not None:
@@ -563,7 +595,7 @@ class PaDTForConditionalGeneration:
             hn_all = self.lm.prefill(plan, low, sess, nf=nf)
             ops.gather_rows(hn_all, plan.last_idx, out=sess.hn_first[rows])
         group["subs"].append(dict(plan=plan, low=low, high=high, pe=pe, proto=proto, hn_all=hn_all, input_ids=input_ids,
-                                  n_proto=n_proto, row0=row0, proto_row0=proto_row0, nf=nf, p_max=p_max,
+                                  n_proto=n_proto, row0=row0, proto_row0=proto_row0, nf=nf, p_max=p_max, forced=forced,
                                   inputs=(attention_mask, pixel_values, image_grid_thw, image_index)))       # what a re-run on the bf16 twin needs
         group["proto_rows"] = proto_row0 + n_proto
         if len(group["subs"]) == group["n_slots"]:
@@ -704,9 +736,31 @@ class PaDTForConditionalGeneration:
         kw = dict(group["opts"].generate_kwargs(), **group["opts"].warper_kwargs(), output_scores=output_scores, output_logits=output_logits)
         if group.get("hooks") is not None:
             kw.update(logits_processor=group["hooks"]["processors"], stopping_criteria=group["hooks"]["criteria"])
+        if sub.get("forced") is not None:
+            kw.update(forced_tokens=sub["forced"])                # the caller's table, in the batch's own numbering
         return fb.generate(input_ids=sub["input_ids"], attention_mask=am, pixel_values=pix, image_grid_thw=grid, max_new_tokens=group["T_max"],
                            schedule=group["schedule"], sync_every=group["sync_every"], use_graph=group["use_graph"], lane=("fb", group["lane"]),
                            output_hidden_states=output_hidden_states, return_dict_in_generate=return_dict_in_generate, image_index=image_index, **kw)
+
+    @torch.no_grad()
+    def score_completions(self, input_ids, attention_mask, pixel_values, image_grid_thw, completions, **generate_kwargs):
+        """Log-likelihood of given completions: ``generate(forced_tokens=completions, max_new_tokens=n, output_token_logprobs=True,
+        **generate_kwargs)`` (n = the table's width) with two more fields on the output object — ``completion_token_logprobs`` (B, n_steps):
+        ``token_logprobs`` with 0.0 wherever the step was not forced or lies after the row's first EOS; ``completion_logprobs`` (B,): its row
+        sums.  completions: what ``forced_tokens`` takes.  Several candidates for one image: repeat the prompt rows and pass ``image_index``."""
+        for k in ("forced_tokens", "max_new_tokens", "output_token_logprobs", "return_dict_in_generate"):
+            if k in generate_kwargs:
+                raise ValueError(f"score_completions sets generate({k}=...) itself")
+        table = check_forced_tokens(completions, input_ids.shape[0], 2 ** 31 - 1, self.config.vocab_size)
+        if not forced_tokens_active(table):
+            raise ValueError("score_completions: generate(forced_tokens=...) holds no token to score")
+        out = self.generate(input_ids=input_ids, attention_mask=attention_mask, pixel_values=pixel_values, image_grid_thw=image_grid_thw,
+                            forced_tokens=table, max_new_tokens=table.shape[1], output_token_logprobs=True, **generate_kwargs)
+        # the ids the decode loop itself stopped rows on (config id + the resolved options' list), not a second resolution of the arguments
+        eos = out.past_key_values.eos_ids
+        L = input_ids.shape[1]
+        out["completion_token_logprobs"], out["completion_logprobs"] = completion_logprobs(out.token_logprobs, out.sequences[:, L:], table, eos)
+        return out
 
     # ------------------------------------------------------------------ vl_decode (padt.py:342-412)
     @torch.no_grad()

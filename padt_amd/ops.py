@@ -984,6 +984,61 @@ def greedy_step(part_val, part_idx, nblk, hidden, hidden_buf, unfinished, tokens
                                     seen.shape[1] if seen is not None else 0), "padt_greedy_step")
 
 
+def _chk_forced(forced, B):
+    assert forced.dtype == torch.int32 and forced.is_cuda and forced.dim() == 2 and forced.is_contiguous() and forced.shape[0] >= B
+
+
+def vrt_head_probe(hidden, table, proto, vrt_off, part_val, part_idx, eos, part_sum, forced, probe_val, step, mode_table=None, logits=None,
+                   table_packed=None, rows=None, gen_cfg=None, seen=None, ban=None):
+    """vrt_head(part_sum=) that also writes probe_val[b] = the processed logit of column forced[b][*step] (padt_vrt_head_probe): forced int32
+    (rows, t_forced) table columns, negative = a free step (nothing written for the row); probe_val fp32 (rows,); step the device counter."""
+    dt = _x16(hidden, table, proto, table_packed)
+    B = hidden.shape[0] if rows is None else rows
+    assert part_sum.dtype == torch.float32 and part_sum.is_cuda and part_sum.is_contiguous()
+    assert part_sum.numel() >= (table.shape[0] + proto.shape[0] + 15) // 16 * B
+    _chk_forced(forced, B)
+    assert probe_val.dtype == torch.float32 and probe_val.is_cuda and probe_val.is_contiguous() and probe_val.numel() >= B
+    assert step is not None and step.dtype == torch.int32
+    if ban is not None:
+        assert ban.dtype == torch.int32 and ban.is_cuda and ban.dim() == 2 and ban.is_contiguous() and ban.shape[0] >= B
+    _lib.check(_fn("padt_vrt_head_probe", dt)(_stream(), _p(hidden), hidden.stride(0), _p(table), table.shape[0], _p(proto),
+                                              proto.shape[0], _p(vrt_off), _p(mode_table), _p(step), _p(logits),
+                                              logits.stride(0) if logits is not None else 0, _p(part_val), _p(part_idx),
+                                              B, hidden.shape[1], eos, _p(table_packed), _p(gen_cfg), _p(seen),
+                                              seen.shape[1] if seen is not None else 0, _p(ban), ban.shape[1] if ban is not None else 0,
+                                              _p(part_sum), _p(forced), forced.shape[1], _p(probe_val)), "padt_vrt_head_probe")
+
+
+def forced_step(part_val, part_idx, nblk, hidden, hidden_buf, unfinished, tokens_out, cur_tok, step, slot, lens, pos3, eos, pad, forced, n_cols,
+                advance=True, gen_cfg=None, seen=None, part_sum=None, logprobs=None, probe_val=None):
+    """greedy_step with the caller's tokens (padt_forced_step): an unfinished row b with 0 <= forced[b][*step] < n_cols takes that column as its
+    token, every other row is the free step.  part_sum / logprobs / probe_val (all or none): vrt_head_probe's outputs and the (B, T_max)
+    log-prob buffer — a forced row gets (probe - max) - log Σ, -inf for a -inf column."""
+    B, D = hidden.shape
+    _chk_forced(forced, B)
+    lp = (part_sum, logprobs, probe_val)
+    if any(t is not None for t in lp):
+        assert all(t is not None for t in lp), "forced_step: part_sum, logprobs and probe_val go together"
+        assert part_sum.dtype == torch.float32 and part_sum.is_cuda and part_sum.is_contiguous() and part_sum.numel() >= nblk * B
+        assert logprobs.dtype == torch.float32 and logprobs.is_cuda and logprobs.is_contiguous() and logprobs.shape == (B, tokens_out.shape[1])
+        assert probe_val.dtype == torch.float32 and probe_val.is_cuda and probe_val.is_contiguous() and probe_val.numel() >= B
+    _lib.check(_lib.load().padt_forced_step(_stream(), _p(part_val), _p(part_idx), nblk, B, D, eos, pad, tokens_out.shape[1],
+                                            _p(unfinished), _p(tokens_out), _p(cur_tok), _p(step), _p(slot), _p(lens), _p(pos3),
+                                            _p(hidden), _p(hidden_buf), 1 if advance else 0, _p(gen_cfg), _p(seen),
+                                            seen.shape[1] if seen is not None else 0, _p(part_sum), _p(logprobs), _p(forced), forced.shape[1],
+                                            _p(probe_val), int(n_cols)), "padt_forced_step")
+
+
+def forced_override(part_idx, forced, step, unfinished, n_cols, batch):
+    """Row path of forced tokens (padt_forced_override): part_idx[b] = forced[b][*step] for the unfinished rows with an entry in [0, n_cols),
+    after sample_token / warp_sample_rows / argmax_rows and before token_logprob_rows / forced_step."""
+    _chk_forced(forced, batch)
+    assert part_idx.dtype == torch.int32 and part_idx.is_cuda and part_idx.numel() >= batch
+    assert unfinished.dtype == torch.int32 and unfinished.numel() >= batch and step.dtype == torch.int32
+    _lib.check(_lib.load().padt_forced_override(_stream(), _p(part_idx), _p(forced), forced.shape[1], _p(step), _p(unfinished), int(n_cols),
+                                                int(batch)), "padt_forced_override")
+
+
 def collect_summary(err, unfinished, nf_rows, nf_batch, n_batch, tokens, done, eos, gen_cfg, out):
     """One launch: out = [err, any(unfinished), nf_rows…, nf_batch[:n_batch]…, first_eos step per row…] (padt_collect_summary)."""
     n_rows = unfinished.numel()

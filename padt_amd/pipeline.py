@@ -20,13 +20,14 @@ def sample_grids(image_grid_thw, image_index):
 
 def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens=1024,
               schedule: Optional[Sequence] = None, need_thinking_mask=None, image_index=None, do_sample=False, min_p=None, typical_p=None,
-              epsilon_cutoff=None, eta_cutoff=None, **gen_kw):
+              epsilon_cutoff=None, eta_cutoff=None, forced_tokens=None, **gen_kw):
     """→ (decoded dict of vl_decode, completions, labels, vrts).  ``input_ids`` carries LOCAL VRT ids (as a processor
     emits them) and is updated in place exactly like the reference's callers do.
     ``image_index``: sample b asks about image image_index[b] of the N <= B images given (generate(image_index=)); everything per sample
     (VRT id ranges, vl_decode) then follows ``image_grid_thw[image_index]``.
     ``do_sample`` (default: greedy, whatever the checkpoint's generation_config says) with ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` /
-    ``eta_cutoff`` and, through ``**gen_kw``, ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: see generate()."""
+    ``eta_cutoff`` and, through ``**gen_kw``, ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: see generate().
+    ``forced_tokens``: generate(forced_tokens=) — GLOBAL ids, numbered like the generated part of ``sequences``."""
     B = input_ids.shape[0]
     grid_in = image_grid_thw
     if image_index is not None:
@@ -36,7 +37,7 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
     out = model.generate(input_ids=ids, attention_mask=attention_mask, pixel_values=pixel_values,
                          image_grid_thw=grid_in, use_cache=True, max_new_tokens=max_new_tokens, do_sample=do_sample,
                          output_hidden_states=True, return_dict_in_generate=True, schedule=schedule, min_p=min_p, typical_p=typical_p,
-                         epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, **gen_kw)
+                         epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, forced_tokens=forced_tokens, **gen_kw)
     L = input_ids.shape[1]
     seq_local = processor.assign_to_local_vrt_id(out["sequences"].cpu(), image_grid_thw.cpu())
     completion_ids = seq_local[:, L:]
@@ -104,12 +105,13 @@ class PipelinedRunner:
     def submit(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens=1024, schedule=None,
                need_thinking_mask=None, sync_every=None, repetition_penalty=None, eos_token_id=None, no_repeat_ngram_size=None,
                bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None, do_sample=False, min_p=None,
-               typical_p=None, epsilon_cutoff=None, eta_cutoff=None, **sampling):
+               typical_p=None, epsilon_cutoff=None, eta_cutoff=None, forced_tokens=None, **sampling):
         """image_index: see generate(); the batch's results are those of the expanded batch.
         do_sample (default: greedy) with min_p / typical_p / epsilon_cutoff / eta_cutoff and, through **sampling, temperature / top_k / top_p /
         seed: see generate(); batches whose resolved options differ in any of them (the seed included) do not share a decode group.
         output_token_logprobs / top_logprobs / output_patch_logprobs (through **sampling, see generate()): the decoded dict of the batch carries
-        "token_logprobs" / "top_token_ids" + "top_logprobs" / "patch_logprobs" when asked; batches that disagree on them do not share a decode group."""
+        "token_logprobs" / "top_token_ids" + "top_logprobs" / "patch_logprobs" when asked; batches that disagree on them do not share a decode group.
+        forced_tokens: generate(forced_tokens=), each batch its own table; a batch that forces and one that does not never share a group."""
         done = []
         bid = self.n_batches
         self.n_batches += 1
@@ -119,6 +121,9 @@ class PipelinedRunner:
         ids = self.processor.assign_to_global_vrt_id(input_ids, image_grid_thw)
         sched = tuple(schedule) if schedule is not None else None
         warpers = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
+        hooks = dict(warpers=warpers) if any(v is not None for v in warpers.values()) else {}
+        if forced_tokens is not None:
+            hooks["forced"] = forced_tokens
         for attempt in range(2):
             if self.cur is None:
                 while len(self.pending) > self.depth - 1:         # the lane about to be reused must have been collected
@@ -148,7 +153,7 @@ class PipelinedRunner:
                                                  no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                                                  suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
                                                  vit_stream=self.vit_stream, inputs_ready=ev_in, image_index=image_index,
-                                                 hooks=dict(warpers=warpers) if any(v is not None for v in warpers.values()) else None,
+                                                 hooks=dict(hooks) if hooks else None,
                                                  **sampling)
             if ctx is not None:
                 break
