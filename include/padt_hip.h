@@ -455,6 +455,22 @@ int  padt_seen_init(void* stream, const long* ids, const int* rows, long n, void
  *   equals the last n - 1 history ids (n = 1: every id of the history).  Ids outside [0, n_cols) set no bit; n_cols <= 32 ban_words. */
 int  padt_gen_rules(void* stream, const int* rules, const int* hist, long ld_hist, const int* hist_len, const long* tokens, long ld_tokens,
                     const int* step, void* ban, long ban_words, long n_cols, long batch);
+/* generate(token_automaton=A): the step's ban bitmap from the state of a token automaton — every column of [0, n_cols) is banned except the
+ * keys of the edges of the row's state.  One block per session row; NOT HF's prefix_allowed_tokens_fn (no host callback: the table is data).
+ * table: table_ints int32 in DEVICE memory, packed by ops.token_automaton_tensor:
+ *   [0] magic 0x54413031 [1] S <= 4096 states [2] E <= 32768 edges [3] start state [4 .. 4 + S] edge offsets [5 + S ..) E (key, next state)
+ *   pairs, per state sorted by key: the classes EOS = -3, TEXT = -2, VRT = -1 first, then explicit text ids (0 <= id < vocab) ascending.
+ *   An explicit id matches before a class; VRT = the row's own columns vocab + vrt_off[b] .. vocab + vrt_off[b + 1] - 1, EOS = an id of
+ *   gen_cfg's EOS list, TEXT = a text id that is none of them (the EOS ids are carved out of the range unless the state has an EOS edge).
+ * state: int32 [batch][2] = (state, valid_for_step), reset to (-1, -1).  At *step = t: valid == t keeps the state (a repeated launch is
+ *   idempotent), valid == t - 1 advances it by tokens[b][t - 1], anything else rebuilds it from the start state over tokens[b][0 .. t).  A token
+ *   without an edge leads to the off-automaton state -1 for good.  An empty allowed set (state -1, a state without edges, a VRT-only state of
+ *   a row without patches) allows the EOS ids alone.  Rows with unfinished[b] == 0 keep their state and ban nothing.
+ * ban: [batch][ban_words] rebuilt from scratch, bits >= n_cols zero; rules_ban (optional, another buffer of the same shape: padt_gen_rules'
+ *   output of this step) is OR-ed in last, so padt_vrt_head_ban reads the union.  A table that fails the header's checks writes nothing. */
+int  padt_token_automaton(void* stream, const int* table, long table_ints, const void* gen_cfg, const int* vrt_off, const long* tokens,
+                          long ld_tokens, const int* step, const int* unfinished, int* state, void* ban, long ban_words,
+                          const void* rules_ban, long n_cols, long vocab, long batch);
 
 /* ---- caller-side post-processing --------------------------------------------------------------- */
 /* out[o][y][x] = sigmoid(bilinear(masks[o][:src_h[o]][:src_w[o]] → dst_h[o] x dst_w[o], align_corners=False))[y][x] > 0.5,

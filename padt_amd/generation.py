@@ -151,6 +151,226 @@ def completion_logprobs(token_logprobs: torch.Tensor, tokens: torch.Tensor, forc
     return per, per.sum(1)
 
 
+# ------------------------------------------------------------------------------------------------ generate(token_automaton=)
+class TokenAutomaton:
+    """Which tokens a row may emit next, given what it emitted so far: a deterministic automaton over the generated tokens, walked on the
+    device inside the decode step (padt_token_automaton).  NOT HF's ``prefix_allowed_tokens_fn``: there is no callback — the table is data.
+
+    States are 0 .. S - 1.  ``edges[s]`` lists state s' edges ``(key, next_state)``; a key is a text id (0 <= id < vocab_size) or a class:
+    ``VRT`` — any of the row's own patch tokens (table columns vocab_size + vrt_off[row] .. vocab_size + vrt_off[row + 1] - 1), ``TEXT`` — any
+    text id that is none of the call's EOS ids, ``EOS`` — any of the call's EOS ids.  An explicit id wins over a class.  The tokens allowed in
+    a state are exactly the keys of its edges.  Two rules the device shares with ``allowed()``: a token without an edge (possible under
+    ``forced_tokens``, a caller processor or a ``schedule`` only) takes the row to the off-automaton state ``OFF`` for good; and wherever the
+    allowed set is empty (``OFF``, a terminal state, a ``VRT``-only state of a sample without patches) the EOS ids are allowed and nothing else.
+
+    Normal form: per state the edges sorted by key (classes first), duplicate keys refused; ``key`` = (start, edges) is hashable and equal
+    for equal tables — it decides whether two batches can share a decode group.  ``ValueError`` naming ``token_automaton`` for a malformed
+    table (``check(vocab_size)`` adds the id range once the vocabulary is known), ``NotImplementedError`` above ``MAX_STATES`` states /
+    ``MAX_EDGES`` edges (the packed table's caps)."""
+    VRT, TEXT, EOS = -1, -2, -3
+    OFF = -1
+    MAX_STATES, MAX_EDGES = ops.TOKEN_AUTOMATON_MAX_STATES, ops.TOKEN_AUTOMATON_MAX_EDGES
+    _CLASS_NAMES = {-1: "VRT", -2: "TEXT", -3: "EOS"}
+
+    def __init__(self, edges, start=0):
+        name = "token_automaton"
+        try:
+            table = [list(st) for st in edges]
+        except TypeError:
+            raise ValueError(f"{name}: a list of per-state edge lists [(key, next_state), ...] is required, got {edges!r}") from None
+        S = len(table)
+        n_edges = sum(len(st) for st in table)
+        if S > self.MAX_STATES or n_edges > self.MAX_EDGES:
+            raise NotImplementedError(f"{name}: {S} states / {n_edges} edges; at most {self.MAX_STATES} states and {self.MAX_EDGES} edges "
+                                      "on the MI355X path")
+        if isinstance(start, bool) or not isinstance(start, numbers.Integral) or not 0 <= int(start) < S:
+            raise ValueError(f"{name}: the start state {start!r} is outside the table ({S} states)")
+        norm = []
+        for s, st in enumerate(table):
+            out = []
+            for e in st:
+                try:
+                    k, nx = e
+                except (TypeError, ValueError):
+                    raise ValueError(f"{name}: state {s}: an edge is a (key, next_state) pair, got {e!r}") from None
+                for v in (k, nx):
+                    if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                        raise ValueError(f"{name}: state {s}: keys and states must be integers, got {e!r}")
+                k, nx = int(k), int(nx)
+                if k < self.EOS:
+                    raise ValueError(f"{name}: state {s}: key {k} is neither a token id nor one of VRT / TEXT / EOS")
+                if k >= 2 ** 31 - 1:
+                    raise ValueError(f"{name}: state {s}: id {k} is outside the vocabulary")
+                if not 0 <= nx < S:
+                    raise ValueError(f"{name}: state {s}: next_state {nx} is outside the table ({S} states)")
+                out.append((k, nx))
+            out.sort()
+            for a, b in zip(out, out[1:]):
+                if a[0] == b[0]:
+                    raise ValueError(f"{name}: state {s}: duplicate key {self._CLASS_NAMES.get(a[0], a[0])}")
+            norm.append(tuple(out))
+        self.start, self.edges = int(start), tuple(norm)
+        # a reachable state without edges must be terminal: entered through EOS edges only
+        seen, todo = {self.start}, [self.start]
+        if not self.edges[self.start]:
+            raise ValueError(f"{name}: the start state {self.start} has no edges")
+        while todo:
+            s = todo.pop()
+            for k, nx in self.edges[s]:
+                if not self.edges[nx] and k != self.EOS:
+                    raise ValueError(f"{name}: state {nx} has no edges and is entered from state {s} through "
+                                     f"{self._CLASS_NAMES.get(k, k)}, not through an EOS edge")
+                if nx not in seen:
+                    seen.add(nx)
+                    todo.append(nx)
+
+    @property
+    def key(self):
+        return (self.start, self.edges)
+
+    def __eq__(self, other):
+        return self.key == other.key if isinstance(other, TokenAutomaton) else NotImplemented
+
+    def __hash__(self):
+        return hash(self.key)
+
+    def __repr__(self):
+        return f"TokenAutomaton({len(self.edges)} states, {sum(len(e) for e in self.edges)} edges, start={self.start})"
+
+    def check(self, vocab_size):
+        """The id range, once the vocabulary is known: ValueError naming token_automaton for an explicit id outside [0, vocab_size).  → self."""
+        for s, st in enumerate(self.edges):
+            for k, _ in st:
+                if k >= int(vocab_size):
+                    raise ValueError(f"token_automaton: state {s}: id {k} is not a text id (0 <= id < {int(vocab_size)}); patch tokens are "
+                                     "named through the VRT class")
+        return self
+
+    @classmethod
+    def from_sequences(cls, seqs, repeat=False):
+        """The trie of the given sequences (items: text ids or the class constants); every complete sequence is followed by an ``EOS`` edge
+        into one terminal state.  ``repeat=True``: the end of a sequence also carries the start state's edges, so another sequence may follow —
+        the OVD / closed-set-label case, ``from_sequences([name_ids + [VRT] * 5 for name_ids in categories], repeat=True)``.  States are
+        numbered breadth-first in key order, so the same set of sequences gives the same key in whatever order it is listed."""
+        name = "token_automaton"
+        children, ends = [{}], set()
+        n_seq = 0
+        for seq in seqs:
+            n_seq += 1
+            node = 0
+            try:
+                items = list(seq)
+            except TypeError:
+                raise ValueError(f"{name}: from_sequences takes sequences of ids / class constants, got {seq!r}") from None
+            if not items:
+                raise ValueError(f"{name}: from_sequences: an empty sequence")
+            for k in items:
+                if isinstance(k, bool) or not isinstance(k, numbers.Integral) or int(k) < cls.EOS:
+                    raise ValueError(f"{name}: from_sequences: {k!r} is neither a token id nor one of VRT / TEXT / EOS")
+                k = int(k)
+                if k == cls.EOS:
+                    raise ValueError(f"{name}: from_sequences appends the EOS edge itself: sequences must not contain EOS")
+                if k not in children[node]:
+                    if len(children) > 2 * cls.MAX_EDGES:
+                        raise NotImplementedError(f"{name}: more than {cls.MAX_STATES} states / {cls.MAX_EDGES} edges on the MI355X path")
+                    children[node][k] = len(children)
+                    children.append({})
+                node = children[node][k]
+            ends.add(node)
+        if n_seq == 0:
+            raise ValueError(f"{name}: from_sequences needs at least one sequence")
+        term = len(children)
+        table = []
+        for node, ch in enumerate(children):
+            st = dict(ch)
+            if node in ends:
+                if repeat:
+                    for k, nx in children[0].items():
+                        if k in st:
+                            raise ValueError(f"{name}: from_sequences(repeat=True): after a complete sequence the key "
+                                             f"{cls._CLASS_NAMES.get(k, k)} both continues a longer sequence and starts a new one")
+                        st[k] = nx
+                st[cls.EOS] = term
+            table.append(st)
+        table.append({})
+        # canonical numbering: breadth-first from the start state, edges in key order
+        order, number = [0], {0: 0}
+        for node in order:
+            for k in sorted(table[node]):
+                nx = table[node][k]
+                if nx not in number:
+                    number[nx] = len(order)
+                    order.append(nx)
+        return cls([[(k, number[nx]) for k, nx in table[node].items()] for node in order], start=0)
+
+    def step(self, state, token, n_text, vrt_range, eos_ids):
+        """The state after `token` in `state` (OFF stays OFF; a token without an edge leads to OFF)."""
+        if state == self.OFF:
+            return self.OFF
+        token = int(token)
+        st = dict(self.edges[state])
+        lo, hi = int(n_text) + int(vrt_range[0]), int(n_text) + int(vrt_range[1])
+        if 0 <= token < n_text and token in st:
+            return st[token]
+        if lo <= token < hi:
+            return st.get(self.VRT, self.OFF)
+        if 0 <= token < n_text:
+            return st.get(self.EOS if token in {int(e) for e in eos_ids} else self.TEXT, self.OFF)
+        return self.OFF
+
+    def walk(self, tokens, n_text, vrt_range, eos_ids):
+        """The state after the generated prefix `tokens`, from the start state."""
+        state = self.start
+        for tok in tokens:
+            state = self.step(state, tok, n_text, vrt_range, eos_ids)
+        return state
+
+    def allowed_in(self, state, n_text, vrt_range, eos_ids):
+        """The sorted table columns allowed in `state` for a row whose patches are columns n_text + vrt_range[0] .. n_text + vrt_range[1] - 1."""
+        eos = sorted({int(e) for e in eos_ids if 0 <= int(e) < n_text})
+        out = set()
+        if state != self.OFF:
+            st = dict(self.edges[state])
+            if self.TEXT in st:
+                out.update(range(int(n_text)))
+                if self.EOS not in st:
+                    out.difference_update(eos)
+            if self.VRT in st:
+                out.update(range(int(n_text) + int(vrt_range[0]), int(n_text) + int(vrt_range[1])))
+            if self.EOS in st:
+                out.update(eos)
+            out.update(k for k in st if 0 <= k < n_text)
+        return sorted(out) if out else eos
+
+    def allowed(self, tokens, n_text, vrt_range, eos_ids):
+        """The sorted list of allowed table columns after the generated prefix `tokens` — a plain Python walk: the specification the kernel
+        is compared against.  n_text: the vocabulary size; vrt_range = (lo, hi): the row's patch offsets (vrt_off[row], vrt_off[row + 1]);
+        eos_ids: the call's EOS ids."""
+        return self.allowed_in(self.walk(tokens, n_text, vrt_range, eos_ids), n_text, vrt_range, eos_ids)
+
+    def accepts(self, tokens, n_text, vrt_range, eos_ids):
+        """True when every token of `tokens`, up to and including the first EOS id, was allowed where it stands."""
+        state, eos = self.start, {int(e) for e in eos_ids}
+        for tok in tokens:
+            if int(tok) not in self.allowed_in(state, n_text, vrt_range, eos_ids):
+                return False
+            if int(tok) in eos:
+                return True
+            state = self.step(state, tok, n_text, vrt_range, eos_ids)
+        return True
+
+
+def check_token_automaton(token_automaton, vocab_size):
+    """generate(token_automaton=A) → A, checked against the vocabulary; None stays None.  ValueError naming the argument for anything that
+    is not a TokenAutomaton."""
+    if token_automaton is None:
+        return None
+    if not isinstance(token_automaton, TokenAutomaton):
+        raise ValueError(f"generate(token_automaton=...): a padt_amd.generation.TokenAutomaton is required, got {type(token_automaton).__name__} "
+                         "(it is not HF's prefix_allowed_tokens_fn: a callable cannot run inside the captured step)")
+    return token_automaton.check(vocab_size)
+
+
 # generate()'s named parameters a generation_config may carry: an explicit argument (not None) wins, as in HF (padt.py:436)
 _GENERATE_CONFIG_NAMED = ("max_new_tokens", "max_length", "do_sample", "repetition_penalty", "eos_token_id", "pad_token_id", "temperature", "top_k",
                           "top_p", "no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens", "min_p", "typical_p",
@@ -238,6 +458,7 @@ class StepMode(NamedTuple):
     reference: bool = False          # precision="reference": reference.ReferencePath.step instead of step_kernels
     warpers: bool = False            # min_p / typical_p / epsilon_cutoff / eta_cutoff: padt_warp_sample_rows_f32 warps the row and draws
     forced: bool = False             # generate(forced_tokens=): the probe head / padt_forced_step / padt_forced_override read the session's table
+    automaton: bool = False          # generate(token_automaton=): padt_token_automaton writes the bitmap the head reads (the union with the rules')
 
 
 @dataclass(frozen=True)
@@ -257,12 +478,18 @@ class GenOptions:
     # or neither does) but deliberately NOT a dataclass field: the fields are the options generate_kwargs() spells as generate() arguments for a
     # re-run, and the table travels with its batch instead (modeling._non_finite_batch).
     forced: InitVar[bool] = False
+    # generate(token_automaton=A): A.key, or None.  Like `forced` an init-only attribute — part of equality, hash and repr (batches share a
+    # decode group only when their automata are equal: a session holds ONE packed table), not a dataclass field and not in generate_kwargs():
+    # the automaton object travels with its batch to a re-run.
+    automaton: InitVar[Optional[tuple]] = None
 
-    def __post_init__(self, forced):
+    def __post_init__(self, forced, automaton):
         object.__setattr__(self, "forced", bool(forced))
+        object.__setattr__(self, "automaton", automaton)
 
     def _key(self):
-        return tuple(getattr(self, f.name) for f in fields(self)) + (self.forced,)      # every field, whatever is added later, and the flag
+        # every field, whatever is added later, and the two init-only attributes
+        return tuple(getattr(self, f.name) for f in fields(self)) + (self.forced, self.automaton)
 
     def __eq__(self, other):
         return self._key() == other._key() if isinstance(other, GenOptions) else NotImplemented
@@ -271,7 +498,9 @@ class GenOptions:
         return hash(self._key())
 
     def __repr__(self):
-        args = [f"{f.name}={getattr(self, f.name)!r}" for f in fields(self)] + [f"forced={self.forced!r}"]
+        a = self.automaton                                        # the key of a large table is long: its size and hash stand for it
+        auto = "None" if a is None else f"<{len(a[1])} states, {sum(len(e) for e in a[1])} edges, start {a[0]}, #{hash(a) & 0xffffffff:08x}>"
+        args = [f"{f.name}={getattr(self, f.name)!r}" for f in fields(self)] + [f"forced={self.forced!r}", f"automaton={auto}"]
         return f"GenOptions({', '.join(args)})"
 
     @property
@@ -299,7 +528,8 @@ class GenOptions:
     def step_mode(self, processors: bool = False, reference: bool = False) -> StepMode:
         return StepMode(sampling=self.sampling is not None, keep_scores=self.keep_scores, keep_logits=self.keep_logits, rules=self.rules is not None,
                         token_logprobs=self.token_logprobs, top_k=self.top_logprobs, patches=self.patch_logprobs, processors=bool(processors),
-                        reference=bool(reference), warpers=self.sampling is not None and self.sampling.warpers, forced=self.forced)
+                        reference=bool(reference), warpers=self.sampling is not None and self.sampling.warpers, forced=self.forced,
+                        automaton=self.automaton is not None)
 
     def warper_kwargs(self) -> dict:
         """min_p / typical_p / epsilon_cutoff / eta_cutoff as explicit generate() keywords (with_warpers values), next to generate_kwargs():

@@ -369,6 +369,9 @@ class DecodeSession:
         self.topk_ws = None              # padt_topk_logprob_rows_f32's chunk workspace, sized for k = 32
         self.forced = None               # mode.forced (generate(forced_tokens=)): [B][t_max] int32 table columns in session numbering, -1 = free ...
         self.probe_val = None            # ... and the probe head's processed logit of each row's forced column [B]
+        self.atab = None                 # mode.automaton (generate(token_automaton=)): the packed table, ops.TOKEN_AUTOMATON_INTS int32 (fixed size) ...
+        self.astate = None               # ... each row's (state, valid_for_step) [B][2] ...
+        self.aban = None                 # ... and the bitmap padt_token_automaton writes for the head (with rules: its union with `ban`) [B][words]
         self.rope_cs = z(B, hd // 2, 2, dt=torch.float32)
         self.n_qkv = (cfg.num_attention_heads + 2 * Hkv) * hd
         self.graphs = {}                 # captured decode-step graph per mode (different kernel sequences and output buffers)
@@ -414,7 +417,7 @@ class DecodeSession:
         ops.check_finite(self.hn, self.nf, rows_per_flag=1, rows=B)      # sticky per-row flag, read once per generate (modeling.generate_collect)
         self.head_and_select(self.hn, advance=True)
 
-    def begin(self, opts: GenOptions, p_max: int = 0, processors: bool = False, step_fn=None):
+    def begin(self, opts: GenOptions, p_max: int = 0, processors: bool = False, step_fn=None, automaton=None):
         """Start of a generate with these options (p_max: the largest patch count of one sample; processors: the caller's logits_processor runs in
         the hooked loop; step_fn: precision="reference"'s step): the gen_cfg slots and the rule table the captured step reads, the step mode,
         and the log-prob buffers, allocated on first use and set to their finished-row values (0 / -1 / -inf) for every generate that asks.
@@ -455,6 +458,14 @@ class DecodeSession:
                 self.forced = torch.empty((self.B, self.t_max), device=dev, dtype=I32)
                 self.probe_val = torch.zeros(self.B, device=dev, dtype=torch.float32)
             self.forced.fill_(-1)
+        if opts.automaton is not None:                           # `automaton`: the generation.TokenAutomaton whose key the options carry
+            tab = ops.token_automaton_tensor(automaton, key=None if automaton is not None else opts.automaton)
+            if self.atab is None:
+                self.atab = torch.zeros(ops.TOKEN_AUTOMATON_INTS, device=dev, dtype=I32)
+                self.astate = torch.empty((self.B, 2), device=dev, dtype=I32)
+                self.aban = torch.zeros_like(self.ban)
+            self.atab[: tab.numel()].copy_(tab.to(dev, non_blocking=True))
+            self.astate.fill_(-1)                                # no row's state is valid: the first launch starts every row at the start state
         if opts.rules is not None:
             self.rules.copy_(ops.gen_rules_tensor(key=opts.rules).to(dev, non_blocking=True))
             self.hist_len.zero_()                                # rows no batch of the group fills: an empty prompt
@@ -476,6 +487,9 @@ class DecodeSession:
         ban = None
         if m.rules:                                          # this step's ban bitmap from the rows' histories; the head then writes -inf there
             ban = ops.gen_rules(self.rules, self.hist, self.hist_len, self.tokens, self.step, self.ban, cfg.vocab_size + self.np_max)
+        if m.automaton:                                      # the columns the rows' automaton states allow; with rules the union of both bitmaps
+            ban = ops.token_automaton(self.atab, self.gen_cfg, self.vrt_off, self.tokens, self.step, self.unfinished, self.astate, self.aban,
+                                      cfg.vocab_size + self.np_max, cfg.vocab_size, rules_ban=ban)
         # forced tokens (generate(forced_tokens=)): the caller's table decides the token of a forced row.  Fused log-probs: the probe head leaves
         # the processed logit of the forced column next to the LSE partials; without log-probs the plain head runs and only the bookkeeping differs
         fc = self.forced if m.forced else None

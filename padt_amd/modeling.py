@@ -21,8 +21,9 @@ import torch
 from . import _lib, ops
 from .config import PaDTConfig
 from .decoder import PaDTDecoder
-from .generation import (_GENERATE_CONFIG_NAMED, _GENERATE_CONFIG_OWN, check_forced_tokens, check_generate_kwargs, check_top_logprobs,  # noqa: F401
-                         completion_logprobs, forced_tokens_active, generation_config_fields, resolve_options, with_warpers, WARPER_NAMES)
+from .generation import (_GENERATE_CONFIG_NAMED, _GENERATE_CONFIG_OWN, check_forced_tokens, check_generate_kwargs, check_token_automaton,  # noqa: F401
+                         check_top_logprobs, completion_logprobs, forced_tokens_active, generation_config_fields, resolve_options, with_warpers,
+                         WARPER_NAMES)
 from .llm import MODE, LanguageModel, check_shared_destinations, plan_prompt, plan_prompt_shared
 from .vision import VisionEncoder
 from .weights import Fp16RangeError, load_checkpoint_state_dict, prepare_weights, synthetic_state_dict
@@ -332,6 +333,20 @@ class PaDTForConditionalGeneration:
         wrong batch size, n > max_new_tokens, a non-integer dtype or an id outside the table; an all-free table is the call without the
         argument.  It is NOT HF's ``forced_decoder_ids`` / ``forced_eos_token_id`` and NOT ``labels``: no prompt-pass scorer, no loss
         (``forward(is_main=True)`` keeps raising).  ``score_completions`` names the scoring use.
+        Keyword ``token_automaton=A`` (a ``padt_amd.generation.TokenAutomaton``; ``None``: off, the call without the argument): which tokens
+        a row may emit at a position GIVEN WHAT IT EMITTED SO FAR, decided on the device inside the captured step.  Before the head runs,
+        ``padt_token_automaton`` advances every unfinished row's state by its last token and writes the step's ban bitmap — every table
+        column banned except the keys of the state's edges (explicit text ids, ``A.VRT`` = the row's own patch tokens, ``A.TEXT`` = any text
+        id but the EOS ids, ``A.EOS`` = the call's EOS ids); the head writes ``-inf`` at a banned column exactly as for the four bans, so
+        ``.scores``, the arg-max, the sampler and its warpers, ``top_logprobs`` / ``patch_logprobs``, ``forced_tokens`` and the caller's
+        ``logits_processor`` all see the constrained row, and with one of the four bans active the head reads the union of both bitmaps.
+        ``token_logprobs`` under an automaton is therefore the log-softmax OVER THE ALLOWED COLUMNS: the closed-set probability of the token
+        among the candidates the automaton admits.  A forced token (or a caller processor's / a ``schedule``'s) that has no edge takes its row
+        off the automaton; such a row, like any row whose allowed set is empty, is allowed its EOS ids and nothing else.  It is NOT HF's
+        ``prefix_allowed_tokens_fn`` (a Python callback per row and step cannot run inside a captured graph; that argument stays refused):
+        the automaton is a table in device memory, so one captured graph per step mode serves every automaton, and batches share a decode
+        group only when their automata are equal.  ``ValueError`` naming ``token_automaton`` for anything that is not a ``TokenAutomaton`` or
+        names an id outside the text vocabulary.
         """
         if synced_gpus:
             raise NotImplementedError("generate(synced_gpus=True) is the ZeRO-3 / FSDP lock-step loop (padt.py:445,670): every rank holds a full "
@@ -339,6 +354,7 @@ class PaDTForConditionalGeneration:
         # HF's warpers after top-p are keywords of this call (not named parameters: the parameter list is frozen)
         min_p, typical_p, epsilon_cutoff, eta_cutoff = (kwargs.pop(k, None) for k in WARPER_NAMES)
         forced_tokens = kwargs.pop("forced_tokens", None)             # ... and so is the table of forced completion tokens
+        token_automaton = kwargs.pop("token_automaton", None)         # ... and the automaton that says which tokens may follow
         if generation_config is not None:
             named = dict(max_new_tokens=max_new_tokens, max_length=max_length, do_sample=do_sample, repetition_penalty=repetition_penalty,
                          eos_token_id=eos_token_id, pad_token_id=pad_token_id, temperature=temperature, top_k=top_k, top_p=top_p,
@@ -379,6 +395,8 @@ class PaDTForConditionalGeneration:
             hooks = dict(hooks or {}, warpers=warpers)                # generate_launch's channel for them (see there)
         if forced_tokens is not None:
             hooks = dict(hooks or {}, forced=forced_tokens)           # the same channel
+        if token_automaton is not None:
+            hooks = dict(hooks or {}, automaton=token_automaton)
         if output_logits:
             pen = self.generation_config.repetition_penalty if repetition_penalty is None else repetition_penalty
             if float(pen) != 1.0 or schedule is not None or processors is not None:
@@ -422,6 +440,7 @@ class PaDTForConditionalGeneration:
         after top-p, ``hooks=dict(warpers=dict(min_p=..., typical_p=..., epsilon_cutoff=..., eta_cutoff=...))`` (None entries: the
         generation config decides); warpers alone keep the captured step and merged groups.  ``hooks=dict(forced=F)``: generate()'s
         ``forced_tokens`` — per-batch data like the prompt; batches share a group only when both force or neither does.
+        ``hooks=dict(automaton=A)``: generate()'s ``token_automaton``; batches share a group only when their automata are equal.
         """
         # a call's min_p / typical_p / epsilon_cutoff / eta_cutoff arrive as hooks["warpers"] (this method's parameter list is frozen) and are put
         # in front of the generation config's; what is left of `hooks` is the caller's processors / criteria, or nothing
@@ -434,6 +453,10 @@ class PaDTForConditionalGeneration:
             if hooks["forced"] is not None:                       # shape / dtype now; the id bound once the batch's patch count is known (_launch)
                 forced = check_forced_tokens(hooks["forced"], input_ids.shape[0], max_new_tokens, self.config.vocab_size)
             hooks = {k: v for k, v in hooks.items() if k != "forced"} or None
+        automaton = None
+        if hooks is not None and "automaton" in hooks:
+            automaton = check_token_automaton(hooks["automaton"], self.config.vocab_size)
+            hooks = {k: v for k, v in hooks.items() if k != "automaton"} or None
         if image_index is not None and getattr(self, "precision", "default") == "reference":
             raise NotImplementedError("generate(image_index=...) is not implemented with precision='reference' (its prompt pass is its own: "
                                       "reference.ReferencePath.prefill): expand the inputs or use precision='default'")
@@ -449,12 +472,14 @@ class PaDTForConditionalGeneration:
             opts = dataclasses.replace(opts, forced=True)
         else:
             forced = None                                         # an all-free table: the call without the argument
+        if automaton is not None:
+            opts = dataclasses.replace(opts, automaton=automaton.key)
         return owner._launch(opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, max_new_tokens=max_new_tokens,
                              schedule=schedule, hooks=hooks, sync_every=sync_every, use_graph=use_graph, lane=lane, decode_stream=decode_stream,
-                             group=group, n_slots=n_slots, vit_stream=vit_stream, inputs_ready=inputs_ready, forced=forced)
+                             group=group, n_slots=n_slots, vit_stream=vit_stream, inputs_ready=inputs_ready, forced=forced, automaton=automaton)
 
     def _launch(self, opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, *, max_new_tokens, schedule, hooks, sync_every,
-                use_graph, lane, decode_stream, group, n_slots, vit_stream, inputs_ready, forced=None):
+                use_graph, lane, decode_stream, group, n_slots, vit_stream, inputs_ready, forced=None, automaton=None):
         """generate_launch on the group's owner, with the call's options resolved (generation.GenOptions)."""
         self._batches_seen += 1
         if pixel_values is None or image_grid_thw is None:
@@ -487,7 +512,8 @@ class PaDTForConditionalGeneration:
                          use_graph=use_graph, decode_stream=decode_stream, done=0, launched=False, schedule=schedule,
                          opts=opts, lane=lane, owner=self)
             # reference precision: eager split-precision steps (+ fp32 hidden rows, below)
-            sess.begin(opts, p_max, processors=bool(hooks and hooks["processors"]), step_fn=self.ref.step if self.ref is not None else None)
+            sess.begin(opts, p_max, processors=bool(hooks and hooks["processors"]), step_fn=self.ref.step if self.ref is not None else None,
+                       automaton=automaton)
             if hooks is not None:
                 ids_dev = input_ids.detach().to(dev).long().contiguous()
                 hk = dict(hooks, B=B, table_rows=cfg.vocab_size + n_proto, t=0)
@@ -595,7 +621,7 @@ class PaDTForConditionalGeneration:
             hn_all = self.lm.prefill(plan, low, sess, nf=nf)
             ops.gather_rows(hn_all, plan.last_idx, out=sess.hn_first[rows])
         group["subs"].append(dict(plan=plan, low=low, high=high, pe=pe, proto=proto, hn_all=hn_all, input_ids=input_ids,
-                                  n_proto=n_proto, row0=row0, proto_row0=proto_row0, nf=nf, p_max=p_max, forced=forced,
+                                  n_proto=n_proto, row0=row0, proto_row0=proto_row0, nf=nf, p_max=p_max, forced=forced, automaton=automaton,
                                   inputs=(attention_mask, pixel_values, image_grid_thw, image_index)))       # what a re-run on the bf16 twin needs
         group["proto_rows"] = proto_row0 + n_proto
         if len(group["subs"]) == group["n_slots"]:
@@ -738,6 +764,8 @@ class PaDTForConditionalGeneration:
             kw.update(logits_processor=group["hooks"]["processors"], stopping_criteria=group["hooks"]["criteria"])
         if sub.get("forced") is not None:
             kw.update(forced_tokens=sub["forced"])                # the caller's table, in the batch's own numbering
+        if sub.get("automaton") is not None:
+            kw.update(token_automaton=sub["automaton"])           # the batch's automaton object: the options carry its key only
         return fb.generate(input_ids=sub["input_ids"], attention_mask=am, pixel_values=pix, image_grid_thw=grid, max_new_tokens=group["T_max"],
                            schedule=group["schedule"], sync_every=group["sync_every"], use_graph=group["use_graph"], lane=("fb", group["lane"]),
                            output_hidden_states=output_hidden_states, return_dict_in_generate=return_dict_in_generate, image_index=image_index, **kw)
@@ -747,7 +775,10 @@ class PaDTForConditionalGeneration:
         """Log-likelihood of given completions: ``generate(forced_tokens=completions, max_new_tokens=n, output_token_logprobs=True,
         **generate_kwargs)`` (n = the table's width) with two more fields on the output object — ``completion_token_logprobs`` (B, n_steps):
         ``token_logprobs`` with 0.0 wherever the step was not forced or lies after the row's first EOS; ``completion_logprobs`` (B,): its row
-        sums.  completions: what ``forced_tokens`` takes.  Several candidates for one image: repeat the prompt rows and pass ``image_index``."""
+        sums.  completions: what ``forced_tokens`` takes.  Several candidates for one image: repeat the prompt rows and pass ``image_index``.
+        ``token_automaton=A`` (default ``None``; one of ``**generate_kwargs``, handed to generate(token_automaton=)): every step's row is constrained to the columns A allows after the forced prefix,
+        so ``token_logprobs`` is the log-softmax over the ALLOWED columns — the closed-set probability: over the labels of a trie the
+        probabilities of the first branching step sum to 1.  A completion that leaves the automaton scores ``-inf`` at that token."""
         for k in ("forced_tokens", "max_new_tokens", "output_token_logprobs", "return_dict_in_generate"):
             if k in generate_kwargs:
                 raise ValueError(f"score_completions sets generate({k}=...) itself")

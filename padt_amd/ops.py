@@ -858,6 +858,52 @@ def gen_rules(rules, hist, hist_len, tokens, step, ban, n_cols):
     return ban
 
 
+TOKEN_AUTOMATON_MAGIC = 0x54413031
+TOKEN_AUTOMATON_MAX_STATES = 4096      # the packed automaton's caps: a session's copy has a fixed size, so it never moves (captured graphs read it)
+TOKEN_AUTOMATON_MAX_EDGES = 32768
+TOKEN_AUTOMATON_INTS = 5 + TOKEN_AUTOMATON_MAX_STATES + 2 * TOKEN_AUTOMATON_MAX_EDGES
+
+
+def token_automaton_tensor(automaton=None, key=None):
+    """→ the int32 CPU table padt_token_automaton reads (layout in include/padt_hip.h; 5 + S + 2 E ints) for a generation.TokenAutomaton or
+    its `key` = (start, per-state tuples of (key, next state) sorted by key: the classes -3 / -2 / -1 first, then the text ids).
+    NotImplementedError above TOKEN_AUTOMATON_MAX_STATES states / TOKEN_AUTOMATON_MAX_EDGES edges."""
+    start, states = automaton.key if key is None else key
+    S, E = len(states), sum(len(s) for s in states)
+    if S > TOKEN_AUTOMATON_MAX_STATES or E > TOKEN_AUTOMATON_MAX_EDGES:
+        raise NotImplementedError(f"token_automaton: {S} states / {E} edges; the packed table holds at most {TOKEN_AUTOMATON_MAX_STATES} states "
+                                  f"and {TOKEN_AUTOMATON_MAX_EDGES} edges on the MI355X path")
+    offs, flat = [0], []
+    for s in states:
+        for k, nx in s:
+            flat += [int(k), int(nx)]
+        offs.append(len(flat) // 2)
+    return torch.tensor([TOKEN_AUTOMATON_MAGIC, S, E, int(start), *offs, *flat], dtype=torch.int32)
+
+
+def token_automaton(table, gen_cfg, vrt_off, tokens, step, unfinished, state, ban, n_cols, vocab, rules_ban=None):
+    """ban[b] = the step's bitmap for every row b of `state`: every column of [0, n_cols) banned except those the row's automaton state
+    allows (padt_token_automaton).  table int32 device copy of token_automaton_tensor (trailing slack allowed), gen_cfg the device
+    generation config (its EOS ids), vrt_off int32 (>= B + 1,), tokens int64 (>= B, T) the generated ids, step the device step counter,
+    unfinished int32 (>= B,), state int32 (B, 2) = (state, valid_for_step) — fill with -1 to reset —, ban int32 (>= B, words) with
+    32 * words >= n_cols; rules_ban: gen_rules' bitmap of this step (another buffer of ban's shape), OR-ed in.  → ban."""
+    for t in (table, vrt_off, step, unfinished, state, ban):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    B = state.shape[0]
+    assert table.dim() == 1 and table.numel() >= 5
+    assert gen_cfg.is_cuda and gen_cfg.is_contiguous() and gen_cfg.numel() * gen_cfg.element_size() >= 20
+    assert state.dim() == 2 and state.shape[1] == 2 and vrt_off.numel() >= B + 1 and unfinished.numel() >= B and step.numel() >= 1
+    assert tokens.dtype == torch.int64 and tokens.is_cuda and tokens.dim() == 2 and tokens.stride(1) == 1 and tokens.shape[0] >= B
+    assert ban.dim() == 2 and ban.shape[0] >= B and 0 < int(vocab) <= int(n_cols) <= 32 * ban.shape[1]
+    if rules_ban is not None:
+        assert rules_ban.dtype == torch.int32 and rules_ban.is_cuda and rules_ban.is_contiguous() and rules_ban.dim() == 2
+        assert rules_ban.shape[0] >= B and rules_ban.shape[1] == ban.shape[1] and rules_ban.data_ptr() != ban.data_ptr()
+    _lib.check(_lib.load().padt_token_automaton(_stream(), _p(table), table.numel(), _p(gen_cfg), _p(vrt_off), _p(tokens), tokens.stride(0),
+                                                _p(step), _p(unfinished), _p(state), _p(ban), ban.shape[1], _p(rules_ban), int(n_cols),
+                                                int(vocab), B), "padt_token_automaton")
+    return ban
+
+
 def gen_cfg_tensor(repetition_penalty=1.0, eos_ids=(), device="cuda", do_sample=False, seed=0, temperature=1.0, top_k=0, top_p=1.0,
                    write_back=False, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
     """Device copy of the generation-config slots the head / greedy / sampling kernels read:

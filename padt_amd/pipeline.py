@@ -20,14 +20,15 @@ def sample_grids(image_grid_thw, image_index):
 
 def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens=1024,
               schedule: Optional[Sequence] = None, need_thinking_mask=None, image_index=None, do_sample=False, min_p=None, typical_p=None,
-              epsilon_cutoff=None, eta_cutoff=None, forced_tokens=None, **gen_kw):
+              epsilon_cutoff=None, eta_cutoff=None, forced_tokens=None, token_automaton=None, **gen_kw):
     """→ (decoded dict of vl_decode, completions, labels, vrts).  ``input_ids`` carries LOCAL VRT ids (as a processor
     emits them) and is updated in place exactly like the reference's callers do.
     ``image_index``: sample b asks about image image_index[b] of the N <= B images given (generate(image_index=)); everything per sample
     (VRT id ranges, vl_decode) then follows ``image_grid_thw[image_index]``.
     ``do_sample`` (default: greedy, whatever the checkpoint's generation_config says) with ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` /
     ``eta_cutoff`` and, through ``**gen_kw``, ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: see generate().
-    ``forced_tokens``: generate(forced_tokens=) — GLOBAL ids, numbered like the generated part of ``sequences``."""
+    ``forced_tokens``: generate(forced_tokens=) — GLOBAL ids, numbered like the generated part of ``sequences``.
+    ``token_automaton``: generate(token_automaton=) — a generation.TokenAutomaton constraining what may be generated."""
     B = input_ids.shape[0]
     grid_in = image_grid_thw
     if image_index is not None:
@@ -37,7 +38,8 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
     out = model.generate(input_ids=ids, attention_mask=attention_mask, pixel_values=pixel_values,
                          image_grid_thw=grid_in, use_cache=True, max_new_tokens=max_new_tokens, do_sample=do_sample,
                          output_hidden_states=True, return_dict_in_generate=True, schedule=schedule, min_p=min_p, typical_p=typical_p,
-                         epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, forced_tokens=forced_tokens, **gen_kw)
+                         epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, forced_tokens=forced_tokens, token_automaton=token_automaton,
+                         **gen_kw)
     L = input_ids.shape[1]
     seq_local = processor.assign_to_local_vrt_id(out["sequences"].cpu(), image_grid_thw.cpu())
     completion_ids = seq_local[:, L:]
@@ -105,13 +107,14 @@ class PipelinedRunner:
     def submit(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens=1024, schedule=None,
                need_thinking_mask=None, sync_every=None, repetition_penalty=None, eos_token_id=None, no_repeat_ngram_size=None,
                bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None, do_sample=False, min_p=None,
-               typical_p=None, epsilon_cutoff=None, eta_cutoff=None, forced_tokens=None, **sampling):
+               typical_p=None, epsilon_cutoff=None, eta_cutoff=None, forced_tokens=None, token_automaton=None, **sampling):
         """image_index: see generate(); the batch's results are those of the expanded batch.
         do_sample (default: greedy) with min_p / typical_p / epsilon_cutoff / eta_cutoff and, through **sampling, temperature / top_k / top_p /
         seed: see generate(); batches whose resolved options differ in any of them (the seed included) do not share a decode group.
         output_token_logprobs / top_logprobs / output_patch_logprobs (through **sampling, see generate()): the decoded dict of the batch carries
         "token_logprobs" / "top_token_ids" + "top_logprobs" / "patch_logprobs" when asked; batches that disagree on them do not share a decode group.
-        forced_tokens: generate(forced_tokens=), each batch its own table; a batch that forces and one that does not never share a group."""
+        forced_tokens: generate(forced_tokens=), each batch its own table; a batch that forces and one that does not never share a group.
+        token_automaton: generate(token_automaton=); batches share a decode group only when their automata are equal."""
         done = []
         bid = self.n_batches
         self.n_batches += 1
@@ -124,6 +127,8 @@ class PipelinedRunner:
         hooks = dict(warpers=warpers) if any(v is not None for v in warpers.values()) else {}
         if forced_tokens is not None:
             hooks["forced"] = forced_tokens
+        if token_automaton is not None:
+            hooks["automaton"] = token_automaton
         for attempt in range(2):
             if self.cur is None:
                 while len(self.pending) > self.depth - 1:         # the lane about to be reused must have been collected
