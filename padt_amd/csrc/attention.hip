@@ -15,8 +15,6 @@
 #include <cstdlib>
 #include <cstdint>
 
-extern "C" void padt_set_error(const char* msg);
-
 namespace PADT_NS {
 
 typedef short v4s_t __attribute__((ext_vector_type(4)));
@@ -1073,8 +1071,7 @@ extern "C" int PADT_TWIN(padt_attn_varlen)(void* stream, const void* q, long ldq
         default: padt_set_error("padt_attn_varlen: head_dim must be 32, 64, 80 or 128"); return -1;
     }
 #undef PADT_ATTN_CASE
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -1112,8 +1109,7 @@ extern "C" int PADT_TWIN(padt_decode_attn)(void* stream, const void* q, const vo
             break;
         default: padt_set_error("padt_decode_attn: head_dim must be 32 or 128"); return -1;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -1141,8 +1137,7 @@ extern "C" int PADT_TWIN(padt_decode_attn_rope)(void* stream, const void* qkv, l
         const bool dsplit = cache_packed == 2 ? false : (cache_packed == 3 ? true : (long)n_kv_heads * batch <= 128);
         if (dsplit) hipLaunchKernelGGL((decode_attn_rope_packed_kernel<128, NW, true, 2>), dim3(n_kv_heads, batch, 2), dim3(NW * 64), lds, (hipStream_t)stream, pa);
         else hipLaunchKernelGGL((decode_attn_rope_packed_kernel<128, NW, true, 1>), dim3(n_kv_heads, batch), dim3(NW * 64), lds, (hipStream_t)stream, pa);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+        PADT_CHECK_LAUNCH();
         return 0;
     }
     const int nsplit = (max_len + 63) / 64;
@@ -1167,8 +1162,7 @@ extern "C" int PADT_TWIN(padt_decode_attn_rope)(void* stream, const void* qkv, l
             break;
         default: padt_set_error("padt_decode_attn_rope: head_dim must be 32 or 128"); return -1;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -1191,8 +1185,7 @@ extern "C" int padt_rope_table(void* stream, const int* pos3, const void* inv_fr
     const int n = batch * (head_dim / 2);
     hipLaunchKernelGGL(rope_table_kernel, dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, pos3,
                        (const float*)inv_freq, (float*)rope_cs, batch, head_dim / 2, sec0, sec1);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 #endif

@@ -69,6 +69,14 @@ struct PerDeviceOnce {
     }
 };
 
+// The tail of every entry point after its launches: a launch error becomes the library's error string and status -2.
+extern "C" void padt_set_error(const char* msg);
+#define PADT_CHECK_LAUNCH()                                              \
+    do {                                                                 \
+        hipError_t e_ = hipGetLastError();                               \
+        if (e_ != hipSuccess) { padt_set_error(hipGetErrorString(e_)); return -2; } \
+    } while (0)
+
 // In-kernel launch timing (bench.py's in-situ roofline): thread 0 of every block folds its start / end wall-clock tick (100 MHz constant
 // clock, s_memrealtime) into {min start, max end} of the launch's slot.  No barrier, no extra packet in the queue: unlike an event pair
 // around the launch it neither serialises the stream nor counts the dispatch gap.  prof == nullptr: two predicated-off instructions.

@@ -16,14 +16,6 @@
 #include "common.h"
 #include <cstdint>
 
-extern "C" void padt_set_error(const char* msg);
-
-#define PADT_CHECK_LAUNCH(name)                                          \
-    do {                                                                 \
-        hipError_t e_ = hipGetLastError();                               \
-        if (e_ != hipSuccess) { padt_set_error(hipGetErrorString(e_)); return -2; } \
-    } while (0)
-
 namespace {
 
 PADT_DEV void unpack4h(u32x2 v, float* f) { unpack4x(v, f); }   // this file is compiled for X = bf16 only (the (hi, lo) pairs)
@@ -427,7 +419,7 @@ extern "C" int padt_norm_split(void* stream, const void* x, long ldx, int x_f32,
     NormSplitArgs a{x, ldx, x_f32, idx, (const float*)add_f32, ld_add, add_div, (const x16_t*)w, eps, act, (const float*)pos_f32, ld_pos,
                     pos_rows, y0, ld_y0, y0_mode, y1, ld_y1, y1_mode, (int)rows, (int)D, (int)chunk};
     hipLaunchKernelGGL(norm_split_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
-    PADT_CHECK_LAUNCH("norm_split");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -440,7 +432,7 @@ extern "C" int padt_swiglu_split(void* stream, const void* gu_f32, long ld_gu, l
     long blocks = (rows * (I / 4) + 255) / 256;
     if (blocks > 32768) blocks = 32768;
     hipLaunchKernelGGL(swiglu_split_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)gu_f32, ld_gu, (int)I, (x16_t*)y_split, ld_y, rows);
-    PADT_CHECK_LAUNCH("swiglu_split");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -452,7 +444,7 @@ extern "C" int padt_layernorm_f32(void* stream, const void* x_f32, long ldx, con
     }
     hipLaunchKernelGGL(layernorm_f32_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)x_f32, ldx, (const x16_t*)w,
                        (const x16_t*)b, eps, (float*)y_f32, ldy, (int)rows, (int)D);
-    PADT_CHECK_LAUNCH("layernorm_f32");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -465,7 +457,7 @@ extern "C" int padt_rope_half_f32(void* stream, void* x, long ldx, const void* c
     if (blocks > 32768) blocks = 32768;
     hipLaunchKernelGGL(rope_half_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (float*)x, ldx,
                        (const float*)cos_t, (const float*)sin_t, ld_cs, T, n_heads, head_dim);
-    PADT_CHECK_LAUNCH("rope_half_f32");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -499,7 +491,7 @@ extern "C" int padt_attn_f32(void* stream, const void* q, long ldq, const void* 
         case 128: launch_attn_f32<128>(a, nseg, max_seqlen_q, max_seqlen_k, n_heads, s); break;
         default: padt_set_error("padt_attn_f32: head_dim must be 32, 64, 80 or 128"); return -1;
     }
-    PADT_CHECK_LAUNCH("attn_f32");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -773,7 +765,7 @@ extern "C" int padt_attn_f32_mfma(void* stream, const void* q, long ldq, const v
         case 128: launch_attn_f32_mfma<128>(a, nseg, max_seqlen_q, n_heads, s); break;
         default: padt_set_error("padt_attn_f32_mfma: head_dim must be 80 or 128"); return -1;
     }
-    PADT_CHECK_LAUNCH("attn_f32_mfma");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -784,6 +776,6 @@ extern "C" int padt_mask_scatter_f32(void* stream, const void* e2, long ld_e2, c
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(mask_scatter_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)e2, ld_e2,
                        (const float*)mask_tok, ld_tok, cu_patch, obj_w, (float*)masks_f32, n_obj, Hm4, Wm4, dm);
-    PADT_CHECK_LAUNCH("mask_scatter_f32");
+    PADT_CHECK_LAUNCH();
     return 0;
 }

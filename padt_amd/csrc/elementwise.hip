@@ -3,15 +3,7 @@
 #include "common.h"
 #include <cstdint>
 
-extern "C" void padt_set_error(const char* msg);
-
 namespace PADT_NS {
-
-#define PADT_CHECK_LAUNCH(name)                                          \
-    do {                                                                 \
-        hipError_t e_ = hipGetLastError();                               \
-        if (e_ != hipSuccess) { padt_set_error(hipGetErrorString(e_)); return -2; } \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // RMSNorm (HF Qwen2_5_VLRMSNorm, modeling_qwen2_5_vl.py:74-79; padt_decoder.py:71-74,143,156,170): one wave per row,
@@ -70,7 +62,7 @@ extern "C" int PADT_TWIN(padt_rmsnorm)(void* stream, const void* x, long ldx, co
     }
     hipLaunchKernelGGL(rmsnorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const x16_t*)x, ldx,
                        (const x16_t*)add, ld_add, add_div, (const x16_t*)w, (x16_t*)y, ldy, (int)rows, (int)D, eps, act);
-    PADT_CHECK_LAUNCH("rmsnorm");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -116,7 +108,7 @@ extern "C" int PADT_TWIN(padt_layernorm)(void* stream, const void* x, long ldx, 
     if ((D & 7) || (ldx & 7) || (ldy & 7)) { padt_set_error("padt_layernorm: D and strides must be multiples of 8"); return -1; }
     hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const x16_t*)x, ldx,
                        (const x16_t*)w, (const x16_t*)b, (x16_t*)y, ldy, (int)rows, (int)D, eps);
-    PADT_CHECK_LAUNCH("layernorm");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -180,7 +172,7 @@ extern "C" int PADT_TWIN(padt_rope_half)(void* stream, void* x, long ldx, const 
         if (bv > 32768) bv = 32768;
         hipLaunchKernelGGL(rope_half_vec_kernel, dim3((unsigned)bv), dim3(256), 0, (hipStream_t)stream, (x16_t*)x, ldx,
                            (const float*)cos_t, (const float*)sin_t, ld_cs, T, n_heads, head_dim);
-        PADT_CHECK_LAUNCH("rope_half");
+        PADT_CHECK_LAUNCH();
         return 0;
     }
     const long total = T * n_heads * (head_dim / 2);
@@ -188,7 +180,7 @@ extern "C" int PADT_TWIN(padt_rope_half)(void* stream, void* x, long ldx, const 
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(rope_half_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (x16_t*)x, ldx,
                        (const float*)cos_t, (const float*)sin_t, ld_cs, T, n_heads, head_dim);
-    PADT_CHECK_LAUNCH("rope_half");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -218,7 +210,7 @@ extern "C" int PADT_TWIN(padt_row_rstd)(void* stream, const void* x, long ldx, v
     if ((D & 7) || (ldx & 7) || ((uintptr_t)x & 15)) { padt_set_error("padt_row_rstd: D, ldx multiples of 8, x 16-byte aligned"); return -1; }
     hipLaunchKernelGGL(row_rstd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const x16_t*)x, ldx,
                        (float*)out_f32, (int)rows, (int)D, eps);
-    PADT_CHECK_LAUNCH("row_rstd");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -250,7 +242,7 @@ extern "C" int padt_pack_rows(void* stream, const void* src, long ld_src, void* 
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const x16_t*)src, ld_src,
                        (x16_t*)dst, ld_dst, (int)M, (int)(K / 8), to_packed);
-    PADT_CHECK_LAUNCH("pack_rows");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -277,7 +269,7 @@ extern "C" int padt_gather_rows(void* stream, const void* src, long ld_src, cons
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const x16_t*)src,
                        ld_src, idx, (x16_t*)dst, ld_dst, n, (int)(D / 8));
-    PADT_CHECK_LAUNCH("gather_rows");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -300,7 +292,7 @@ extern "C" int padt_gather_rows_f32(void* stream, const void* src, long ld_src, 
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(gather_rows_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                        (const float*)src, ld_src, idx, (float*)dst, ld_dst, n, (int)D);
-    PADT_CHECK_LAUNCH("gather_rows_f32");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -326,7 +318,7 @@ extern "C" int padt_scatter_rows_f32(void* stream, const void* src, long ld_src,
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(scatter_rows_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)src, ld_src, idx, (float*)dst,
                        ld_dst, n, (int)(D / 4));
-    PADT_CHECK_LAUNCH("scatter_rows_f32");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -358,7 +350,7 @@ extern "C" int PADT_TWIN(padt_add_rows)(void* stream, const void* a, long lda, c
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(add_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const x16_t*)a, lda,
                        (const x16_t*)b, ldb, b_rows, (x16_t*)y, ldy, n, (int)(D / 8));
-    PADT_CHECK_LAUNCH("add_rows");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -379,7 +371,7 @@ extern "C" int PADT_SYM(padt_cast_f32_, )(void* stream, const void* x, long ldx,
     if (blocks > 32768) blocks = 32768;
     hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)x,
                        ldx, (x16_t*)y, ldy, rows, (int)D, (int)D_pad, scale);
-    PADT_CHECK_LAUNCH("cast_f32_bf16");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -407,7 +399,7 @@ extern "C" int PADT_SYM(padt_cast_, _f32)(void* stream, const void* x, long ldx,
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const x16_t*)x, ldx, (float*)y, ldy,
                        rows, (int)(D / 8));
-    PADT_CHECK_LAUNCH("cast_bf16_f32");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -444,7 +436,7 @@ extern "C" int PADT_TWIN(padt_rmsnorm_f32)(void* stream, const void* x_f32, long
     }
     hipLaunchKernelGGL(rmsnorm_f32_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)x_f32, ldx,
                        (const x16_t*)w, (x16_t*)y, ldy, (int)rows, (int)D, eps);
-    PADT_CHECK_LAUNCH("rmsnorm_f32");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -460,7 +452,7 @@ extern "C" int padt_sigmoid_f32(void* stream, void* x, long n) {
     long blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(sigmoid_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (float*)x, n);
-    PADT_CHECK_LAUNCH("sigmoid_f32");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -501,7 +493,7 @@ extern "C" int padt_check_finite(void* stream, const void* x, long ldx, long row
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(check_finite_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned*)x, ldx * es, rows, vpr, kind,
                        flags, rows_per_flag);
-    PADT_CHECK_LAUNCH("check_finite");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -538,7 +530,7 @@ extern "C" int padt_embed_tokens(void* stream, const long* ids, const int* img_i
     hipLaunchKernelGGL(embed_tokens_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ids, img_index,
                        (const x16_t*)embed_table, (const x16_t*)proto, (const x16_t*)image_embeds, (x16_t*)out, T,
                        (int)vocab, (int)n_proto, (int)(D / 8), err_flag);
-    PADT_CHECK_LAUNCH("embed_tokens");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -660,7 +652,7 @@ extern "C" int PADT_TWIN(padt_llm_qkv_post)(void* stream, const void* qkv, long 
                   (x16_t*)k_pack, ld_kp, (x16_t*)k_cache, (x16_t*)vt_cache, (int)T, n_heads, n_kv_heads, head_dim,
                   s_max, sec0, sec1, cache_packed ? 1 : 0};
     hipLaunchKernelGGL(llm_qkv_post_kernel, dim3((unsigned)T), dim3(256), 0, (hipStream_t)stream, a);
-    PADT_CHECK_LAUNCH("llm_qkv_post");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -815,7 +807,7 @@ extern "C" int PADT_TWIN(padt_llm_qkv_post_shared)(void* stream, const void* qkv
                         (x16_t*)v_join, ld_vj, (x16_t*)k_cache, (x16_t*)vt_cache, dst_off, dst_sample, dst_slot, dst_row,
                         (int)T, n_heads, n_kv_heads, head_dim, s_max, batch, (int)n_join, sec0, sec1, cache_packed ? 1 : 0};
     hipLaunchKernelGGL(llm_qkv_post_shared_kernel, dim3((unsigned)T), dim3(256), 0, (hipStream_t)stream, a);
-    PADT_CHECK_LAUNCH("llm_qkv_post_shared");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -855,7 +847,7 @@ extern "C" int padt_mask_scatter(void* stream, const void* e2, long ld_e2, const
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(mask_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const x16_t*)e2,
                        ld_e2, (const x16_t*)mask_tok, ld_tok, cu_patch, obj_w, (float*)masks_f32, n_obj, Hm4, Wm4, dm);
-    PADT_CHECK_LAUNCH("mask_scatter");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -909,7 +901,7 @@ extern "C" int padt_mask_upsample_binarize(void* stream, const void* masks_f32, 
                    out_ld_row, (float*)up_f32, up_ld_obj, up_ld_row};
     const int bx = (max_dst_w + 255) / 256;
     hipLaunchKernelGGL(mask_upsample_binarize_kernel, dim3(bx, max_dst_h, n_obj), dim3(256), 0, (hipStream_t)stream, a);
-    PADT_CHECK_LAUNCH("mask_upsample_binarize");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -949,7 +941,7 @@ extern "C" int PADT_TWIN(padt_patchify_normalize)(void* stream, const void* img_
     const int n_patch = (H / patch) * (W / patch);
     hipLaunchKernelGGL(patchify_normalize_kernel, dim3(n_patch), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)img_u8,
                        H, W, (const float*)lut_f32, out, ld_out, out_bf16, patch, merge, temporal);
-    PADT_CHECK_LAUNCH("patchify_normalize");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -1001,7 +993,7 @@ extern "C" int padt_pack_results(void* stream, void* out_i32, long words, int n,
     long blocks = (words + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(pack_results_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    PADT_CHECK_LAUNCH("pack_results");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -1058,7 +1050,7 @@ extern "C" int PADT_TWIN(padt_quant_rows_fp8)(void* stream, const void* x, long 
     }
     hipLaunchKernelGGL(quant_rows_fp8_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const x16_t*)x, ldx,
                        (unsigned char*)x8, ld8, (float*)row_scale_f32, (int)rows, (int)K, norm_eps);
-    PADT_CHECK_LAUNCH("quant_rows_fp8");
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 

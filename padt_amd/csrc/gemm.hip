@@ -19,8 +19,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-extern "C" void padt_set_error(const char* msg);
-
 // Measurement surface: while a slot array is registered, every tile-GEMM call (M > 64) of this process — of either operand-type
 // instantiation — takes the next {start, end} slot and its kernels record their first block start / last block end in 100 MHz ticks.  The
 // caller initialises the slots to {~0, 0}.  The call counter is atomic (lanes of a pipelined runner launch GEMMs from one host thread today,
@@ -710,8 +708,7 @@ static int gemm_bf16_impl(void* stream, const void* A, long lda, const void* W, 
     unsigned long long* prof = (M > 64) ? next_prof_slot() : nullptr;
     if (M > 64 && PADT_TWIN(padt_gemm256_try)(stream, A, lda, W, ldw, bias, C, ldc, R, ldr, M, N, K, epilogue, tag256, rs, &rp, &done, resid_f32, lo_off, C2, ldc2, prof) == 0) {
         if (done >= M) {
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+            PADT_CHECK_LAUNCH();
             return 0;
         }
         // a peeled ragged tail (<= 64 rows): the rest of this function streams it through the skinny kernel
@@ -743,8 +740,7 @@ static int gemm_bf16_impl(void* stream, const void* A, long lda, const void* W, 
         case 6: dispatch_m<EPI_SWIGLU, false>(a, s); break;
         default: padt_set_error("padt_gemm_bf16: unsupported epilogue/out combination"); return -1;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -817,8 +813,7 @@ extern "C" int padt_gemm_split_rows(void* stream, const void* A_split, long lda,
     hipStream_t s = (hipStream_t)stream;
     if (w_packed) split_rows_launch<true>(a, M, epilogue, s);
     else split_rows_launch<false>(a, M, epilogue, s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 #endif
@@ -866,8 +861,7 @@ extern "C" int PADT_SYM(padt_gemm_rmsnorm_, )(void* stream, const void* A, long 
     hipStream_t s = (hipStream_t)stream;
     if (epilogue == EPI_SWIGLU) dispatch_norm<EPI_SWIGLU>(a, eps, s);
     else dispatch_norm<EPI_NONE>(a, eps, s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 
@@ -934,16 +928,14 @@ static int gemm_packed_impl(void* stream, const void* A, long lda, const void* W
         else if (epilogue == EPI_SWIGLU) { if (norm) dispatch_packed<EPI_SWIGLU, true, 3>(a, norm_eps, s); else dispatch_packed<EPI_SWIGLU, false, 3>(a, 0.f, s); }
         else if (epilogue == EPI_RESID) dispatch_packed<EPI_RESID, false, 3>(a, 0.f, s);
         else { if (norm) dispatch_packed<EPI_NONE, true, 3>(a, norm_eps, s); else dispatch_packed<EPI_NONE, false, 3>(a, 0.f, s); }
-        hipError_t e4 = hipGetLastError();
-        if (e4 != hipSuccess) { padt_set_error(hipGetErrorString(e4)); return -2; }
+        PADT_CHECK_LAUNCH();
         return 0;
     }
     if (resid32) {
         a.cs = wscale;
         if (wscale) dispatch_packed<EPI_RESID, false, 1, true>(a, 0.f, s);
         else dispatch_packed<EPI_RESID, false, 0, true>(a, 0.f, s);
-        hipError_t e2 = hipGetLastError();
-        if (e2 != hipSuccess) { padt_set_error(hipGetErrorString(e2)); return -2; }
+        PADT_CHECK_LAUNCH();
         return 0;
     }
     if (wscale) {
@@ -954,8 +946,7 @@ static int gemm_packed_impl(void* stream, const void* A, long lda, const void* W
     } else if (epilogue == EPI_SWIGLU) { if (norm) dispatch_packed<EPI_SWIGLU, true>(a, norm_eps, s); else dispatch_packed<EPI_SWIGLU, false>(a, 0.f, s); }
     else if (epilogue == EPI_RESID) dispatch_packed<EPI_RESID, false>(a, 0.f, s);
     else { if (norm) dispatch_packed<EPI_NONE, true>(a, norm_eps, s); else dispatch_packed<EPI_NONE, false>(a, 0.f, s); }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 

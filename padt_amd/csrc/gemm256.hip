@@ -35,7 +35,6 @@ extern "C" int padt_gemm_knobs(int mode256, int mf, int peel, int colsplit, int 
 #else
 extern Knobs256 padt_g_knobs256;
 #endif
-extern "C" void padt_set_error(const char* msg);
 
 namespace PADT_NS {
 static Knobs256& g_knobs = padt_g_knobs256;
@@ -669,8 +668,7 @@ extern "C" int PADT_TWIN(padt_gemm_fp8_impl)(void* stream, const void* A8, long 
         a.C = X32; a.ldc = ldx; a.R = (const x16_t*)X32; a.ldr = ldx; a.r_f32 = 1; a.C2 = (x16_t*)Xb; a.ldc2 = ldxb;
         run256_fp8<EPI_RESID, true>(a, pl.mf, s);
     } else { padt_set_error("padt_gemm_fp8: epilogue 0, 2 or 3"); return -1; }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    PADT_CHECK_LAUNCH();
     return 0;
 }
 

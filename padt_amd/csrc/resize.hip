@@ -7,8 +7,6 @@
 // precompute_coeffs / normalize_coeffs_8bpc do, padt_amd/preprocess.py) reproduces every byte.
 #include "common.h"
 
-extern "C" void padt_set_error(const char* msg);
-
 namespace {
 constexpr int PRECISION_BITS = 32 - 8 - 2;
 
@@ -54,7 +52,6 @@ extern "C" int padt_resample_pass_u8(void* stream, const void* in_u8, int in_h, 
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(resample_pass_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)in_u8, in_h,
                        in_w, channels, (unsigned char*)out_u8, out_h, out_w, bounds, kk, ksize, horizontal);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    PADT_CHECK_LAUNCH();
     return 0;
 }

@@ -12,8 +12,6 @@
 // Integer work: results are byte-identical to the host statement (tests/test_kernels_gpu.py, tests/golden/postprocess.npz).
 #include "common.h"
 
-extern "C" void padt_set_error(const char* msg);
-
 namespace {
 constexpr int NT = 1024, NW = NT / 64, ITEMS = 4;
 
@@ -231,7 +229,6 @@ extern "C" int padt_mask_rle(void* stream, const void* mask_u8, long ld_obj, lon
     if (packed_u8 != nullptr)
         hipLaunchKernelGGL(rle_pack_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, (const unsigned char*)str_u8, cap_str, str_len, n_obj,
                            (unsigned char*)packed_u8, cap_packed, offsets);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    PADT_CHECK_LAUNCH();
     return 0;
 }

@@ -18,10 +18,7 @@
 // rebuilt from scratch by every launch, so no bit outlives its step.  Bits past n_cols in the last word are zero (the rules' bits aside).
 // A table that is not what the packer writes makes the kernel return before its first write; a state whose offsets or successor leave
 // the table counts as off-automaton.  Every store lands in the row's own ban_words words or its own state pair.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-extern "C" void padt_set_error(const char* msg);
+#include "gen_cfg.h"
 
 namespace {
 
@@ -31,10 +28,8 @@ constexpr int TA_MAX_EDGES = 32768;          // ops.TOKEN_AUTOMATON_MAX_EDGES
 constexpr int TA_KEY_EOS = -3, TA_KEY_TEXT = -2, TA_KEY_VRT = -1;
 constexpr int TA_OFF = -1;                   // the off-automaton state
 
-struct GenCfgEos { float penalty; int eos[4]; };      // the leading slots of the generation config (vrt_head.hip: GenCfg)
-
 struct AutomatonArgs {
-    const int* table; long table_ints; const GenCfgEos* gen; const int* vrt_off; const long* tokens; long ld_tok; const int* step;
+    const int* table; long table_ints; const GenCfg* gen; const int* vrt_off; const long* tokens; long ld_tok; const int* step;
     const int* unfinished; int* state; unsigned* ban; long ban_words; const unsigned* rules_ban; int n_cols; int vocab;
 };
 
@@ -60,14 +55,7 @@ __device__ StateInfo state_info(const Tab& T, int s) {
     return r;
 }
 
-__device__ bool is_eos(const GenCfgEos* g, long tok) {
-    bool r = false;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) r = r || (g->eos[k] >= 0 && tok == (long)g->eos[k]);
-    return r;
-}
-
-__device__ int next_state(const Tab& T, int s, long tok, long v_lo, long v_hi, int vocab, const GenCfgEos* g) {
+__device__ int next_state(const Tab& T, int s, long tok, long v_lo, long v_hi, int vocab, const GenCfg* g) {
     const StateInfo si = state_info(T, s);
     if (!si.ok) return TA_OFF;
     int nx = -2;
@@ -81,7 +69,8 @@ __device__ int next_state(const Tab& T, int s, long tok, long v_lo, long v_hi, i
     }
     if (nx == -2) {
         if (tok >= v_lo && tok < v_hi) nx = si.nx_vrt;
-        else if (tok >= 0 && tok < (long)vocab) nx = is_eos(g, tok) ? si.nx_eos : si.nx_text;
+        // the listed ids alone, not gen_is_eos: the EOS class is what the bitmap below carves out of TEXT, and that is the GenCfg list
+        else if (tok >= 0 && tok < (long)vocab) nx = gen_eos_listed(g, tok) ? si.nx_eos : si.nx_text;
     }
     return (nx >= 0 && nx < T.S) ? nx : TA_OFF;
 }
@@ -185,10 +174,9 @@ extern "C" int padt_token_automaton(void* stream, const int* table, long table_i
         return -1;
     }
     if (rules_ban == ban) { padt_set_error("padt_token_automaton: the rules' bitmap and the output bitmap must be two buffers"); return -1; }
-    AutomatonArgs a{table, table_ints, (const GenCfgEos*)gen_cfg, vrt_off, tokens, ld_tokens, step, unfinished, state, (unsigned*)ban,
+    AutomatonArgs a{table, table_ints, (const GenCfg*)gen_cfg, vrt_off, tokens, ld_tokens, step, unfinished, state, (unsigned*)ban,
                     ban_words, (const unsigned*)rules_ban, (int)n_cols, (int)vocab};
     hipLaunchKernelGGL(token_automaton_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { padt_set_error(hipGetErrorString(e)); return -2; }
+    PADT_CHECK_LAUNCH();
     return 0;
 }

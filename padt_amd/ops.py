@@ -1,6 +1,7 @@
 """Thin torch-tensor → C-ABI wrappers.  PyTorch is used for device memory and streams only; every arithmetic op below
 is a hand-written gfx950 kernel in libpadt_hip.so (see include/padt_hip.h).  No fallbacks."""
 import operator
+import struct
 
 import torch
 
@@ -733,12 +734,19 @@ def vrt_head_nblk(vocab, n_proto):
     return _lib.load().padt_vrt_head_nblk(vocab, n_proto)
 
 
+def _head_call(name, hidden, table, proto, vrt_off, part_val, part_idx, eos, mode_table, step, logits, table_packed, B, gen_cfg, seen, extra):
+    """The argument list every padt_vrt_head* entry point starts with, then `extra`."""
+    _lib.check(_fn(name, _x16(hidden, table, proto, table_packed))(
+        _stream(), _p(hidden), hidden.stride(0), _p(table), table.shape[0], _p(proto), proto.shape[0], _p(vrt_off), _p(mode_table), _p(step),
+        _p(logits), logits.stride(0) if logits is not None else 0, _p(part_val), _p(part_idx), B, hidden.shape[1], eos, _p(table_packed),
+        _p(gen_cfg), _p(seen), seen.shape[1] if seen is not None else 0, *extra), name)
+
+
 def vrt_head(hidden, table, proto, vrt_off, part_val, part_idx, eos, mode_table=None, step=None, logits=None,
              table_packed=None, rows=None, gen_cfg=None, seen=None, ban=None, part_sum=None):
     """table_packed: pack_weight(table) — then `hidden` is a fragment-packed activation buffer holding `rows` valid rows.
     ban: int32 (rows, words) bitmap of banned table rows (gen_rules) → padt_vrt_head_ban; None is padt_vrt_head itself.
     part_sum: fp32 (nblk * rows) → padt_vrt_head_lse: also each block's Σ exp(logit - block max) per row (greedy_step(part_sum=, logprobs=))."""
-    dt = _x16(hidden, table, proto, table_packed)
     B = hidden.shape[0] if rows is None else rows
     name, extra = "padt_vrt_head", ()
     if ban is not None:
@@ -748,11 +756,7 @@ def vrt_head(hidden, table, proto, vrt_off, part_val, part_idx, eos, mode_table=
         assert part_sum.dtype == torch.float32 and part_sum.is_cuda and part_sum.is_contiguous()
         assert part_sum.numel() >= (table.shape[0] + proto.shape[0] + 15) // 16 * B
         name, extra = "padt_vrt_head_lse", ((_p(ban), ban.shape[1]) if ban is not None else (0, 0)) + (_p(part_sum),)
-    _lib.check(_fn(name, dt)(_stream(), _p(hidden), hidden.stride(0), _p(table), table.shape[0], _p(proto),
-                             proto.shape[0], _p(vrt_off), _p(mode_table), _p(step), _p(logits),
-                             logits.stride(0) if logits is not None else 0, _p(part_val), _p(part_idx),
-                             B, hidden.shape[1], eos, _p(table_packed), _p(gen_cfg), _p(seen),
-                             seen.shape[1] if seen is not None else 0, *extra), name)
+    _head_call(name, hidden, table, proto, vrt_off, part_val, part_idx, eos, mode_table, step, logits, table_packed, B, gen_cfg, seen, extra)
 
 
 def seen_init(ids, rows, seen):
@@ -904,21 +908,24 @@ def token_automaton(table, gen_cfg, vrt_off, tokens, step, unfinished, state, ba
     return ban
 
 
+# The generation-config slots.  csrc/gen_cfg.h (struct GenCfg, with a static_assert on every offset) is the layout's single definition;
+# this is its pack format, one 4-byte item per slot.
+GEN_CFG_FMT = "<f4iiIfifii4f"
+GEN_CFG_INTS = 16
+assert struct.calcsize(GEN_CFG_FMT) == 4 * GEN_CFG_INTS
+
+
 def gen_cfg_tensor(repetition_penalty=1.0, eos_ids=(), device="cuda", do_sample=False, seed=0, temperature=1.0, top_k=0, top_p=1.0,
                    write_back=False, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
     """Device copy of the generation-config slots the head / greedy / sampling kernels read:
     {float penalty; int eos[4]; int do_sample; unsigned seed; float temperature; int top_k; float top_p; int write_back; int pad;
     float min_p; float typical_p; float epsilon_cutoff; float eta_cutoff} — the last four read by warp_sample_rows alone, off at 0 / 1 / 0 / 0.
     write_back: sample_token overwrites its rows with the warped scores (output_scores / stopping criteria under sampling)."""
-    import struct
     eos = list(eos_ids)[:4] + [-1] * (4 - min(4, len(eos_ids)))
-    raw = struct.pack("<f4iiIfifii4f", float(repetition_penalty), *eos, 1 if do_sample else 0, int(seed) & 0xFFFFFFFF, float(temperature),
+    raw = struct.pack(GEN_CFG_FMT, float(repetition_penalty), *eos, 1 if do_sample else 0, int(seed) & 0xFFFFFFFF, float(temperature),
                       int(top_k), float(top_p), 1 if write_back else 0, 0, float(min_p), float(typical_p), float(epsilon_cutoff),
                       float(eta_cutoff))
     return torch.frombuffer(bytearray(raw), dtype=torch.int32).clone().to(device)
-
-
-GEN_CFG_INTS = 16
 
 
 def sample_token(logits, n_rows_table, gen_cfg, step, part_val, part_idx, batch):
@@ -1009,25 +1016,29 @@ def topk_logprob_rows(rows, n_cols, unfinished, step, workspace, batch, top_idx=
                                                       _p(patch_lp), p_cap, _p(workspace), int(batch)), "padt_topk_logprob_rows_f32")
 
 
+def _step_call(name, part_val, part_idx, nblk, hidden, hidden_buf, unfinished, tokens_out, cur_tok, step, slot, lens, pos3, eos, pad, advance,
+               gen_cfg, seen, extra):
+    """The argument list every step entry point (padt_greedy_step, _lp, padt_forced_step) starts with, then `extra`."""
+    B, D = hidden.shape
+    _lib.check(getattr(_lib.load(), name)(
+        _stream(), _p(part_val), _p(part_idx), nblk, B, D, eos, pad, tokens_out.shape[1], _p(unfinished), _p(tokens_out), _p(cur_tok), _p(step),
+        _p(slot), _p(lens), _p(pos3), _p(hidden), _p(hidden_buf), 1 if advance else 0, _p(gen_cfg), _p(seen),
+        seen.shape[1] if seen is not None else 0, *extra), name)
+
+
 def greedy_step(part_val, part_idx, nblk, hidden, hidden_buf, unfinished, tokens_out, cur_tok, step, slot, lens, pos3,
                 eos, pad, advance=True, gen_cfg=None, seen=None, part_sum=None, logprobs=None):
     """part_sum / logprobs (both or neither): vrt_head(part_sum=)'s block sums and the fp32 (B, T_max) buffer that gets the selected token's
     log-prob at the device step counter (padt_greedy_step_lp)."""
-    lib = _lib.load()
-    B, D = hidden.shape
+    name, extra = "padt_greedy_step", ()
     if part_sum is not None or logprobs is not None:
         assert part_sum is not None and logprobs is not None, "greedy_step: part_sum and logprobs go together"
+        B = hidden.shape[0]
         assert part_sum.dtype == torch.float32 and part_sum.is_cuda and part_sum.is_contiguous() and part_sum.numel() >= nblk * B
         assert logprobs.dtype == torch.float32 and logprobs.is_cuda and logprobs.is_contiguous() and logprobs.shape == (B, tokens_out.shape[1])
-        _lib.check(lib.padt_greedy_step_lp(_stream(), _p(part_val), _p(part_idx), nblk, B, D, eos, pad, tokens_out.shape[1],
-                                           _p(unfinished), _p(tokens_out), _p(cur_tok), _p(step), _p(slot), _p(lens), _p(pos3),
-                                           _p(hidden), _p(hidden_buf), 1 if advance else 0, _p(gen_cfg), _p(seen),
-                                           seen.shape[1] if seen is not None else 0, _p(part_sum), _p(logprobs)), "padt_greedy_step_lp")
-        return
-    _lib.check(lib.padt_greedy_step(_stream(), _p(part_val), _p(part_idx), nblk, B, D, eos, pad, tokens_out.shape[1],
-                                    _p(unfinished), _p(tokens_out), _p(cur_tok), _p(step), _p(slot), _p(lens), _p(pos3),
-                                    _p(hidden), _p(hidden_buf), 1 if advance else 0, _p(gen_cfg), _p(seen),
-                                    seen.shape[1] if seen is not None else 0), "padt_greedy_step")
+        name, extra = "padt_greedy_step_lp", (_p(part_sum), _p(logprobs))
+    _step_call(name, part_val, part_idx, nblk, hidden, hidden_buf, unfinished, tokens_out, cur_tok, step, slot, lens, pos3, eos, pad, advance,
+               gen_cfg, seen, extra)
 
 
 def _chk_forced(forced, B):
@@ -1038,7 +1049,6 @@ def vrt_head_probe(hidden, table, proto, vrt_off, part_val, part_idx, eos, part_
                    table_packed=None, rows=None, gen_cfg=None, seen=None, ban=None):
     """vrt_head(part_sum=) that also writes probe_val[b] = the processed logit of column forced[b][*step] (padt_vrt_head_probe): forced int32
     (rows, t_forced) table columns, negative = a free step (nothing written for the row); probe_val fp32 (rows,); step the device counter."""
-    dt = _x16(hidden, table, proto, table_packed)
     B = hidden.shape[0] if rows is None else rows
     assert part_sum.dtype == torch.float32 and part_sum.is_cuda and part_sum.is_contiguous()
     assert part_sum.numel() >= (table.shape[0] + proto.shape[0] + 15) // 16 * B
@@ -1047,12 +1057,8 @@ def vrt_head_probe(hidden, table, proto, vrt_off, part_val, part_idx, eos, part_
     assert step is not None and step.dtype == torch.int32
     if ban is not None:
         assert ban.dtype == torch.int32 and ban.is_cuda and ban.dim() == 2 and ban.is_contiguous() and ban.shape[0] >= B
-    _lib.check(_fn("padt_vrt_head_probe", dt)(_stream(), _p(hidden), hidden.stride(0), _p(table), table.shape[0], _p(proto),
-                                              proto.shape[0], _p(vrt_off), _p(mode_table), _p(step), _p(logits),
-                                              logits.stride(0) if logits is not None else 0, _p(part_val), _p(part_idx),
-                                              B, hidden.shape[1], eos, _p(table_packed), _p(gen_cfg), _p(seen),
-                                              seen.shape[1] if seen is not None else 0, _p(ban), ban.shape[1] if ban is not None else 0,
-                                              _p(part_sum), _p(forced), forced.shape[1], _p(probe_val)), "padt_vrt_head_probe")
+    _head_call("padt_vrt_head_probe", hidden, table, proto, vrt_off, part_val, part_idx, eos, mode_table, step, logits, table_packed, B, gen_cfg,
+               seen, (_p(ban), ban.shape[1] if ban is not None else 0, _p(part_sum), _p(forced), forced.shape[1], _p(probe_val)))
 
 
 def forced_step(part_val, part_idx, nblk, hidden, hidden_buf, unfinished, tokens_out, cur_tok, step, slot, lens, pos3, eos, pad, forced, n_cols,
@@ -1060,7 +1066,7 @@ def forced_step(part_val, part_idx, nblk, hidden, hidden_buf, unfinished, tokens
     """greedy_step with the caller's tokens (padt_forced_step): an unfinished row b with 0 <= forced[b][*step] < n_cols takes that column as its
     token, every other row is the free step.  part_sum / logprobs / probe_val (all or none): vrt_head_probe's outputs and the (B, T_max)
     log-prob buffer — a forced row gets (probe - max) - log Σ, -inf for a -inf column."""
-    B, D = hidden.shape
+    B = hidden.shape[0]
     _chk_forced(forced, B)
     lp = (part_sum, logprobs, probe_val)
     if any(t is not None for t in lp):
@@ -1068,11 +1074,8 @@ def forced_step(part_val, part_idx, nblk, hidden, hidden_buf, unfinished, tokens
         assert part_sum.dtype == torch.float32 and part_sum.is_cuda and part_sum.is_contiguous() and part_sum.numel() >= nblk * B
         assert logprobs.dtype == torch.float32 and logprobs.is_cuda and logprobs.is_contiguous() and logprobs.shape == (B, tokens_out.shape[1])
         assert probe_val.dtype == torch.float32 and probe_val.is_cuda and probe_val.is_contiguous() and probe_val.numel() >= B
-    _lib.check(_lib.load().padt_forced_step(_stream(), _p(part_val), _p(part_idx), nblk, B, D, eos, pad, tokens_out.shape[1],
-                                            _p(unfinished), _p(tokens_out), _p(cur_tok), _p(step), _p(slot), _p(lens), _p(pos3),
-                                            _p(hidden), _p(hidden_buf), 1 if advance else 0, _p(gen_cfg), _p(seen),
-                                            seen.shape[1] if seen is not None else 0, _p(part_sum), _p(logprobs), _p(forced), forced.shape[1],
-                                            _p(probe_val), int(n_cols)), "padt_forced_step")
+    _step_call("padt_forced_step", part_val, part_idx, nblk, hidden, hidden_buf, unfinished, tokens_out, cur_tok, step, slot, lens, pos3, eos, pad,
+               advance, gen_cfg, seen, (_p(part_sum), _p(logprobs), _p(forced), forced.shape[1], _p(probe_val), int(n_cols)))
 
 
 def forced_override(part_idx, forced, step, unfinished, n_cols, batch):
