@@ -364,6 +364,21 @@ int  padt_vrt_head_probe(void* stream, const void* hidden, long ldh, const void*
                          long ld_logits, void* part_val, void* part_idx, long batch, long D, int eos,
                          const void* embed_table_packed, const void* gen_cfg, const void* seen, long seen_words,
                          const void* ban, long ban_words, void* part_sum, const int* forced, long t_forced, void* probe_val);
+/* generate(logit_bias=, patch_bias=, exponential_decay_length_penalty=): every head above with an additive score bias and / or the exponential
+ * length decay, applied where a logit becomes a score, in HF's processor order:
+ *   x = logit + bias[column]                       bias: fp32 [vocab + n_proto] over the table columns, nullable; -inf is a ban
+ *   the repetition penalty on x, then the logit mask / mode table / ban bitmap (-inf), as in padt_vrt_head_ban
+ *   an EOS column (eos, or one of gen_cfg's ids): v = v + |v| * decay[*step]      decay: fp32 [t_decay], nullable; an entry of 0, or *step
+ *   outside [0, t_decay), changes nothing; product and sum round separately (HF's two tensor ops); -inf stays -inf (HF: NaN)
+ * The written row, the arg-max partials, part_sum and probe_val all describe the edited row.  The head is chosen by the nullable outputs:
+ * forced != NULL → padt_vrt_head_probe (part_sum, probe_val, t_forced > 0 required), else part_sum != NULL → padt_vrt_head_lse, else
+ * padt_vrt_head_ban; with bias = decay = NULL the call IS that head, bit for bit. */
+int  padt_vrt_head_bias(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab, const void* proto,
+                        long n_proto, const int* vrt_off, const int* mode_table, const int* step, void* logits_f32,
+                        long ld_logits, void* part_val, void* part_idx, long batch, long D, int eos,
+                        const void* embed_table_packed, const void* gen_cfg, const void* seen, long seen_words,
+                        const void* ban, long ban_words, void* part_sum, const int* forced, long t_forced, void* probe_val,
+                        const void* bias, const void* decay, long t_decay);
 /* padt_greedy_step(_lp) with the forced table: after the arg-max (and the LSE fold) an unfinished row with a forced entry in [0, n_cols) takes
  * it as its token — appended, fed to the next step, entered in `seen`, an EOS id finishes the row — even where its score is -inf (the
  * no-candidate → pad branch applies to free rows only).  part_sum / logprobs / probe_val: all three (then logprobs[b][*step] =

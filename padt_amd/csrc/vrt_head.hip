@@ -35,7 +35,17 @@ struct HeadArgs {
     float* part_sum;                   // LSE kernels: [nblk][B] Σ exp(v - block max) over the block's 16 masked logits (token log-probs)
     const int* forced; int t_forced;   // PROBE kernels: [B][t_forced] table columns the caller forces (generate(forced_tokens=)), < 0 = free step
     float* probe_val;                  // PROBE kernels: [B] the processed logit at forced[m][*step]
+    const float* bias;                 // optional [V + NP] additive bias over the table columns (generate(logit_bias=, patch_bias=)): logit + bias[row]
+    const float* decay; int t_decay;   // optional [t_decay] a[t] of generate(exponential_decay_length_penalty=), read at *step: 0 = no change
 };
+
+// HF's ExponentialDecayLengthPenalty on one EOS column: v + |v| * a, the product and the sum rounded separately as HF's two tensor ops are (a
+// contraction into one FMA would change the last bit).  -inf stays -inf (HF: NaN).
+PADT_DEV float eos_decay(float v, float a) {
+#pragma clang fp contract(off)
+    const float pen = fabsf(v) * a;
+    return v == -INFINITY ? v : v + pen;
+}
 
 // PACKED: text rows come from a fragment-packed copy of the table ([V/16][D/32][64 lanes][8], ops.pack_weight — every wave
 // load is 1 KiB contiguous) and the hidden rows from the 16-row fragment-packed activation layout; prototype rows (rebuilt
@@ -49,7 +59,12 @@ struct HeadArgs {
 // row (best = -inf) yields s = 0.  MFMA order, cross-wave sum and the (best, idx) partials are those of LSE = false, bit for bit.
 // PROBE (padt_vrt_head_probe, an LSE kernel plus one store): the lane that owns column forced[m][*step] of sample m also writes the value v it
 // writes to `logits` — masked, penalised, ban-filtered — to probe_val[m]; a negative entry, or a step outside [0, t_forced), writes nothing.
-template <int MT, int NT, bool PACKED, bool LSE = false, bool PROBE = false>
+// EDIT (padt_vrt_head_bias with a bias vector and / or a decay table; every other launch is EDIT = false and compiles to the code it was
+// before the flag existed — whether two runtime null tests would have cost the plain step anything was not settled, profiles/score_bias.md §2): HF's
+// processor order — the bias is added to the raw logit BEFORE the repetition penalty (SequenceBias comes first), the mask / schedule / ban
+// filter follows, and a surviving EOS column (the config's id or one of gen's) becomes v + |v| * decay[*step] LAST
+// (ExponentialDecayLengthPenalty).  Every consumer — the written row, the arg-max and LSE partials, the probe value — sees the edited value.
+template <int MT, int NT, bool PACKED, bool LSE = false, bool PROBE = false, bool EDIT = false>
 __global__ __launch_bounds__(256) void vrt_head_kernel(HeadArgs p) {
     extern __shared__ __attribute__((aligned(16))) float red_raw[];
     typedef float RedT[NT * MT][64][4];
@@ -119,11 +134,30 @@ __global__ __launch_bounds__(256) void vrt_head_kernel(HeadArgs p) {
     __syncthreads();
     const int mode = (p.mode_table && p.step) ? p.mode_table[*p.step] : 0;
     const float pen = (p.gen && p.seen) ? p.gen->penalty : 1.0f;
+    float dec = 0.f;                                              // EDIT: this step's a[t]; 0 (before `start`, past the table, no table): no edit
+    int dcol[5] = {-1, -1, -1, -1, -1};                           // ... and the columns it edits, read once: the config's EOS id and gen's list
+    if constexpr (EDIT) {
+        if (p.decay) { const int st = *p.step; if (st >= 0 && st < p.t_decay) dec = p.decay[st]; }
+        if (dec != 0.f) {
+            dcol[0] = p.eos;
+            if (p.gen) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) dcol[1 + k] = p.gen->eos[k];
+            }
+        }
+    }
     for (int q = wave; q < NT * MT; q += 4) {                     // (table block, sample block) pairs this wave finishes
         const int i = q / MT, j = q % MT;
         const int blk = blockIdx.x * NT + i;
         if (blk >= nblk) continue;
         const int n0 = blk * 16;
+        float bv[4] = {0.f, 0.f, 0.f, 0.f};                       // EDIT: the lane's four bias values, asked for before the LDS reads below
+        if constexpr (EDIT) {
+            if (p.bias) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { const int row = n0 + fq * 4 + r; if (row < NTOT) bv[r] = p.bias[row]; }
+            }
+        }
         f32x4 sum = *reinterpret_cast<f32x4*>(&red[0][q][lane][0]);
 #pragma unroll
         for (int w = 1; w < 4; ++w) sum += *reinterpret_cast<f32x4*>(&red[w][q][lane][0]);
@@ -148,8 +182,14 @@ __global__ __launch_bounds__(256) void vrt_head_kernel(HeadArgs p) {
             }
             if (p.ban && ok) ok = !((p.ban[(long)m * p.ban_words + (row >> 5)] >> (row & 31)) & 1u);   // a pure ban: the penalty no longer matters
             float sc = sum[r];
+            if constexpr (EDIT) {
+                if (p.bias) sc += bv[r];
+            }
             if (pen != 1.0f && ok && ((p.seen[(long)m * p.seen_words + (row >> 5)] >> (row & 31)) & 1u)) sc = sc < 0.f ? sc * pen : sc / pen;
-            const float v = ok ? sc : -INFINITY;
+            float v = ok ? sc : -INFINITY;
+            if constexpr (EDIT) {
+                if (dec != 0.f && row < p.V && (row == dcol[0] || row == dcol[1] || row == dcol[2] || row == dcol[3] || row == dcol[4])) v = eos_decay(v, dec);
+            }
             if (p.logits && m < p.B && row < NTOT) p.logits[(long)m * p.ldl + row] = v;
             if constexpr (PROBE) {
                 if (row == fcol && row < NTOT) p.probe_val[m] = v;   // fcol >= 0 only for m < B; one lane owns the column
@@ -180,28 +220,28 @@ __global__ __launch_bounds__(256) void vrt_head_kernel(HeadArgs p) {
     }
 }
 
-template <int MT, int NT, bool PACKED, bool LSE, bool PROBE>
+template <int MT, int NT, bool PACKED, bool LSE, bool PROBE, bool EDIT>
 static void launch_head(const HeadArgs& a, int nblk, hipStream_t s) {
     constexpr int lds = 4 * NT * MT * 64 * 16;
     if constexpr (lds > 64 * 1024) {
         static PerDeviceOnce once;
-        once.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vrt_head_kernel<MT, NT, PACKED, LSE, PROBE>),
+        once.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vrt_head_kernel<MT, NT, PACKED, LSE, PROBE, EDIT>),
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
     }
-    hipLaunchKernelGGL((vrt_head_kernel<MT, NT, PACKED, LSE, PROBE>), dim3((nblk + NT - 1) / NT), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((vrt_head_kernel<MT, NT, PACKED, LSE, PROBE, EDIT>), dim3((nblk + NT - 1) / NT), dim3(256), lds, s, a);
 }
 
-template <bool LSE, bool PROBE = false>
+template <bool LSE, bool PROBE = false, bool EDIT = false>
 static void dispatch_head(const HeadArgs& a, int nblk, hipStream_t s) {
     if (a.Ep) {                                                 // NT = 4 table blocks per thread block (2 at 128 rows): profiles/r03_head_nt_ab.log
-        if (a.B <= 16) launch_head<1, 4, true, LSE, PROBE>(a, nblk, s);
-        else if (a.B <= 32) launch_head<2, 4, true, LSE, PROBE>(a, nblk, s);
-        else if (a.B <= 64) launch_head<4, 4, true, LSE, PROBE>(a, nblk, s);
-        else launch_head<8, 2, true, LSE, PROBE>(a, nblk, s);
-    } else if (a.B <= 16) launch_head<1, 1, false, LSE, PROBE>(a, nblk, s);
-    else if (a.B <= 32) launch_head<2, 1, false, LSE, PROBE>(a, nblk, s);
-    else if (a.B <= 64) launch_head<4, 1, false, LSE, PROBE>(a, nblk, s);
-    else launch_head<8, 1, false, LSE, PROBE>(a, nblk, s);
+        if (a.B <= 16) launch_head<1, 4, true, LSE, PROBE, EDIT>(a, nblk, s);
+        else if (a.B <= 32) launch_head<2, 4, true, LSE, PROBE, EDIT>(a, nblk, s);
+        else if (a.B <= 64) launch_head<4, 4, true, LSE, PROBE, EDIT>(a, nblk, s);
+        else launch_head<8, 2, true, LSE, PROBE, EDIT>(a, nblk, s);
+    } else if (a.B <= 16) launch_head<1, 1, false, LSE, PROBE, EDIT>(a, nblk, s);
+    else if (a.B <= 32) launch_head<2, 1, false, LSE, PROBE, EDIT>(a, nblk, s);
+    else if (a.B <= 64) launch_head<4, 1, false, LSE, PROBE, EDIT>(a, nblk, s);
+    else launch_head<8, 1, false, LSE, PROBE, EDIT>(a, nblk, s);
 }
 
 static int vrt_head_impl(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab,
@@ -209,7 +249,8 @@ static int vrt_head_impl(void* stream, const void* hidden, long ldh, const void*
                          const int* step, void* logits_f32, long ld_logits, void* part_val, void* part_idx,
                          long batch, long D, int eos, const void* embed_table_packed, const void* gen_cfg,
                          const void* seen, long seen_words, const void* ban, long ban_words, void* part_sum = nullptr,
-                         const int* forced = nullptr, long t_forced = 0, void* probe_val = nullptr) {
+                         const int* forced = nullptr, long t_forced = 0, void* probe_val = nullptr, const void* bias = nullptr,
+                         const void* decay = nullptr, long t_decay = 0) {
     if (batch <= 0) return 0;
     if (batch > 128 || (D & 7) || (ldh & 7)) { padt_set_error("padt_vrt_head: batch <= 128, D % 8 == 0 required"); return -1; }
     if (embed_table_packed && ((D & 31) || (vocab & 15) || ((uintptr_t)embed_table_packed & 15) || ((uintptr_t)hidden & 15))) {
@@ -219,12 +260,17 @@ static int vrt_head_impl(void* stream, const void* hidden, long ldh, const void*
     HeadArgs a{(const x16_t*)hidden, ldh, (const x16_t*)embed_table, (int)vocab, (const x16_t*)proto, (int)n_proto,
                vrt_off, mode_table, step, (float*)logits_f32, ld_logits, (float*)part_val, (int*)part_idx, (int)batch,
                (int)D, eos, (const x16_t*)embed_table_packed, (const GenCfg*)gen_cfg, (const unsigned*)seen, seen_words,
-               (const unsigned*)ban, ban_words, (float*)part_sum, forced, (int)t_forced, (float*)probe_val};
+               (const unsigned*)ban, ban_words, (float*)part_sum, forced, (int)t_forced, (float*)probe_val, (const float*)bias,
+               (const float*)decay, (int)t_decay};
     if (seen && seen_words * 32 < vocab + n_proto) { padt_set_error("padt_vrt_head: seen bitmap narrower than the table"); return -1; }
     if (ban && ban_words * 32 < vocab + n_proto) { padt_set_error("padt_vrt_head_ban: ban bitmap narrower than the table"); return -1; }
     const int nblk = (int)padt_vrt_head_nblk(vocab, n_proto);
     hipStream_t s = (hipStream_t)stream;
-    if (forced) dispatch_head<true, true>(a, nblk, s);
+    if (bias || decay) {                                        // the EDIT instantiations: the only launches that read the two pointers
+        if (forced) dispatch_head<true, true, true>(a, nblk, s);
+        else if (part_sum) dispatch_head<true, false, true>(a, nblk, s);
+        else dispatch_head<false, false, true>(a, nblk, s);
+    } else if (forced) dispatch_head<true, true>(a, nblk, s);
     else if (part_sum) dispatch_head<true>(a, nblk, s);
     else dispatch_head<false>(a, nblk, s);
     PADT_CHECK_LAUNCH();
@@ -281,6 +327,28 @@ extern "C" int PADT_TWIN(padt_vrt_head_probe)(void* stream, const void* hidden, 
     return vrt_head_impl(stream, hidden, ldh, embed_table, vocab, proto, n_proto, vrt_off, mode_table, step, logits_f32, ld_logits, part_val,
                          part_idx, batch, D, eos, embed_table_packed, gen_cfg, seen, seen_words, ban, ban_words, part_sum, forced, t_forced,
                          probe_val);
+}
+
+// Every head above with an additive score bias and / or the exponential length decay (generate(logit_bias=, patch_bias=,
+// exponential_decay_length_penalty=)); bias fp32 [vocab + n_proto] or null, decay fp32 [t_decay] or null (then t_decay is ignored), read at *step.
+// The head is chosen as the other entry points choose it: forced != null → the probe head (part_sum, probe_val and t_forced required), else
+// part_sum != null → the LSE head, else the plain head; ban is optional in all three.  bias = decay = null is that head, bit for bit.
+extern "C" int PADT_TWIN(padt_vrt_head_bias)(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab,
+                             const void* proto, long n_proto, const int* vrt_off, const int* mode_table,
+                             const int* step, void* logits_f32, long ld_logits, void* part_val, void* part_idx,
+                             long batch, long D, int eos, const void* embed_table_packed, const void* gen_cfg,
+                             const void* seen, long seen_words, const void* ban, long ban_words, void* part_sum,
+                             const int* forced, long t_forced, void* probe_val, const void* bias, const void* decay, long t_decay) {
+    if (batch <= 0) return 0;
+    if (forced && (part_sum == nullptr || probe_val == nullptr || step == nullptr || t_forced <= 0 || t_forced > 0x7fffffffL)) {
+        padt_set_error("padt_vrt_head_bias: a forced table needs part_sum, the step counter, t_forced > 0 and probe_val"); return -1;
+    }
+    if (decay && (step == nullptr || t_decay <= 0 || t_decay > 0x7fffffffL)) {
+        padt_set_error("padt_vrt_head_bias: the decay table needs the step counter and 0 < t_decay < 2^31"); return -1;
+    }
+    return vrt_head_impl(stream, hidden, ldh, embed_table, vocab, proto, n_proto, vrt_off, mode_table, step, logits_f32, ld_logits, part_val,
+                         part_idx, batch, D, eos, embed_table_packed, gen_cfg, seen, seen_words, ban, ban_words, part_sum,
+                         forced, forced ? t_forced : 0, forced ? probe_val : nullptr, bias, decay, decay ? t_decay : 0);
 }
 
 }  // namespace PADT_NS

@@ -2,6 +2,7 @@
 arguments are ignored, refused or unknown), ``GenOptions`` — the ONE named, hashable value a call's arguments and the checkpoint's
 generation_config.json resolve to, carried from ``generate_launch`` through the decode session to a re-run on the bf16 twin — and
 ``StepMode``, the part of it that selects the decode step's kernel sequence (one captured graph per value)."""
+import math
 import numbers
 from dataclasses import InitVar, dataclass, fields
 from typing import NamedTuple, Optional
@@ -31,7 +32,7 @@ _GENERATE_REJECTED = ("inputs", "prefix_allowed_tokens_fn", "assistant_model", "
                       "negative_prompt_ids", "negative_prompt_attention_mask", "pixel_values_videos", "video_grid_thw", "second_per_grid_ts",
                       "inputs_embeds", "past_key_values", "position_ids", "cache_position", "rope_deltas", "stop_strings", "max_time",
                       "sequence_bias", "forced_bos_token_id", "forced_eos_token_id",
-                      "exponential_decay_length_penalty", "prompt_lookup_num_tokens", "dola_layers", "labels")
+                      "prompt_lookup_num_tokens", "dola_layers", "labels")
 
 
 def check_generate_kwargs(kwargs: dict, max_new_tokens, max_length, prompt_len) -> int:
@@ -371,10 +372,180 @@ def check_token_automaton(token_automaton, vocab_size):
     return token_automaton.check(vocab_size)
 
 
+# ------------------------------------------------------------------------------------------------ generate(logit_bias=, patch_bias=, exponential_decay_length_penalty=)
+# The three edits that ADD to a score.  The specification (score_bias_row below is its plain statement; the head kernel, padt_vrt_head_bias,
+# is compared against it bit for bit), for a row's masked logit l of table column c at step t (tokens generated so far), in HF's processor
+# order — SequenceBias, RepetitionPenalty, the bans, ExponentialDecayLengthPenalty:
+#   1. x = l + bias[c]: one fp32 add; bias[c] is the call's logit_bias entry of a text column, the row's patch_bias entry of its own patch
+#      column, 0 where nothing is listed; -inf is a legal bias and acts as a ban
+#   2. the repetition penalty on x          3. logit mask, schedule, ban bitmap: -inf
+#   4. c one of the call's EOS ids and t > start: v = v + |v| * a[t], a[t] = fp32(factor ** (t - start) - 1) computed in double and rounded
+#      once (decay_table); the product and the sum round separately.  A column that is already -inf stays -inf (HF produces NaN there).
+# NOT HF's sequence_bias (multi-token sequences), min_new_tokens, min_length or forced_eos_token_id: those stay refused by name.
+def _bias_value(name, v, where):
+    if isinstance(v, torch.Tensor) and v.numel() == 1:
+        v = v.item()
+    if isinstance(v, bool) or not isinstance(v, numbers.Real):
+        raise ValueError(f"{name}: a bias is a real number, got {v!r} ({where})")
+    v = float(v)
+    if math.isnan(v) or v == math.inf or abs(v) > 3.4028234663852886e38 and v != -math.inf:
+        raise ValueError(f"{name}: a bias must be a finite fp32 value or -inf (a ban), got {v!r} ({where})")
+    return float(torch.tensor(v, dtype=torch.float32))               # what the device adds
+
+
+def check_logit_bias(logit_bias, vocab_size):
+    """generate(logit_bias=) → its normal form: a tuple of (id, bias) pairs sorted by id, the biases rounded to fp32, zero entries dropped
+    (adding 0 is the call without the entry); None for None / nothing left.  Accepts a dict {id: bias} or a list of [id, bias] pairs (the
+    OpenAI / vLLM shapes; string keys that spell integers included).  Text ids only: a VRT id raises NotImplementedError pointing to
+    patch_bias, NaN / +inf / a repeated or malformed entry ValueError, all naming logit_bias."""
+    name = "generate(logit_bias=...)"
+    if logit_bias is None:
+        return None
+    if isinstance(logit_bias, dict):
+        items = list(logit_bias.items())
+    else:
+        try:
+            items = [tuple(e) for e in logit_bias]
+        except TypeError:
+            raise ValueError(f"{name}: a dict {{id: bias}} or a list of [id, bias] pairs is required, got {logit_bias!r}") from None
+    out = {}
+    for e in items:
+        if len(e) != 2:
+            raise ValueError(f"{name}: an entry is an [id, bias] pair, got {e!r}")
+        k, v = e
+        if isinstance(k, str) and k.strip().lstrip("+-").isdigit():
+            k = int(k)
+        if isinstance(k, torch.Tensor) and k.numel() == 1 and not (k.dtype.is_floating_point or k.dtype == torch.bool):
+            k = int(k)
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+            raise ValueError(f"{name}: token ids must be integers, got {k!r}")
+        k = int(k)
+        if k < 0:
+            raise ValueError(f"{name}: id {k} is outside the vocabulary")
+        if k >= int(vocab_size):
+            raise NotImplementedError(f"{name}: id {k} is not a text id (0 <= id < {int(vocab_size)}): a VRT id means another patch in every "
+                                      "sample — bias a sample's own patches with patch_bias")
+        if k in out:
+            raise ValueError(f"{name}: id {k} is listed twice")
+        out[k] = _bias_value(name, v, f"id {k}")
+    key = tuple(sorted((k, v) for k, v in out.items() if v != 0.0))
+    return key or None
+
+
+def check_patch_bias(patch_bias, B, patches=None, grids=None):
+    """generate(patch_bias=) → its normal form: a list of B entries, each None or an fp32 CPU tensor over that row's own patches in VRT-id
+    order; None when every entry is None.  An entry may be a 1-D tensor / sequence of the row's patch count or a 2-D map (h/2, w/2) over the
+    merged patch grid (flattened row-major: VRT-id order).  A map keeps its shape until `grids` is given, so that it can still be checked
+    against the row's grid; with `grids` every entry comes back 1-D.  patches: the rows' patch counts, grids: their merged grids (h/2, w/2),
+    once known (modeling._launch runs the check again with both).  ValueError naming patch_bias and the row for a wrong batch size, rank,
+    length or map shape, NaN or +inf."""
+    name = "generate(patch_bias=...)"
+    if patch_bias is None:
+        return None
+    if isinstance(patch_bias, torch.Tensor):
+        raise ValueError(f"{name}: a list of {int(B)} per-row entries (None, a 1-D tensor or a 2-D map) is required, got one tensor of shape "
+                         f"{tuple(patch_bias.shape)}")
+    try:
+        rows = list(patch_bias)
+    except TypeError:
+        raise ValueError(f"{name}: a list of per-row entries is required, got {patch_bias!r}") from None
+    if len(rows) != int(B):
+        raise ValueError(f"{name}: {len(rows)} entries for a batch of {int(B)} samples")
+    out = []
+    for b, r in enumerate(rows):
+        if r is None:
+            out.append(None)
+            continue
+        try:
+            t = torch.as_tensor(r).detach().cpu()
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"{name}: row {b}: a float tensor is required, got {type(r).__name__}") from None
+        if t.dtype == torch.bool or t.dtype.is_complex or t.dim() not in (1, 2):
+            raise ValueError(f"{name}: row {b}: a 1-D float tensor over the row's patches or a 2-D (h/2, w/2) map is required, got dtype "
+                             f"{t.dtype}, shape {tuple(t.shape)}")
+        t = t.to(torch.float64)
+        if bool(torch.isnan(t).any()) or bool((t == math.inf).any()):
+            raise ValueError(f"{name}: row {b}: NaN or +inf (a bias is finite or -inf, a ban)")
+        t32 = t.to(torch.float32)
+        if bool((torch.isinf(t32) & ~torch.isinf(t)).any()):
+            raise ValueError(f"{name}: row {b}: a value beyond fp32's range")
+        if t.dim() == 2 and grids is not None and tuple(t.shape) != tuple(int(x) for x in grids[b]):
+            raise ValueError(f"{name}: row {b}: a {tuple(t.shape)} map for a merged patch grid of {tuple(int(x) for x in grids[b])}")
+        if patches is not None and t.numel() != int(patches[b]):
+            raise ValueError(f"{name}: row {b}: {t.numel()} values for {int(patches[b])} patches")
+        out.append((t32.reshape(-1) if grids is not None else t32).contiguous())      # a map keeps its shape until it was checked against the grid
+    return out if any(t is not None for t in out) else None
+
+
+def check_decay_length_penalty(value, max_new_tokens=None):
+    """generate(exponential_decay_length_penalty=(start, factor)) → (int start, float factor), None for None.  start: an integer >= 0, counted
+    in generated tokens as HF counts it; factor: a positive real; factor ** max_new_tokens must be finite in fp32 (the largest entry of the
+    device table).  ValueError naming the argument."""
+    name = "generate(exponential_decay_length_penalty=...)"
+    if value is None:
+        return None
+    try:
+        start, factor = value
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: a (start_index, decay_factor) pair is required, got {value!r}") from None
+    if isinstance(start, bool) or not isinstance(start, numbers.Integral) or int(start) < 0:
+        raise ValueError(f"{name}: start_index must be an integer >= 0, got {start!r}")
+    if isinstance(factor, bool) or not isinstance(factor, numbers.Real) or not (float(factor) > 0.0) or math.isinf(float(factor)):
+        raise ValueError(f"{name}: decay_factor must be a positive real number, got {factor!r}")
+    start, factor = int(start), float(factor)
+    if max_new_tokens is not None:
+        try:
+            top = factor ** int(max_new_tokens)
+        except OverflowError:
+            top = math.inf
+        if not top <= 3.4028234663852886e38:
+            raise ValueError(f"{name}: decay_factor ** max_new_tokens = {factor!r} ** {int(max_new_tokens)} is not finite in fp32")
+    return (start, factor)
+
+
+def decay_table(decay, t_max, n_steps=None) -> torch.Tensor:
+    """The device table of the decay (start, factor): fp32 (t_max,) with a[t] = fp32(factor ** (t - start) - 1) for start < t < n_steps —
+    computed in double with Python's pow, as HF's ExponentialDecayLengthPenalty computes its scalar, and rounded once, as its tensor multiply
+    rounds it — and 0 (no edit) everywhere else.  n_steps: the call's max_new_tokens, the range check_decay_length_penalty validated (a
+    session's table may be longer than the call: the steps past n_steps are never run, and their powers may not even fit a double); None:
+    t_max.  A power beyond the double range is +inf, never an exception.  None → all 0."""
+    t_max = int(t_max)
+    n = t_max if n_steps is None else max(0, min(t_max, int(n_steps)))
+    vals = [0.0] * t_max
+    if decay is not None:
+        start, factor = decay
+        for t in range(start + 1, n):
+            try:
+                vals[t] = factor ** (t - start) - 1
+            except OverflowError:
+                vals[t] = math.inf
+    return torch.tensor(vals, dtype=torch.float64).to(torch.float32)
+
+
+def score_bias_row(logits, bias=None, penalty=1.0, seen=None, banned=None, eos_ids=(), a_t=0.0):
+    """Steps 1-4 of the specification above on fp32 rows (..., n): logits — the masked logits (−inf outside the mask); bias (n,) or None; seen /
+    banned — bool (..., n) masks or None; a_t — the decay table's entry of this step (0: no edit).  Plain torch, one rounding per step."""
+    x = logits.to(torch.float32)
+    if bias is not None:
+        x = x + bias.to(torch.float32)
+    if float(penalty) != 1.0 and seen is not None:
+        pen = torch.tensor(float(penalty), dtype=torch.float32, device=x.device)
+        x = torch.where(seen, torch.where(x < 0, x * pen, x / pen), x)
+    if banned is not None:
+        x = torch.where(banned, torch.full_like(x, -math.inf), x)
+    a = torch.tensor(float(a_t), dtype=torch.float32, device=x.device)
+    if float(a) != 0.0:
+        x = x.clone()
+        for e in dict.fromkeys(int(e) for e in eos_ids):
+            v = x[..., e]
+            x[..., e] = torch.where(torch.isinf(v) & (v < 0), v, v + v.abs() * a)
+    return x
+
+
 # generate()'s named parameters a generation_config may carry: an explicit argument (not None) wins, as in HF (padt.py:436)
 _GENERATE_CONFIG_NAMED = ("max_new_tokens", "max_length", "do_sample", "repetition_penalty", "eos_token_id", "pad_token_id", "temperature", "top_k",
                           "top_p", "no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens", "min_p", "typical_p",
-                          "epsilon_cutoff", "eta_cutoff")
+                          "epsilon_cutoff", "eta_cutoff", "exponential_decay_length_penalty")
 # ... and those whose value is this path's own default either way (hidden states and the dict output are what its callers consume)
 _GENERATE_CONFIG_OWN = ("use_cache", "output_hidden_states", "return_dict_in_generate")
 
@@ -418,6 +589,7 @@ class Sampling(NamedTuple):
         return self.min_p > 0.0 or self.typical_p < 1.0 or self.epsilon_cutoff > 0.0 or self.eta_cutoff > 0.0
 
 
+DECAY_OFF = (0, 1.0)     # exponential_decay_length_penalty spelled as off: HF's processor with factor 1 adds |v| * 0; here it IS no decay
 _SAMPLING_OFF = dict(min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0)
 WARPER_NAMES = tuple(_SAMPLING_OFF)
 
@@ -459,6 +631,7 @@ class StepMode(NamedTuple):
     warpers: bool = False            # min_p / typical_p / epsilon_cutoff / eta_cutoff: padt_warp_sample_rows_f32 warps the row and draws
     forced: bool = False             # generate(forced_tokens=): the probe head / padt_forced_step / padt_forced_override read the session's table
     automaton: bool = False          # generate(token_automaton=): padt_token_automaton writes the bitmap the head reads (the union with the rules')
+    bias: bool = False               # logit_bias / patch_bias / exponential_decay_length_penalty: padt_vrt_head_bias reads the session's bias vector and decay table
 
 
 @dataclass(frozen=True)
@@ -482,14 +655,23 @@ class GenOptions:
     # decode group only when their automata are equal: a session holds ONE packed table), not a dataclass field and not in generate_kwargs():
     # the automaton object travels with its batch to a re-run.
     automaton: InitVar[Optional[tuple]] = None
+    # generate(logit_bias=) in check_logit_bias' normal form, generate(exponential_decay_length_penalty=) as (start, factor), and "this batch
+    # carries a patch_bias" (the tensors travel with their batch like the forced table).  Init-only attributes like the two above — part of
+    # equality, hash and repr; spelled for a re-run by bias_kwargs(), not by generate_kwargs().
+    logit_bias: InitVar[Optional[tuple]] = None
+    decay: InitVar[Optional[tuple]] = None
+    patch_bias: InitVar[bool] = False
 
-    def __post_init__(self, forced, automaton):
+    def __post_init__(self, forced, automaton, logit_bias, decay, patch_bias):
         object.__setattr__(self, "forced", bool(forced))
         object.__setattr__(self, "automaton", automaton)
+        object.__setattr__(self, "logit_bias", logit_bias or None)
+        object.__setattr__(self, "decay", None if decay is None else (int(decay[0]), float(decay[1])))
+        object.__setattr__(self, "patch_bias", bool(patch_bias))
 
     def _key(self):
-        # every field, whatever is added later, and the two init-only attributes
-        return tuple(getattr(self, f.name) for f in fields(self)) + (self.forced, self.automaton)
+        # every field, whatever is added later, and the init-only attributes
+        return tuple(getattr(self, f.name) for f in fields(self)) + (self.forced, self.automaton, self.logit_bias, self.decay, self.patch_bias)
 
     def __eq__(self, other):
         return self._key() == other._key() if isinstance(other, GenOptions) else NotImplemented
@@ -501,6 +683,9 @@ class GenOptions:
         a = self.automaton                                        # the key of a large table is long: its size and hash stand for it
         auto = "None" if a is None else f"<{len(a[1])} states, {sum(len(e) for e in a[1])} edges, start {a[0]}, #{hash(a) & 0xffffffff:08x}>"
         args = [f"{f.name}={getattr(self, f.name)!r}" for f in fields(self)] + [f"forced={self.forced!r}", f"automaton={auto}"]
+        lb = self.logit_bias
+        args += [f"logit_bias={lb!r}" if lb is None or len(lb) <= 8 else f"logit_bias=<{len(lb)} ids, #{hash(lb) & 0xffffffff:08x}>",
+                 f"decay={self.decay!r}", f"patch_bias={self.patch_bias!r}"]
         return f"GenOptions({', '.join(args)})"
 
     @property
@@ -512,6 +697,11 @@ class GenOptions:
     def write_back(self) -> bool:
         """The sampling kernel overwrites its rows with the warped scores: whoever reads the row after it must see what was sampled from."""
         return self.sampling is not None and bool(self.keep_scores or self.token_logprobs or self.want_rows or self.sampling.warpers)
+
+    @property
+    def score_bias(self) -> bool:
+        """One of the three additive edits is on: the head is padt_vrt_head_bias with the session's bias vector and decay table."""
+        return self.logit_bias is not None or self.decay is not None or self.patch_bias
 
     @property
     def reads_prompt(self) -> bool:
@@ -529,13 +719,19 @@ class GenOptions:
         return StepMode(sampling=self.sampling is not None, keep_scores=self.keep_scores, keep_logits=self.keep_logits, rules=self.rules is not None,
                         token_logprobs=self.token_logprobs, top_k=self.top_logprobs, patches=self.patch_logprobs, processors=bool(processors),
                         reference=bool(reference), warpers=self.sampling is not None and self.sampling.warpers, forced=self.forced,
-                        automaton=self.automaton is not None)
+                        automaton=self.automaton is not None, bias=self.score_bias)
 
     def warper_kwargs(self) -> dict:
         """min_p / typical_p / epsilon_cutoff / eta_cutoff as explicit generate() keywords (with_warpers values), next to generate_kwargs():
         off is spelled 0.0 / 1.0, never None, so that no generation_config can switch a warper back on."""
         s = self.sampling
         return dict(_SAMPLING_OFF) if s is None else {name: getattr(s, name) for name in WARPER_NAMES}
+
+    def bias_kwargs(self) -> dict:
+        """logit_bias / exponential_decay_length_penalty as explicit generate() keywords, next to generate_kwargs() and warper_kwargs().
+        Off is spelled as off ({} / (0, 1.0): no entry, a factor whose table is all 0), never None, so that no generation_config can switch
+        the decay back on.  The patch_bias tensors travel with their batch."""
+        return dict(logit_bias=dict(self.logit_bias or ()), exponential_decay_length_penalty=self.decay or DECAY_OFF)
 
     def generate_kwargs(self) -> dict:
         """Explicit generate() arguments that resolve back to these options under ANY generation_config: what is off is spelled as off (0, [],

@@ -8,8 +8,8 @@ post-processing (utils.py:252-266) and the two JSONL files with the reference's 
 Tokenisation / chat templating is the caller's (`prepare`): it needs the checkpoint's tokenizer files, which are not part of
 this repository.  `prepare(samples) -> dict(input_ids (local VRT ids), attention_mask, pixel_values, image_grid_thw,
 image_sizes [(w, h)], ids [image_id])`; optionally `image_index` (several samples on one image: generate(image_index=), with
-`pixel_values` / `image_grid_thw` holding each image once) and `forced_tokens` (the batch's completion tokens to force:
-generate(forced_tokens=)).
+`pixel_values` / `image_grid_thw` holding each image once), `forced_tokens` (the batch's completion tokens to force:
+generate(forced_tokens=)) and `patch_bias` (one entry per sample over its own patches: generate(patch_bias=)).
 """
 import json
 import os
@@ -22,10 +22,11 @@ from .postprocess import postprocess_results
 def infer_dataset(model, processor, dataset: Sequence, prepare: Callable, output_dir: str, batch_size: int = 1,
                   datasetname: str = "coco", suffix: str = "", rank: int = 0, world: int = 1, max_new_tokens: int = 1024,
                   depth: int = 2, merge: int = 4, schedule=None, repetition_penalty=None, eos_token_id=None,
-                  token_automaton=None):
+                  token_automaton=None, logit_bias=None, exponential_decay_length_penalty=None):
     """repetition_penalty / eos_token_id: None = the checkpoint's generation_config.json (model.generation_config), as HF's
     generate() inside the reference's loop applies it (utils.py:230-236 → padt.py:436).
-    token_automaton: generate(token_automaton=) for every batch of the run (e.g. the dataset's category names followed by their VRTs)."""
+    token_automaton: generate(token_automaton=) for every batch of the run (e.g. the dataset's category names followed by their VRTs).
+    logit_bias / exponential_decay_length_penalty: generate()'s, for every batch of the run; a batch's own patch prior comes from `prepare`."""
     os.makedirs(output_dir, exist_ok=True)
     f_res = os.path.join(output_dir, f"{datasetname}_{rank}_pred_results_{suffix}.json")
     f_comp = os.path.join(output_dir, f"{datasetname}_{rank}_pred_comp_{suffix}.json")
@@ -56,9 +57,11 @@ def infer_dataset(model, processor, dataset: Sequence, prepare: Callable, output
         meta.append({"ids": list(b["ids"]), "image_sizes": list(b["image_sizes"])})
         extra = {"image_index": b["image_index"]} if b.get("image_index") is not None else {}
         extra["forced_tokens"] = b.get("forced_tokens")           # None: nothing forced
+        extra["patch_bias"] = b.get("patch_bias")                 # None: no prior over the patches
         drain(runner.submit(b["input_ids"], b["attention_mask"], b["pixel_values"], b["image_grid_thw"],
                             max_new_tokens=max_new_tokens, schedule=schedule, repetition_penalty=repetition_penalty,
-                            eos_token_id=eos_token_id, token_automaton=token_automaton, **extra))
+                            eos_token_id=eos_token_id, token_automaton=token_automaton, logit_bias=logit_bias,
+                            exponential_decay_length_penalty=exponential_decay_length_penalty, **extra))
         n += len(b["ids"])
     drain(runner.flush())
     return {"samples": n, "results_file": f_res, "completions_file": f_comp}

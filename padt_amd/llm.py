@@ -19,7 +19,7 @@ import torch
 
 from . import ops
 from .config import PaDTConfig
-from .generation import GenOptions, StepMode
+from .generation import GenOptions, StepMode, decay_table
 
 I32 = torch.int32
 
@@ -372,6 +372,8 @@ class DecodeSession:
         self.atab = None                 # mode.automaton (generate(token_automaton=)): the packed table, ops.TOKEN_AUTOMATON_INTS int32 (fixed size) ...
         self.astate = None               # ... each row's (state, valid_for_step) [B][2] ...
         self.aban = None                 # ... and the bitmap padt_token_automaton writes for the head (with rules: its union with `ban`) [B][words]
+        self.bias = None                 # mode.bias (generate(logit_bias=, patch_bias=)): fp32 [V + np_max] added to the raw logit of its column ...
+        self.decay = None                # ... and exponential_decay_length_penalty's a[t] fp32 [t_max], read at the device step counter (generation.decay_table)
         self.rope_cs = z(B, hd // 2, 2, dt=torch.float32)
         self.n_qkv = (cfg.num_attention_heads + 2 * Hkv) * hd
         self.graphs = {}                 # captured decode-step graph per mode (different kernel sequences and output buffers)
@@ -417,8 +419,8 @@ class DecodeSession:
         ops.check_finite(self.hn, self.nf, rows_per_flag=1, rows=B)      # sticky per-row flag, read once per generate (modeling.generate_collect)
         self.head_and_select(self.hn, advance=True)
 
-    def begin(self, opts: GenOptions, p_max: int = 0, processors: bool = False, step_fn=None, automaton=None):
-        """Start of a generate with these options (p_max: the largest patch count of one sample; processors: the caller's logits_processor runs in
+    def begin(self, opts: GenOptions, p_max: int = 0, processors: bool = False, step_fn=None, automaton=None, n_steps=None):
+        """Start of a generate with these options (p_max: the largest patch count of one sample; n_steps: the call's max_new_tokens, None = the session's t_max — the decay table is filled up to there; processors: the caller's logits_processor runs in
         the hooked loop; step_fn: precision="reference"'s step): the gen_cfg slots and the rule table the captured step reads, the step mode,
         and the log-prob buffers, allocated on first use and set to their finished-row values (0 / -1 / -inf) for every generate that asks.
         top_logprobs uses the leading B * t_max * k elements of ONE flat (ids, values) pair sized for k = 32 as [B][t_max][k], so a captured
@@ -466,6 +468,17 @@ class DecodeSession:
                 self.aban = torch.zeros_like(self.ban)
             self.atab[: tab.numel()].copy_(tab.to(dev, non_blocking=True))
             self.astate.fill_(-1)                                # no row's state is valid: the first launch starts every row at the start state
+        if opts.score_bias:                                      # text columns and the decay now; each batch of the group adds its patch segment (modeling._launch)
+            if self.bias is None:
+                self.bias = torch.zeros(self.cfg.vocab_size + self.np_max, device=dev, dtype=torch.float32)
+                self.decay = torch.zeros(self.t_max, device=dev, dtype=torch.float32)
+            else:
+                self.bias.zero_()
+            if opts.logit_bias is not None:
+                ids = torch.tensor([k for k, _ in opts.logit_bias], dtype=torch.long)
+                val = torch.tensor([v for _, v in opts.logit_bias], dtype=torch.float32)
+                self.bias.index_copy_(0, ids.to(dev), val.to(dev))
+            self.decay.copy_(decay_table(opts.decay, self.t_max, n_steps).to(dev, non_blocking=True))
         if opts.rules is not None:
             self.rules.copy_(ops.gen_rules_tensor(key=opts.rules).to(dev, non_blocking=True))
             self.hist_len.zero_()                                # rows no batch of the group fills: an empty prompt
@@ -498,7 +511,10 @@ class DecodeSession:
         if hp is not None:                                   # packed table + packed hidden rows: 1 KiB contiguous wave loads
             ops.pack_rows(hn, self.hn_pk, self.B, to_packed=True)
             head_in, head_kw = self.hn_pk, dict(head_kw, table_packed=hp, rows=self.B)
-        if probe is not None:
+        if m.bias:                                           # the additive edits: the same heads, reading the session's bias vector and decay table
+            ops.vrt_head_bias(head_in, W["llm.head"], self.proto, self.vrt_off, self.part_val, self.part_idx, cfg.eos_token_id, bias=self.bias,
+                              decay=self.decay, part_sum=psum, forced=fc if probe is not None else None, probe_val=probe, **head_kw)
+        elif probe is not None:
             ops.vrt_head_probe(head_in, W["llm.head"], self.proto, self.vrt_off, self.part_val, self.part_idx, cfg.eos_token_id, psum, fc, probe,
                                **head_kw)
         else:

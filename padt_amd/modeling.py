@@ -21,8 +21,8 @@ import torch
 from . import _lib, ops
 from .config import PaDTConfig
 from .decoder import PaDTDecoder
-from .generation import (_GENERATE_CONFIG_NAMED, _GENERATE_CONFIG_OWN, check_forced_tokens, check_generate_kwargs, check_token_automaton,  # noqa: F401
-                         check_top_logprobs, completion_logprobs, forced_tokens_active, generation_config_fields, resolve_options, with_warpers,
+from .generation import (_GENERATE_CONFIG_NAMED, _GENERATE_CONFIG_OWN, check_decay_length_penalty, check_forced_tokens, check_generate_kwargs,  # noqa: F401
+                         check_logit_bias, check_patch_bias, check_token_automaton, check_top_logprobs, completion_logprobs, forced_tokens_active, generation_config_fields, resolve_options, with_warpers,
                          WARPER_NAMES)
 from .llm import MODE, LanguageModel, check_shared_destinations, plan_prompt, plan_prompt_shared
 from .vision import VisionEncoder
@@ -204,6 +204,8 @@ class PaDTForConditionalGeneration:
         for k in ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff"):      # validated where they are used (generation.resolve_options)
             if d.get(k) is not None:
                 setattr(g, k, float(d[k]))
+        if d.get("exponential_decay_length_penalty") is not None:             # (start, factor); the range check needs the call's max_new_tokens
+            g.exponential_decay_length_penalty = check_decay_length_penalty(d["exponential_decay_length_penalty"])
         return g
 
     @classmethod
@@ -347,6 +349,32 @@ class PaDTForConditionalGeneration:
         the automaton is a table in device memory, so one captured graph per step mode serves every automaton, and batches share a decode
         group only when their automata are equal.  ``ValueError`` naming ``token_automaton`` for anything that is not a ``TokenAutomaton`` or
         names an id outside the text vocabulary.
+        Keywords ``logit_bias`` / ``patch_bias`` / ``exponential_decay_length_penalty``: the three edits that ADD to a score, applied by the
+        logit head itself where a logit becomes a score (``padt_vrt_head_bias``), so the arg-max, ``token_logprobs``, the sampler and its
+        warpers, ``.scores``, ``top_logprobs`` / ``patch_logprobs``, the value a forced token is scored at and the caller's ``logits_processor``
+        all see the edited row.  The order is HF's processor order (generation.score_bias_row is the specification): the bias is added to the
+        masked logit FIRST (where HF's ``SequenceBiasLogitsProcessor`` sits), then the repetition penalty, then the bans, the decay last.
+        ``logit_bias`` (the OpenAI / vLLM name): a dict ``{id: bias}`` or a list of ``[id, bias]`` pairs over TEXT ids, one fp32 add per
+        listed column; ``-inf`` is a legal bias and a ban; NaN / ``+inf`` raise ``ValueError``, a VRT id ``NotImplementedError`` pointing to
+        ``patch_bias``.  With an EOS id it is a soft length control.  It is NOT HF's ``sequence_bias`` (multi-token sequences), which stays
+        refused by name like ``min_new_tokens``, ``min_length`` and ``forced_eos_token_id``.
+        ``patch_bias``: a list of B entries — ``None``, a 1-D float tensor over the row's own patches in VRT-id order, or a 2-D ``(h/2, w/2)``
+        map over its merged patch grid — added to the row's own patch columns: a prior over where the row points (``-inf`` outside a region of
+        interest, on patches of objects already found, a saliency map of the previous frame).  ``patch_logprobs`` is then ``-inf`` outside
+        the region and renormalised inside.  With ``image_index`` every query carries its own entry.  ``ValueError`` naming the argument and
+        the row for a wrong length or shape, NaN or ``+inf``.
+        ``exponential_decay_length_penalty=(start, factor)`` (HF's ``ExponentialDecayLengthPenalty``; defaults from ``generation_config=`` /
+        generation_config.json): once more than ``start`` tokens were generated (t > start), every EOS column's score v becomes
+        ``v + |v| * fp32(factor ** (t - start) - 1)``, product and sum rounded separately as HF's two tensor ops are.  ``start`` an integer >= 0,
+        ``factor`` a positive real with ``factor ** max_new_tokens`` finite in fp32, else ``ValueError``.  One deviation: an EOS column that is
+        already ``-inf`` (banned, masked by a ``schedule``) stays ``-inf`` where HF produces NaN.
+        Bias vector and decay table live in the session's device memory: one captured graph (its own step mode) serves every value;
+        batches share a decode group only when ``logit_bias`` and the decay are equal and both or neither carry a ``patch_bias``.  Without the
+        three the call is what it was: same kernels, same step mode.  ``output_logits=True`` under greedy decoding is refused with any of them;
+        under ``do_sample=True`` it is served as with the bans: ``.logits`` are the rows the head wrote, BEFORE the warpers but already carrying
+        the bias and the decay (HF's raw logits carry no processor).  A ``generation_config=`` that sets no decay leaves the checkpoint's
+        ``exponential_decay_length_penalty`` in force, as for every other named field here (HF replaces the model's config wholesale);
+        pass ``exponential_decay_length_penalty=(0, 1.0)`` to switch it off.
         """
         if synced_gpus:
             raise NotImplementedError("generate(synced_gpus=True) is the ZeRO-3 / FSDP lock-step loop (padt.py:445,670): every rank holds a full "
@@ -355,12 +383,14 @@ class PaDTForConditionalGeneration:
         min_p, typical_p, epsilon_cutoff, eta_cutoff = (kwargs.pop(k, None) for k in WARPER_NAMES)
         forced_tokens = kwargs.pop("forced_tokens", None)             # ... and so is the table of forced completion tokens
         token_automaton = kwargs.pop("token_automaton", None)         # ... and the automaton that says which tokens may follow
+        logit_bias, patch_bias = kwargs.pop("logit_bias", None), kwargs.pop("patch_bias", None)      # ... and the three additive score edits
+        decay = kwargs.pop("exponential_decay_length_penalty", None)
         if generation_config is not None:
             named = dict(max_new_tokens=max_new_tokens, max_length=max_length, do_sample=do_sample, repetition_penalty=repetition_penalty,
                          eos_token_id=eos_token_id, pad_token_id=pad_token_id, temperature=temperature, top_k=top_k, top_p=top_p,
                          no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens,
                          begin_suppress_tokens=begin_suppress_tokens, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff,
-                         eta_cutoff=eta_cutoff)
+                         eta_cutoff=eta_cutoff, exponential_decay_length_penalty=decay)
             for k, v in generation_config_fields(generation_config).items():
                 if k in _GENERATE_CONFIG_NAMED:
                     if named[k] is None:
@@ -376,7 +406,7 @@ class PaDTForConditionalGeneration:
                 elif k not in _GENERATE_CONFIG_OWN:
                     kwargs.setdefault(k, v)                           # the keyword policy below names what this path does not implement
             (max_new_tokens, max_length, do_sample, repetition_penalty, eos_token_id, pad_token_id, temperature, top_k, top_p, no_repeat_ngram_size,
-             bad_words_ids, suppress_tokens, begin_suppress_tokens, min_p, typical_p, epsilon_cutoff, eta_cutoff) = (
+             bad_words_ids, suppress_tokens, begin_suppress_tokens, min_p, typical_p, epsilon_cutoff, eta_cutoff, decay) = (
                 named[k] for k in _GENERATE_CONFIG_NAMED)
         max_new_tokens = check_generate_kwargs(kwargs, max_new_tokens, max_length, None if input_ids is None else input_ids.shape[1])
         top_logprobs = check_top_logprobs(top_logprobs)
@@ -397,6 +427,8 @@ class PaDTForConditionalGeneration:
             hooks = dict(hooks or {}, forced=forced_tokens)           # the same channel
         if token_automaton is not None:
             hooks = dict(hooks or {}, automaton=token_automaton)
+        if logit_bias is not None or patch_bias is not None or decay is not None:
+            hooks = dict(hooks or {}, bias=dict(logit_bias=logit_bias, patch_bias=patch_bias, decay=decay))
         if output_logits:
             pen = self.generation_config.repetition_penalty if repetition_penalty is None else repetition_penalty
             if float(pen) != 1.0 or schedule is not None or processors is not None:
@@ -441,6 +473,9 @@ class PaDTForConditionalGeneration:
         generation config decides); warpers alone keep the captured step and merged groups.  ``hooks=dict(forced=F)``: generate()'s
         ``forced_tokens`` — per-batch data like the prompt; batches share a group only when both force or neither does.
         ``hooks=dict(automaton=A)``: generate()'s ``token_automaton``; batches share a group only when their automata are equal.
+        ``hooks=dict(bias=dict(logit_bias=..., patch_bias=..., decay=...))``: generate()'s ``logit_bias`` / ``patch_bias`` /
+        ``exponential_decay_length_penalty`` (None entries: off, the decay then follows the generation config); the patch tensors are per-batch
+        data, the other two part of the options.
         """
         # a call's min_p / typical_p / epsilon_cutoff / eta_cutoff arrive as hooks["warpers"] (this method's parameter list is frozen) and are put
         # in front of the generation config's; what is left of `hooks` is the caller's processors / criteria, or nothing
@@ -457,6 +492,17 @@ class PaDTForConditionalGeneration:
         if hooks is not None and "automaton" in hooks:
             automaton = check_token_automaton(hooks["automaton"], self.config.vocab_size)
             hooks = {k: v for k, v in hooks.items() if k != "automaton"} or None
+        logit_bias = patch_bias = None
+        decay = getattr(gen_cfg, "exponential_decay_length_penalty", None)
+        if hooks is not None and "bias" in hooks:
+            hb = hooks["bias"] or {}
+            logit_bias = check_logit_bias(hb.get("logit_bias"), self.config.vocab_size)
+            patch_bias = check_patch_bias(hb.get("patch_bias"), input_ids.shape[0])      # lengths once the batch's patch counts are known (_launch)
+            decay = hb.get("decay") if hb.get("decay") is not None else decay
+            hooks = {k: v for k, v in hooks.items() if k != "bias"} or None
+        decay = check_decay_length_penalty(decay, max_new_tokens)
+        if decay is not None and decay[1] == 1.0:
+            decay = None                                          # a[t] = 1 ** k - 1 = 0 at every step: the call without the argument
         if image_index is not None and getattr(self, "precision", "default") == "reference":
             raise NotImplementedError("generate(image_index=...) is not implemented with precision='reference' (its prompt pass is its own: "
                                       "reference.ReferencePath.prefill): expand the inputs or use precision='default'")
@@ -474,12 +520,18 @@ class PaDTForConditionalGeneration:
             forced = None                                         # an all-free table: the call without the argument
         if automaton is not None:
             opts = dataclasses.replace(opts, automaton=automaton.key)
+        if logit_bias is not None or patch_bias is not None or decay is not None:
+            opts = dataclasses.replace(opts, logit_bias=logit_bias, decay=decay, patch_bias=patch_bias is not None)
+            if keep_logits and opts.sampling is None:
+                raise NotImplementedError("generate(output_logits=True) with a logits processor active (logit_bias, patch_bias or "
+                                          "exponential_decay_length_penalty): only the processed rows are kept on this path — ask for output_scores=True")
         return owner._launch(opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, max_new_tokens=max_new_tokens,
                              schedule=schedule, hooks=hooks, sync_every=sync_every, use_graph=use_graph, lane=lane, decode_stream=decode_stream,
-                             group=group, n_slots=n_slots, vit_stream=vit_stream, inputs_ready=inputs_ready, forced=forced, automaton=automaton)
+                             group=group, n_slots=n_slots, vit_stream=vit_stream, inputs_ready=inputs_ready, forced=forced, automaton=automaton,
+                             patch_bias=patch_bias)
 
     def _launch(self, opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, *, max_new_tokens, schedule, hooks, sync_every,
-                use_graph, lane, decode_stream, group, n_slots, vit_stream, inputs_ready, forced=None, automaton=None):
+                use_graph, lane, decode_stream, group, n_slots, vit_stream, inputs_ready, forced=None, automaton=None, patch_bias=None):
         """generate_launch on the group's owner, with the call's options resolved (generation.GenOptions)."""
         self._batches_seen += 1
         if pixel_values is None or image_grid_thw is None:
@@ -502,6 +554,11 @@ class PaDTForConditionalGeneration:
         need_s = max(plan.lens) + T_max
         if forced is not None:                                    # ids are the batch's own numbering: text ids and its n_proto patch rows
             forced = check_forced_tokens(forced, B, T_max, cfg.vocab_size, [n_proto] * B)
+        if patch_bias is not None:                                # lengths and map shapes against the rows' own patch grids
+            ms = cfg.vision_config.spatial_merge_size
+            gi = grid if image_index is None else grid[torch.as_tensor([int(i) for i in image_index], dtype=torch.long)]
+            patch_bias = check_patch_bias(patch_bias, B, [plan.vrt_off[i + 1] - plan.vrt_off[i] for i in range(B)],
+                                          [(int(g[1]) // ms, int(g[2]) // ms) for g in gi])
         if opts.rules is not None:
             need_s = max(need_s, plan.L_pad)                      # the session's history rows hold the padded prompt row
         if hooks is not None and (group is not None or n_slots != 1):
@@ -513,7 +570,7 @@ class PaDTForConditionalGeneration:
                          opts=opts, lane=lane, owner=self)
             # reference precision: eager split-precision steps (+ fp32 hidden rows, below)
             sess.begin(opts, p_max, processors=bool(hooks and hooks["processors"]), step_fn=self.ref.step if self.ref is not None else None,
-                       automaton=automaton)
+                       automaton=automaton, n_steps=T_max)
             if hooks is not None:
                 ids_dev = input_ids.detach().to(dev).long().contiguous()
                 hk = dict(hooks, B=B, table_rows=cfg.vocab_size + n_proto, t=0)
@@ -611,6 +668,14 @@ class PaDTForConditionalGeneration:
             # this batch's rows of the session's table, in session numbering like the prompt history; the steps past n stay free (-1: begin())
             tab = torch.where(forced >= cfg.vocab_size, forced + proto_row0, forced) if proto_row0 else forced
             sess.forced[rows, : tab.shape[1]].copy_(tab.to(dev, non_blocking=True))
+        if patch_bias is not None:
+            # this batch's segment of the session's bias vector: its own prototype rows (begin() zero-filled the vector; a row without an entry adds 0)
+            seg = torch.zeros(n_proto, dtype=torch.float32)
+            for b, pb in enumerate(patch_bias):
+                if pb is not None:
+                    seg[plan.vrt_off[b]: plan.vrt_off[b + 1]] = pb.reshape(-1)
+            c0 = cfg.vocab_size + proto_row0
+            sess.bias[c0: c0 + n_proto].copy_(seg.to(dev, non_blocking=True))
 
         # ---- prefill; the first token is selected together with the other batches of the group (launch_decode)
         if self.ref is not None:
@@ -622,6 +687,7 @@ class PaDTForConditionalGeneration:
             ops.gather_rows(hn_all, plan.last_idx, out=sess.hn_first[rows])
         group["subs"].append(dict(plan=plan, low=low, high=high, pe=pe, proto=proto, hn_all=hn_all, input_ids=input_ids,
                                   n_proto=n_proto, row0=row0, proto_row0=proto_row0, nf=nf, p_max=p_max, forced=forced, automaton=automaton,
+                                  patch_bias=patch_bias,
                                   inputs=(attention_mask, pixel_values, image_grid_thw, image_index)))       # what a re-run on the bf16 twin needs
         group["proto_rows"] = proto_row0 + n_proto
         if len(group["subs"]) == group["n_slots"]:
@@ -759,13 +825,16 @@ class PaDTForConditionalGeneration:
                           "instantiation" % (self.overflow_reruns, self._batches_seen), RuntimeWarning, stacklevel=3)
         am, pix, grid, image_index = sub["inputs"]
         # the group's options spelled as explicit arguments (an "off" is 0 / [], never the default), and what this collect was asked to return
-        kw = dict(group["opts"].generate_kwargs(), **group["opts"].warper_kwargs(), output_scores=output_scores, output_logits=output_logits)
+        kw = dict(group["opts"].generate_kwargs(), **group["opts"].warper_kwargs(), **group["opts"].bias_kwargs(), output_scores=output_scores,
+                  output_logits=output_logits)
         if group.get("hooks") is not None:
             kw.update(logits_processor=group["hooks"]["processors"], stopping_criteria=group["hooks"]["criteria"])
         if sub.get("forced") is not None:
             kw.update(forced_tokens=sub["forced"])                # the caller's table, in the batch's own numbering
         if sub.get("automaton") is not None:
             kw.update(token_automaton=sub["automaton"])           # the batch's automaton object: the options carry its key only
+        if sub.get("patch_bias") is not None:
+            kw.update(patch_bias=sub["patch_bias"])               # the batch's tensors: the options only say that there are some
         return fb.generate(input_ids=sub["input_ids"], attention_mask=am, pixel_values=pix, image_grid_thw=grid, max_new_tokens=group["T_max"],
                            schedule=group["schedule"], sync_every=group["sync_every"], use_graph=group["use_graph"], lane=("fb", group["lane"]),
                            output_hidden_states=output_hidden_states, return_dict_in_generate=return_dict_in_generate, image_index=image_index, **kw)

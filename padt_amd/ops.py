@@ -1061,6 +1061,32 @@ def vrt_head_probe(hidden, table, proto, vrt_off, part_val, part_idx, eos, part_
                seen, (_p(ban), ban.shape[1] if ban is not None else 0, _p(part_sum), _p(forced), forced.shape[1], _p(probe_val)))
 
 
+def vrt_head_bias(hidden, table, proto, vrt_off, part_val, part_idx, eos, bias=None, decay=None, step=None, mode_table=None, logits=None,
+                  table_packed=None, rows=None, gen_cfg=None, seen=None, ban=None, part_sum=None, forced=None, probe_val=None):
+    """vrt_head / vrt_head_probe with the score edits of generate(logit_bias=, patch_bias=, exponential_decay_length_penalty=)
+    (padt_vrt_head_bias): bias fp32 (table rows + proto rows,) added to the raw logit before the repetition penalty; decay fp32 (t,) — an EOS
+    column's v becomes v + |v| * decay[*step] after the mask and the bans.  The head is the one the other wrappers pick: forced (+ part_sum,
+    probe_val) → the probe head, part_sum → the LSE head, else the plain one; bias = decay = None is that head, bit for bit."""
+    B = hidden.shape[0] if rows is None else rows
+    n_cols = table.shape[0] + proto.shape[0]
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.is_cuda and bias.dim() == 1 and bias.is_contiguous() and bias.numel() >= n_cols
+    if decay is not None:
+        assert decay.dtype == torch.float32 and decay.is_cuda and decay.dim() == 1 and decay.is_contiguous() and decay.numel() > 0
+        assert step is not None and step.dtype == torch.int32
+    if ban is not None:
+        assert ban.dtype == torch.int32 and ban.is_cuda and ban.dim() == 2 and ban.is_contiguous() and ban.shape[0] >= B
+    if part_sum is not None:
+        assert part_sum.dtype == torch.float32 and part_sum.is_cuda and part_sum.is_contiguous() and part_sum.numel() >= (n_cols + 15) // 16 * B
+    if forced is not None:
+        _chk_forced(forced, B)
+        assert part_sum is not None and step is not None and step.dtype == torch.int32
+        assert probe_val is not None and probe_val.dtype == torch.float32 and probe_val.is_cuda and probe_val.is_contiguous() and probe_val.numel() >= B
+    _head_call("padt_vrt_head_bias", hidden, table, proto, vrt_off, part_val, part_idx, eos, mode_table, step, logits, table_packed, B, gen_cfg,
+               seen, (_p(ban), ban.shape[1] if ban is not None else 0, _p(part_sum), _p(forced), forced.shape[1] if forced is not None else 0,
+                      _p(probe_val) if forced is not None else 0, _p(bias), _p(decay), decay.numel() if decay is not None else 0))
+
+
 def forced_step(part_val, part_idx, nblk, hidden, hidden_buf, unfinished, tokens_out, cur_tok, step, slot, lens, pos3, eos, pad, forced, n_cols,
                 advance=True, gen_cfg=None, seen=None, part_sum=None, logprobs=None, probe_val=None):
     """greedy_step with the caller's tokens (padt_forced_step): an unfinished row b with 0 <= forced[b][*step] < n_cols takes that column as its
