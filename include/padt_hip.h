@@ -187,6 +187,11 @@ int padt_rope_table(void* stream, const int* pos3, const void* inv_freq, void* r
                     int sec1);
 
 /* ---- row kernels ---------------------------------------------------------------------------------------------------- */
+/* Every entry point below that makes vector accesses checks what they need — the row width and every row stride a multiple of 8 (16-bit
+ * rows) or 4 (fp32 rows) elements, every base pointer at the alignment of its vectors (16 bytes; 8 bytes for the 16-bit weight, bias,
+ * output or split rows that go with fp32 rows, and for fp8 codes) — and returns -1 with the rule in padt_last_error() before it launches
+ * anything; padt_rope_half, padt_llm_qkv_post and padt_llm_qkv_post_shared take their scalar path instead.  The table per entry point
+ * is in DESIGN.md, "Row kernel contract". */
 /* y = act(w * (x [+ add[row/add_div]]) * rsqrt(mean(.^2)+eps)), act: 0 none, 1 exact GELU.
  * HF:74-79; padt_decoder.py:71-74,143,156,168-172,220. */
 int padt_rmsnorm(void* stream, const void* x, long ldx, const void* add, long ld_add, int add_div, const void* w, void* y,
@@ -490,7 +495,9 @@ int  padt_token_automaton(void* stream, const int* table, long table_ints, const
 /* ---- caller-side post-processing --------------------------------------------------------------- */
 /* out[o][y][x] = sigmoid(bilinear(masks[o][:src_h[o]][:src_w[o]] → dst_h[o] x dst_w[o], align_corners=False))[y][x] > 0.5,
  * one byte per pixel; masks fp32 logits as returned by vl_decode (src_h = 4*H, src_w = 4*W of pred_mask_valid_hw).
- * up_f32 (optional) receives the up-sampled logits.  eval/evaluation_scripts/utils.py:262, eval/test_demo.py:153. */
+ * up_f32 (optional) receives the up-sampled logits.  eval/evaluation_scripts/utils.py:262, eval/test_demo.py:153.
+ * (max_dst_h, max_dst_w) are the launch extents = the size of an output plane: an object larger than them is cropped to them (what lies
+ * inside is the full-size resize, nothing outside is written) and NOT reported here — padt_mask_rle on the result reports it. */
 int padt_mask_upsample_binarize(void* stream, const void* masks_f32, long ld_obj, long ld_row, const int* src_h,
                                 const int* src_w, const int* dst_h, const int* dst_w, void* out_u8, long out_ld_obj,
                                 long out_ld_row, void* up_f32, long up_ld_obj, long up_ld_row, int n_obj, int max_dst_h,

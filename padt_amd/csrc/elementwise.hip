@@ -56,8 +56,9 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const x16_t* __restrict__ 
 extern "C" int PADT_TWIN(padt_rmsnorm)(void* stream, const void* x, long ldx, const void* add, long ld_add, int add_div,
                             const void* w, void* y, long ldy, long rows, long D, float eps, int act) {
     if (rows <= 0) return 0;
-    if ((D & 7) || (ldx & 7) || (ldy & 7) || (add && (ld_add & 7)) || add_div <= 0) {
-        padt_set_error("padt_rmsnorm: D and strides must be multiples of 8");
+    if ((D & 7) || (ldx & 7) || (ldy & 7) || (add && (ld_add & 7)) || add_div <= 0 || ((uintptr_t)x & 15) || ((uintptr_t)add & 15) ||
+        ((uintptr_t)w & 15) || ((uintptr_t)y & 15)) {
+        padt_set_error("padt_rmsnorm: D and strides must be multiples of 8, x, add, w and y 16-byte aligned");
         return -1;
     }
     hipLaunchKernelGGL(rmsnorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const x16_t*)x, ldx,
@@ -105,7 +106,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const x16_t* __restrict_
 extern "C" int PADT_TWIN(padt_layernorm)(void* stream, const void* x, long ldx, const void* w, const void* b, void* y, long ldy,
                               long rows, long D, float eps) {
     if (rows <= 0) return 0;
-    if ((D & 7) || (ldx & 7) || (ldy & 7)) { padt_set_error("padt_layernorm: D and strides must be multiples of 8"); return -1; }
+    if ((D & 7) || (ldx & 7) || (ldy & 7) || ((uintptr_t)x & 15) || ((uintptr_t)w & 15) || ((uintptr_t)b & 15) || ((uintptr_t)y & 15)) {
+        padt_set_error("padt_layernorm: D and strides must be multiples of 8, x, w, b and y 16-byte aligned");
+        return -1;
+    }
     hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const x16_t*)x, ldx,
                        (const x16_t*)w, (const x16_t*)b, (x16_t*)y, ldy, (int)rows, (int)D, eps);
     PADT_CHECK_LAUNCH();
@@ -263,7 +267,10 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const x16_t* __restric
 extern "C" int padt_gather_rows(void* stream, const void* src, long ld_src, const int* idx, void* dst, long ld_dst,
                                 long n, long D) {
     if (n <= 0) return 0;
-    if ((D & 7) || (ld_src & 7) || (ld_dst & 7)) { padt_set_error("padt_gather_rows: D and strides must be multiples of 8"); return -1; }
+    if ((D & 7) || (ld_src & 7) || (ld_dst & 7) || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15)) {
+        padt_set_error("padt_gather_rows: D and strides must be multiples of 8, src and dst 16-byte aligned");
+        return -1;
+    }
     const long total = n * (D / 8);
     long blocks = (total + 255) / 256;
     if (blocks > 16384) blocks = 16384;
@@ -344,7 +351,10 @@ __global__ __launch_bounds__(256) void add_rows_kernel(const x16_t* __restrict__
 extern "C" int PADT_TWIN(padt_add_rows)(void* stream, const void* a, long lda, const void* b, long ldb, long b_rows, void* y,
                              long ldy, long n, long D) {
     if (n <= 0) return 0;
-    if ((D & 7) || (lda & 7) || (ldb & 7) || (ldy & 7) || b_rows <= 0) { padt_set_error("padt_add_rows: bad arguments"); return -1; }
+    if ((D & 7) || (lda & 7) || (ldb & 7) || (ldy & 7) || b_rows <= 0 || ((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)y & 15)) {
+        padt_set_error("padt_add_rows: D and strides must be multiples of 8, b_rows >= 1, a, b and y 16-byte aligned");
+        return -1;
+    }
     const long total = n * (D / 8);
     long blocks = (total + 255) / 256;
     if (blocks > 16384) blocks = 16384;
@@ -524,7 +534,10 @@ extern "C" int padt_embed_tokens(void* stream, const long* ids, const int* img_i
                                  const void* proto, const void* image_embeds, void* out, long T, long vocab, long n_proto,
                                  long D, int* err_flag) {
     if (T <= 0) return 0;
-    if (D & 7) { padt_set_error("padt_embed_tokens: D must be a multiple of 8"); return -1; }
+    if ((D & 7) || ((uintptr_t)embed_table & 15) || ((uintptr_t)proto & 15) || ((uintptr_t)image_embeds & 15) || ((uintptr_t)out & 15)) {
+        padt_set_error("padt_embed_tokens: D must be a multiple of 8, both tables, image_embeds and out 16-byte aligned");
+        return -1;
+    }
     long blocks = (T * (D / 8) + 255) / 256;
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(embed_tokens_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ids, img_index,
@@ -552,6 +565,7 @@ struct QkvPostArgs {
     x16_t* kc; x16_t* vtc;   // caches
     int T, Hq, Hkv, D, S_max, sec0, sec1;
     int cache_packed;          // 1: fragment-packed cache images (csrc/attention.hip decode_attn_rope_packed_kernel), 0: row-major K / V^T
+    int vec;                   // 1: the 16-byte path (set by the entry point: D % 16, strides % 8 and 16-byte aligned pointers), 0: the scalar one
 };
 
 // element offsets inside one (sample, kv head) cache image; D % 32 == 0, S_max % 32 == 0 for the packed forms
@@ -578,7 +592,7 @@ __global__ __launch_bounds__(256) void llm_qkv_post_kernel(QkvPostArgs p) {
         cs[1][d] = sinf(ang);
     }
     __syncthreads();
-    if ((half & 7) == 0 && (p.ld & 7) == 0 && (p.ld_q & 7) == 0 && (p.ld_kp & 7) == 0) {
+    if (p.vec) {
         // 16-byte path: item = (head, 8-wide chunk of the first half); its partner chunk sits D/2 further
         const int cph = half >> 3;
         const int items = (p.Hq + p.Hkv) * cph;
@@ -650,7 +664,10 @@ extern "C" int PADT_TWIN(padt_llm_qkv_post)(void* stream, const void* qkv, long 
     if (cache_packed && ((head_dim & 31) || (s_max & 31))) { padt_set_error("padt_llm_qkv_post: packed caches need head_dim % 32 == 0 and s_max % 32 == 0"); return -1; }
     QkvPostArgs a{(const x16_t*)qkv, ld_qkv, pos3, sample, slot, lens, (const float*)inv_freq, (x16_t*)q_out, ld_q,
                   (x16_t*)k_pack, ld_kp, (x16_t*)k_cache, (x16_t*)vt_cache, (int)T, n_heads, n_kv_heads, head_dim,
-                  s_max, sec0, sec1, cache_packed ? 1 : 0};
+                  s_max, sec0, sec1, cache_packed ? 1 : 0, 0};
+    // the 16-byte path needs whole 8-element chunks per half head and 16-byte aligned rows of every 16-bit operand; anything else takes the scalar path
+    a.vec = (head_dim & 15) == 0 && (ld_qkv & 7) == 0 && (ld_q & 7) == 0 && (ld_kp & 7) == 0 && ((uintptr_t)qkv & 15) == 0 &&
+            ((uintptr_t)q_out & 15) == 0 && ((uintptr_t)k_pack & 15) == 0 && ((uintptr_t)k_cache & 15) == 0;
     hipLaunchKernelGGL(llm_qkv_post_kernel, dim3((unsigned)T), dim3(256), 0, (hipStream_t)stream, a);
     PADT_CHECK_LAUNCH();
     return 0;
@@ -675,6 +692,7 @@ struct QkvPostSharedArgs {
     const int* dst_off;        // [T+1] CSR offsets into the three lists below
     const int* dst_sample; const int* dst_slot; const int* dst_row;
     int T, Hq, Hkv, D, S_max, B, n_join, sec0, sec1, cache_packed;
+    int vec;                   // as QkvPostArgs::vec
 };
 
 __global__ __launch_bounds__(256) void llm_qkv_post_shared_kernel(QkvPostSharedArgs p) {
@@ -692,7 +710,7 @@ __global__ __launch_bounds__(256) void llm_qkv_post_shared_kernel(QkvPostSharedA
     __syncthreads();
     auto cache_ok = [&](int n) { return (unsigned)p.dst_sample[n] < (unsigned)p.B && (unsigned)p.dst_slot[n] < (unsigned)p.S_max; };
     auto join_ok = [&](int n) { return (unsigned)p.dst_row[n] < (unsigned)p.n_join; };
-    const bool vec = (half & 7) == 0 && (p.ld & 7) == 0 && (p.ld_q & 7) == 0 && (p.ld_kj & 7) == 0 && (p.ld_vj & 7) == 0;
+    const bool vec = p.vec != 0;
     if (vec) {
         // 16-byte path: item = (head, 8-wide chunk of the first half); its partner chunk sits D/2 further
         const int cph = half >> 3;
@@ -805,7 +823,9 @@ extern "C" int PADT_TWIN(padt_llm_qkv_post_shared)(void* stream, const void* qkv
     if (T == 0) return 0;
     QkvPostSharedArgs a{(const x16_t*)qkv, ld_qkv, pos3, (const float*)inv_freq, (x16_t*)q_out, ld_q, (x16_t*)k_join, ld_kj,
                         (x16_t*)v_join, ld_vj, (x16_t*)k_cache, (x16_t*)vt_cache, dst_off, dst_sample, dst_slot, dst_row,
-                        (int)T, n_heads, n_kv_heads, head_dim, s_max, batch, (int)n_join, sec0, sec1, cache_packed ? 1 : 0};
+                        (int)T, n_heads, n_kv_heads, head_dim, s_max, batch, (int)n_join, sec0, sec1, cache_packed ? 1 : 0, 0};
+    a.vec = (head_dim & 15) == 0 && (ld_qkv & 7) == 0 && (ld_q & 7) == 0 && (ld_kj & 7) == 0 && (ld_vj & 7) == 0 && ((uintptr_t)qkv & 15) == 0 &&
+            ((uintptr_t)q_out & 15) == 0 && ((uintptr_t)k_join & 15) == 0 && ((uintptr_t)v_join & 15) == 0 && ((uintptr_t)k_cache & 15) == 0;
     hipLaunchKernelGGL(llm_qkv_post_shared_kernel, dim3((unsigned)T), dim3(256), 0, (hipStream_t)stream, a);
     PADT_CHECK_LAUNCH();
     return 0;
@@ -857,12 +877,16 @@ extern "C" int padt_mask_scatter(void* stream, const void* e2, long ld_e2, const
 // fused into one pass: fp32 bilinear resize (align_corners=False; source index = max(scale*(dst+0.5)-0.5, 0), scale =
 // in/out as float, the same expression order as torch's upsample_bilinear2d) of each object's valid logit region to its
 // image size, fp32 sigmoid, threshold, one byte per pixel.  Optionally also stores the up-sampled logits (tests).
+// The launch extents (max_dst_h, max_dst_w) are the size of an output plane: an object with dst_h > max_dst_h or dst_w > max_dst_w is CROPPED to
+// them — its pixels inside the extents are those of the full-size resize, nothing is written outside — and not reported here; padt_mask_rle,
+// which runs on the result, is what reports such an object (n_counts < 0).
 struct MaskPostArgs {
     const float* masks; long ld_obj, ld_row;
     const int* src_h; const int* src_w;
     const int* dst_h; const int* dst_w;
     unsigned char* out; long out_ld_obj, out_ld_row;
     float* up; long up_ld_obj, up_ld_row;
+    int max_w;                                   // launch extent in x: the width of an output row
 };
 
 __global__ __launch_bounds__(256) void mask_upsample_binarize_kernel(MaskPostArgs p) {
@@ -870,6 +894,7 @@ __global__ __launch_bounds__(256) void mask_upsample_binarize_kernel(MaskPostArg
     const int H = p.dst_h[o], W = p.dst_w[o], hs = p.src_h[o], ws = p.src_w[o];
     const int y = blockIdx.y;
     if (y >= H) return;
+    const int x_end = W < p.max_w ? W : p.max_w;                  // an object beyond the launch extents is cropped (rows: by the grid)
     const float sy = (float)hs / (float)H, sx = (float)ws / (float)W;
     float fy = sy * ((float)y + 0.5f) - 0.5f;
     fy = fy < 0.f ? 0.f : fy;
@@ -878,7 +903,7 @@ __global__ __launch_bounds__(256) void mask_upsample_binarize_kernel(MaskPostArg
     const float ly1 = fy - (float)y0, ly0 = 1.f - ly1;
     const float* r0 = p.masks + (long)o * p.ld_obj + (long)y0 * p.ld_row;
     const float* r1 = p.masks + (long)o * p.ld_obj + (long)y1 * p.ld_row;
-    for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < W; x += gridDim.x * blockDim.x) {
+    for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < x_end; x += gridDim.x * blockDim.x) {
         float fx = sx * ((float)x + 0.5f) - 0.5f;
         fx = fx < 0.f ? 0.f : fx;
         const int x0 = (int)fx;
@@ -898,7 +923,7 @@ extern "C" int padt_mask_upsample_binarize(void* stream, const void* masks_f32, 
     if (n_obj <= 0 || max_dst_h <= 0 || max_dst_w <= 0) return 0;
     if (n_obj > 65535 || max_dst_h > 65535) { padt_set_error("padt_mask_upsample_binarize: n_obj and max_dst_h must be <= 65535"); return -1; }
     MaskPostArgs a{(const float*)masks_f32, ld_obj, ld_row, src_h, src_w, dst_h, dst_w, (unsigned char*)out_u8, out_ld_obj,
-                   out_ld_row, (float*)up_f32, up_ld_obj, up_ld_row};
+                   out_ld_row, (float*)up_f32, up_ld_obj, up_ld_row, max_dst_w};
     const int bx = (max_dst_w + 255) / 256;
     hipLaunchKernelGGL(mask_upsample_binarize_kernel, dim3(bx, max_dst_h, n_obj), dim3(256), 0, (hipStream_t)stream, a);
     PADT_CHECK_LAUNCH();

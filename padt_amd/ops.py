@@ -711,8 +711,7 @@ def llm_qkv_post_shared(qkv, pos3, inv_freq, q_out, k_cache, vt_cache, k_join, v
     for t in (dst_off, dst_sample, dst_slot, dst_row):
         assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
     assert dst_off.numel() == T + 1 and dst_sample.numel() == dst_slot.numel() == dst_row.numel()
-    for t in (qkv, q_out, k_join, v_join, k_cache, vt_cache):       # the kernel's 16-byte accesses
-        assert t.data_ptr() % 16 == 0
+    # no alignment assertion: on a base that is not 16-byte aligned the entry point takes the kernel's scalar branch (same bits)
     _lib.check(_fn("padt_llm_qkv_post_shared", dt)(_stream(), _p(qkv), qkv.stride(0), _p(pos3), _p(inv_freq), _p(q_out), q_out.stride(0),
                                             _p(k_join), k_join.stride(0), _p(v_join), v_join.stride(0), k_join.shape[0], _p(k_cache),
                                             _p(vt_cache), _p(dst_off), _p(dst_sample), _p(dst_slot), _p(dst_row), T, n_heads, n_kv_heads,
@@ -1148,14 +1147,21 @@ def stash_step_f32(src, step, dst):
     return dst
 
 
-def mask_upsample_binarize(masks, src_h, src_w, dst_h, dst_w, max_h, max_w, want_logits=False):
+def mask_upsample_binarize(masks, src_h, src_w, dst_h, dst_w, max_h, max_w, want_logits=False, out=None, up=None):
     """masks (n_obj, Hm, Wm) fp32 logits; src/dst sizes int32 device tensors (n_obj,) → uint8 (n_obj, max_h, max_w)
-    [, fp32 up-sampled logits]."""
+    [, fp32 up-sampled logits].  (max_h, max_w) are the launch extents: an object larger than them is cropped to them, and mask_rle on the
+    result reports it.  out / up: caller-owned (n_obj, max_h, max_w) planes (any object and row stride) to write instead of fresh zeros;
+    up implies want_logits."""
     lib = _lib.load()
     assert masks.dtype == torch.float32 and masks.stride(-1) == 1
     n = masks.shape[0]
-    out = torch.zeros((n, max_h, max_w), dtype=torch.uint8, device=masks.device)
-    up = torch.zeros((n, max_h, max_w), dtype=torch.float32, device=masks.device) if want_logits else None
+    want_logits = want_logits or up is not None
+    if out is None:
+        out = torch.zeros((n, max_h, max_w), dtype=torch.uint8, device=masks.device)
+    if up is None and want_logits:
+        up = torch.zeros((n, max_h, max_w), dtype=torch.float32, device=masks.device)
+    assert out.dtype == torch.uint8 and out.shape == (n, max_h, max_w) and out.stride(2) == 1
+    assert up is None or (up.dtype == torch.float32 and up.shape == (n, max_h, max_w) and up.stride(2) == 1)
     for t in (src_h, src_w, dst_h, dst_w):
         assert t.dtype == torch.int32 and t.numel() == n
     _lib.check(lib.padt_mask_upsample_binarize(_stream(), _p(masks), masks.stride(0), masks.stride(1), _p(src_h), _p(src_w),
@@ -1300,19 +1306,24 @@ def gemm_hp(a_split, w2, bias=None, out=None, epilogue=EPI_NONE, residual=None, 
 
 
 def norm_split(x, w=None, eps=1e-6, act=0, idx=None, add=None, add_div=1, pos=None, y0_mode=OUT_SPLIT, y1_mode=OUT_NONE, chunk=None,
-               rows=None, D=None):
-    """→ (y0, y1) of padt_norm_split; x bf16 or fp32 (rows, >= D); modes OUT_NONE / OUT_F32 / OUT_SPLIT (split rows are 2*D wide)."""
+               rows=None, D=None, y0=None, y1=None):
+    """→ (y0, y1) of padt_norm_split; x bf16 or fp32 (rows, >= D); modes OUT_NONE / OUT_F32 / OUT_SPLIT (split rows are 2*D wide).
+    y0 / y1: caller-owned outputs of the mode's type and width (any row stride the entry point accepts) instead of fresh ones."""
     lib = _lib.load()
     assert x.dtype in (BF16, F32) and x.stride(-1) == 1
     D = x.shape[1] if D is None else D
     rows = (idx.numel() if idx is not None else x.shape[0]) if rows is None else rows
     chunk = D if chunk is None else chunk
 
-    def mk(mode):
+    def mk(mode, y):
         if mode == OUT_NONE:
             return None
-        return torch.empty((rows, D if mode == OUT_F32 else 2 * D), device=x.device, dtype=F32 if mode == OUT_F32 else BF16)
-    y0, y1 = mk(y0_mode), mk(y1_mode)
+        shape, dt = (rows, D if mode == OUT_F32 else 2 * D), F32 if mode == OUT_F32 else BF16
+        if y is None:
+            return torch.empty(shape, device=x.device, dtype=dt)
+        assert y.dtype == dt and y.shape == shape and y.stride(-1) == 1, (y.dtype, y.shape, y.stride())
+        return y
+    y0, y1 = mk(y0_mode, y0), mk(y1_mode, y1)
     if add is not None:
         assert add.dtype == F32 and add.stride(-1) == 1
     if pos is not None:

@@ -1,10 +1,12 @@
 """tests/edge_util.py on the CPU: the windows hold their tensors, the poison is where it should be, and outside_unchanged sees one planted
 element below, to the right of, and (split output) in the gap between the windows — the checks of tests/test_gemm_edges_gpu.py are only as
-good as these."""
+good as these.  Arena / Failures / three (shared by the GEMM, row and mask edge suites) run here on CPU tensors: a body that
+over-reads by one element, writes one element outside its window, or depends on the poison is caught by the assertion meant for it."""
 import pytest
 import torch
 
-from edge_util import MIN_COLS, MIN_ROWS, SENTINEL, nan_fill, outside_is_nan, outside_unchanged, same_bits, window
+from edge_util import (BYTE_SENTINEL, MIN_COLS, MIN_ROWS, SENTINEL, Arena, Failures, nan_fill, outside_is_nan, outside_unchanged, same_bits,
+                       sentinel_of, three, window)
 
 DTYPES = [torch.bfloat16, torch.float16, torch.float32, torch.uint8]
 
@@ -115,3 +117,106 @@ def test_same_bits():
     assert same_bits(a.to(torch.bfloat16), a.to(torch.bfloat16)) and not same_bits(a.half(), torch.tensor([1.0, 2.0, 0.0]).half())
     a2 = torch.randn(6, 10)[:, 2:7]                                  # strided views compare by value
     assert same_bits(a2, a2.clone())
+
+
+# ------------------------------------------------------------------------------------------------------------ Arena / Failures / three
+def test_sentinels_per_type():
+    assert sentinel_of(torch.uint8) == BYTE_SENTINEL == 0xA5 and nan_fill(torch.uint8) == 0x7F
+    assert sentinel_of(torch.int32) == -1234 and isinstance(sentinel_of(torch.int32), int)
+    for dt in (torch.float32, torch.bfloat16, torch.float16):
+        assert sentinel_of(dt) == SENTINEL and torch.isfinite(torch.tensor(SENTINEL, dtype=dt))          # bf16 rounds it to -1232: bits are compared
+
+
+@pytest.mark.parametrize("dtype", [torch.uint8, torch.int32, torch.float32, torch.bfloat16], ids=str)
+def test_arena_output_windows_carry_their_types_sentinel(dtype):
+    ar = Arena(True)
+    t = torch.ones(5, 24).to(dtype)
+    v = ar.out(t)
+    backing, spec, fill = ar.outs[0]
+    assert fill == sentinel_of(dtype) and backing.dtype == dtype and torch.equal(v, t)
+    assert int((backing == fill).sum()) == backing.numel() - t.numel()
+    ar.check()
+    v.fill_(7)                                                       # inside: free
+    ar.check()
+    backing[MIN_ROWS + 5, MIN_COLS] = 7                              # the row below
+    with pytest.raises(AssertionError, match="outside the window changed"):
+        ar.check()
+    backing[MIN_ROWS + 5, MIN_COLS] = fill
+    backing[MIN_ROWS + 4, MIN_COLS + 24] = 7                         # one element to the right
+    with pytest.raises(AssertionError, match="outside the window changed"):
+        ar.check()
+    ar1 = Arena(False)
+    v1 = ar1.out(torch.zeros(9).to(dtype))
+    ar1.check()
+    ar1.outs[0][0][MIN_COLS + 9] = 1
+    with pytest.raises(AssertionError):
+        ar1.check()
+    assert v1.numel() == 9
+
+
+def test_arena_windows_strides_offsets_and_poison():
+    ar = Arena(True)
+    a, b, c = ar.inp(torch.ones(5, 24)), ar.inp(torch.ones(7, 24)), ar.out(torch.ones(5, 24))
+    assert len({a.stride(0), b.stride(0), c.stride(0)}) == 3 and all(s % 16 == 0 for s in (a.stride(0), b.stride(0), c.stride(0)))
+    assert a.storage_offset() == MIN_ROWS * a.stride(0) + MIN_COLS
+    base = a.as_strided((MIN_ROWS + 5 + MIN_ROWS + 8, a.stride(0)), (a.stride(0), 1), 0)               # the whole backing
+    assert int(torch.isnan(base).sum()) == base.numel() - 5 * 24
+    z = Arena(False).inp(torch.ones(5, 24))
+    assert float(z.as_strided((1,), (1,), 0)) == 0.0                 # zeros around the inputs of the second run
+    u = ar.inp(torch.ones(4, 16, dtype=torch.uint8))
+    assert int(u.as_strided((1,), (1,), 0)) == 0x7F
+    # a window 4 elements in (8 bytes for a 16-bit type) and a row stride that is no multiple of 8
+    w = ar.inp(torch.ones(3, 80, dtype=torch.bfloat16), c0=MIN_COLS + 4)
+    assert w.storage_offset() % 8 == 4 and (w.data_ptr() - w.storage_offset() * 2) % 16 == 0 and w.data_ptr() % 16 == 8
+    o = ar.out(torch.ones(3, 80, dtype=torch.bfloat16), ld=MIN_COLS + 80 + MIN_COLS + 4)
+    assert o.stride(0) % 8 == 4
+    ar.check()
+    with pytest.raises(AssertionError):                              # a stride that leaves less than the margin behind the window
+        ar.inp(torch.ones(3, 80), ld=MIN_COLS + 80 + MIN_COLS - 1)
+    s = ar.out(torch.ones(32, 40), slab=True)                        # a slab: natural stride, whole sentinel rows around it
+    assert s.stride(0) == 40 and ar.outs[-1][1] == (MIN_ROWS, 0, 32, 40)
+    sp = ar.out(torch.full((4, 20), SENTINEL), spec=[(0, 0, 4, 8), (0, 12, 4, 8)])
+    sp[:, :8] = 1.0
+    ar.check()
+    sp[2, 9] = 1.0                                                   # the gap of a split window is outside
+    with pytest.raises(AssertionError):
+        ar.check()
+
+
+def test_three_catches_an_over_read_a_stray_store_and_a_wrong_result():
+    x = torch.arange(12.0).view(3, 4)
+
+    def run(body, check=lambda got: None):
+        f = Failures()
+        three(f, "case", body, check)
+        return f.msgs
+
+    def good(ar):
+        X, Y = ar.inp(x), ar.out(torch.zeros(3, 4))
+        Y.copy_(X * 2)
+        return {"y": Y}
+    assert run(good, lambda got: torch.testing.assert_close(got["y"], x * 2)) == []
+
+    def over_read(ar):                                               # one element past the row end enters the sum
+        X, Y = ar.inp(x), ar.out(torch.zeros(3, 1))
+        wide = X.as_strided((3, 5), (X.stride(0), 1), X.storage_offset())
+        Y.copy_(wide.sum(1, keepdim=True))
+        return {"y": Y}
+    msgs = run(over_read)
+    assert len(msgs) == 1 and "case: 2" in msgs[0]                   # NaN run != zero run
+
+    def stray_store(ar):
+        X, Y = ar.inp(x), ar.out(torch.zeros(3, 4))
+        Y.copy_(X)
+        Y.as_strided((1,), (1,), Y.storage_offset() + 4).fill_(1.0)  # one element right of row 0
+        return {"y": Y}
+    msgs = run(stray_store)
+    assert len(msgs) == 2 and all("case: 3" in m for m in msgs)      # both runs
+
+    msgs = run(good, lambda got: torch.testing.assert_close(got["y"], x * 3))
+    assert len(msgs) == 1 and "case: 1" in msgs[0]
+    f = Failures()
+    with f.step("a"):
+        assert False, "boom"
+    with pytest.raises(AssertionError, match=r"1 failed:\n\[a\] boom"):
+        f.done()

@@ -27,12 +27,10 @@ locality asserted above: a read of A rows past M (W rows past N) that stays insi
 never stored.  The K-direction guards and every store-side bound are visible: without stage_tile's `k < K` select every 128^2-tile output is NaN
 (assertions 1 and 2), without store_frag's `m >= M` bound or with the peeled tail's mirror advanced by the stream's stride assertion 3 fails.
 """
-import contextlib
-
 import pytest
 import torch
 
-from edge_util import MIN_COLS, MIN_ROWS, SENTINEL, nan_fill, outside_unchanged, same_bits, window
+from edge_util import MIN_COLS, MIN_ROWS, SENTINEL, Arena, Failures, same_bits, three
 from test_decoder_hp_gpu import rel_err, split_close
 from test_kernels_f16_gpu import close_f16
 from test_kernels_gpu import close_bf16, close_f32, interleave_gate_up
@@ -84,80 +82,6 @@ def swiglu_ref(lin):
     """fp32 rows over [gate16 | up16]-interleaved weight rows → silu(gate) * up"""
     y = lin.view(lin.shape[0], lin.shape[1] // 32, 2, 16)
     return (silu(y[:, :, 0]) * y[:, :, 1]).reshape(lin.shape[0], lin.shape[1] // 2)
-
-
-class Arena:
-    """The windows of one launch.  poison: NaN (else zeros) around the inputs; the sentinel around the outputs either way.  Every 2-D window
-    gets a row stride of its own (a multiple of 16 elements, which satisfies every entry point's stride rule)."""
-
-    def __init__(self, poison):
-        self.poison, self.outs, self.lds = poison, [], set()
-
-    def _ld(self, cols, ld):
-        if ld is None:
-            ld = (C0 + cols + MIN_COLS + 15) // 16 * 16
-            while ld in self.lds:
-                ld += 16
-        self.lds.add(ld)
-        return ld
-
-    def _win(self, t, ld, slab, fill):
-        if t.dim() == 1:
-            return window(t, 0, C0, 0, MIN_COLS + 8, fill) + ((C0, t.numel()),)
-        if slab:                                                     # rows at their natural stride (fragment-packed images and buffers)
-            return window(t, R0, 0, R0, 0, fill) + ((R0, 0) + tuple(t.shape),)
-        ld = self._ld(t.shape[1], ld)
-        return window(t, R0, C0, R0 + 8, ld - C0 - t.shape[1], fill) + ((R0, C0) + tuple(t.shape),)
-
-    def inp(self, t, ld=None, slab=False):
-        return self._win(t, ld, slab, nan_fill(t.dtype) if self.poison else 0)[1]
-
-    def out(self, t, ld=None, slab=False, spec=None):
-        """t: the window's initial contents; spec: the windows inside it that may be written (default: all of it), relative to its corner."""
-        backing, view, whole = self._win(t, ld, slab, SENTINEL)
-        if spec is not None:
-            whole = [(whole[0] + r, whole[1] + c, rows, cols) for r, c, rows, cols in spec]
-        self.outs.append((backing, whole))
-        return view
-
-    def check(self):
-        for backing, spec in self.outs:
-            outside_unchanged(backing, spec, SENTINEL)
-
-
-class Failures:
-    """Collects the failed assertions of a test that loops over epilogues / variants, so that one run shows all of them."""
-
-    def __init__(self):
-        self.msgs = []
-
-    @contextlib.contextmanager
-    def step(self, what):
-        try:
-            yield
-        except AssertionError as e:
-            self.msgs.append(f"[{what}] {str(e)[:600]}")
-
-    def done(self):
-        assert not self.msgs, f"{len(self.msgs)} failed:\n" + "\n".join(self.msgs)
-
-
-def three(fails, what, body, check):
-    """The three assertions of an operand-window case.  body(arena) → {name: result view}; check(results) compares with the reference."""
-    got = {}
-    for poison in (True, False):
-        ar = Arena(poison)
-        outs = body(ar)
-        torch.cuda.synchronize()
-        got[poison] = {k: v.clone() for k, v in outs.items()}
-        with fails.step(f"{what}: 3 (outside the output windows, {'NaN' if poison else 'zero'} run)"):
-            ar.check()
-    with fails.step(f"{what}: 1 (reference)"):
-        check(got[True])
-    for k, v in got[True].items():
-        with fails.step(f"{what}: 2 (bit-identical to the run with zeros around the operands)"):
-            assert same_bits(v, got[False][k]), f"{k}: {int((v != got[False][k]).sum())} of {v.numel()} elements differ, " \
-                                                f"{int((~torch.isfinite(v.float())).sum())} non-finite"
 
 
 # ------------------------------------------------------------------------------------------------------------ ops.gemm epilogues
