@@ -346,7 +346,8 @@ int  padt_vrt_head_lse(void* stream, const void* hidden, long ldh, const void* e
                        const void* ban, long ban_words, void* part_sum);
 /* argmax reduction (ties → lowest id), pad/EOS bookkeeping, token append, hidden-row stash, slot/len/position/step
  * advance — all on device.  padt.py:745-757, 732-737.  gen_cfg / seen as in padt_vrt_head: extra EOS ids stop a row too
- * (generation_config's eos_token_id list), and the chosen token's bit is set in the row's seen bitmap. */
+ * (generation_config's eos_token_id list), and the chosen token's bit is set in the row's seen bitmap.  A row without a candidate — the
+ * sentinel index 0x7fffffff, or a best value of -inf (padt_argmax_rows_f32 reports column 0 for such a row) — continues with pad. */
 int  padt_greedy_step(void* stream, const void* part_val, const void* part_idx, long nblk, long batch, long D, int eos,
                       int pad, long t_max, int* unfinished, long* tokens_out, long* cur_tok, int* step, int* slot,
                       int* lens, int* pos3, const void* hidden, void* hidden_buf, int advance, const void* gen_cfg,
@@ -409,6 +410,11 @@ int  padt_forced_override(void* stream, void* part_idx, const int* forced, long 
  * -inf elsewhere: HF's `scores` under sampling, padt.py:717-720). */
 int  padt_sample_token(void* stream, void* logits_f32, long ld_logits, long n_rows_table, const void* gen_cfg, const int* step,
                        void* part_val, void* part_idx, long batch);
+/* padt_sample_token with the generator keyed as padt_warp_sample_rows_f32 keys its own (below): row_base (nullable; then vrt_off [batch + 1]
+ * and vocab are required) names the first row of b's own batch inside a merged decode group, and the draw uses (b - row_base[b], column in
+ * the batch's own numbering), so a batch draws inside a group what it draws alone.  Null: padt_sample_token's (b, column). */
+int  padt_sample_token_keyed(void* stream, void* logits_f32, long ld_logits, long n_rows_table, const void* gen_cfg, const int* step,
+                             void* part_val, void* part_idx, long batch, long vocab, const int* vrt_off, const int* row_base);
 /* The rest of HF's warper chain and the draw (generate(min_p=, typical_p=, epsilon_cutoff=, eta_cutoff=)): MinP → Typical → Epsilon → Eta
  * (generation/logits_process.py, min_tokens_to_keep = 1; each takes the softmax over the survivors of the stage before it) over fp32 rows that
  * hold the scores after temperature / top-k / top-p — what padt_sample_token leaves with write_back, whose own draw is then ignored.

@@ -74,7 +74,9 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyArgs p) {
         long next = unf ? (long)si[0] : (long)p.pad;                 // padt.py:749
         // a row whose logits are all NaN (an fp16 operand overflowed upstream: the range guard flags the batch, padt_check_finite) has no
         // arg-max — bidx is still the sentinel; continue with the pad token so that every later index stays inside its table
-        const bool no_choice = si[0] == 0x7fffffff || next < 0 || (p.seen && (next >> 5) >= p.seen_words);
+        // ... and so has a row whose best value is -inf (padt_argmax_rows_f32 reports column 0 for it, torch.argmax's answer: every column
+        // was banned by a caller's processor on the hooked loop) — the head's and the samplers' partials carry the sentinel there already
+        const bool no_choice = si[0] == 0x7fffffff || sv[0] == -INFINITY || next < 0 || (p.seen && (next >> 5) >= p.seen_words);
         if (no_choice) next = (long)p.pad;
         bool is_forced = false;
         if constexpr (FORCED) {

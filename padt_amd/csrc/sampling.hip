@@ -37,7 +37,8 @@ PADT_DEV float gumbel_noise(unsigned seed, unsigned step, unsigned row, unsigned
 
 __global__ __launch_bounds__(1024) void sample_token_kernel(float* logits, long ld, int n, const GenCfg* __restrict__ g,
                                                             const int* __restrict__ step, float* __restrict__ out_val,
-                                                            int* __restrict__ out_idx) {
+                                                            int* __restrict__ out_idx, int vocab, const int* __restrict__ vrt_off,
+                                                            const int* __restrict__ row_base) {
     __shared__ unsigned hist[256];                                        // radix histogram; then the per-wave tie counts of the cut search
     __shared__ unsigned sel[2];                                           // chosen bin, remaining rank
     __shared__ float sval[1024];
@@ -51,6 +52,13 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(float* logits, long 
     const int k = g->top_k;
     const float top_p = g->top_p;
     const unsigned seed = g->seed, st = step ? (unsigned)*step : 0u;
+    // the generator's (row, index) counter in the numbering of the row's own batch (padt_sample_token_keyed): a batch of a merged decode
+    // group draws what it draws alone; without row_base: (b, column)
+    int rb = row_base ? row_base[b] : 0;
+    rb = (rb < 0 || rb > b) ? 0 : rb;                                     // an index read from device memory: vrt_off[rb] stays inside [0, batch]
+    const unsigned key_row = (unsigned)(b - rb);
+    const int col0 = row_base ? vrt_off[rb] : 0;
+    auto key_col = [&](int i) { return (unsigned)(i >= vocab && row_base ? i - col0 : i); };
     // ---- top-k threshold (key of the k-th largest entry), or keep everything finite
     unsigned thresh = float_key(-INFINITY) + 1u;                          // any finite value
     if (k > 0 && k < n) {
@@ -175,14 +183,14 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(float* logits, long 
             __syncthreads();
         }
         if (keep) {
-            best = (sval[tid] - mx) / T + gumbel_noise(seed, st, (unsigned)b, (unsigned)sidx[tid]);
+            best = (sval[tid] - mx) / T + gumbel_noise(seed, st, key_row, key_col(sidx[tid]));
             bidx = sidx[tid];
         }
         if (jk > 0) {
             const int last = tie_last;
             for (int i = tid; i < n && i <= last; i += 1024) {
                 if (float_key(row[i]) == thresh) {
-                    const float sc = (tv - mx) / T + gumbel_noise(seed, st, (unsigned)b, (unsigned)i);
+                    const float sc = (tv - mx) / T + gumbel_noise(seed, st, key_row, key_col(i));
                     if (argmax_less(best, bidx, sc, i)) { best = sc; bidx = i; }
                 }
             }
@@ -191,7 +199,7 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(float* logits, long 
         for (int i = tid; i < n; i += 1024) {
             const float v = row[i];
             if (float_key(v) >= thresh) {
-                const float sc = (v - mx) / T + gumbel_noise(seed, st, (unsigned)b, (unsigned)i);
+                const float sc = (v - mx) / T + gumbel_noise(seed, st, key_row, key_col(i));
                 if (argmax_less(best, bidx, sc, i)) { best = sc; bidx = i; }
             }
         }
@@ -228,7 +236,26 @@ extern "C" int padt_sample_token(void* stream, void* logits_f32, long ld_logits,
     if (batch <= 0) return 0;
     if (gen_cfg == nullptr || n_rows_table <= 0 || n_rows_table > 0x7fffffffL) { padt_set_error("padt_sample_token: gen_cfg and a table size are required"); return -1; }
     hipLaunchKernelGGL(sample_token_kernel, dim3((unsigned)batch), dim3(1024), 0, (hipStream_t)stream, (float*)logits_f32, ld_logits,
-                       (int)n_rows_table, (const GenCfg*)gen_cfg, step, (float*)part_val, (int*)part_idx);
+                       (int)n_rows_table, (const GenCfg*)gen_cfg, step, (float*)part_val, (int*)part_idx, 0, (const int*)nullptr,
+                       (const int*)nullptr);
+    PADT_CHECK_LAUNCH();
+    return 0;
+}
+
+// padt_sample_token with the generator keyed like padt_warp_sample_rows_f32's: row_base[b] = the first row of b's own batch inside a merged
+// decode group, vrt_off [batch + 1], vocab — the draw of row b, column c uses (b - row_base[b], c >= vocab ? c - vrt_off[row_base[b]] : c), the
+// numbers the batch has alone.  row_base null: padt_sample_token.
+extern "C" int padt_sample_token_keyed(void* stream, void* logits_f32, long ld_logits, long n_rows_table, const void* gen_cfg,
+                                       const int* step, void* part_val, void* part_idx, long batch, long vocab, const int* vrt_off,
+                                       const int* row_base) {
+    if (batch <= 0) return 0;
+    if (gen_cfg == nullptr || n_rows_table <= 0 || n_rows_table > 0x7fffffffL) { padt_set_error("padt_sample_token_keyed: gen_cfg and a table size are required"); return -1; }
+    if (row_base != nullptr && (vrt_off == nullptr || vocab < 0 || vocab > n_rows_table)) {
+        padt_set_error("padt_sample_token_keyed: row_base needs vrt_off and 0 <= vocab <= n_rows_table");
+        return -1;
+    }
+    hipLaunchKernelGGL(sample_token_kernel, dim3((unsigned)batch), dim3(1024), 0, (hipStream_t)stream, (float*)logits_f32, ld_logits,
+                       (int)n_rows_table, (const GenCfg*)gen_cfg, step, (float*)part_val, (int*)part_idx, (int)vocab, vrt_off, row_base);
     PADT_CHECK_LAUNCH();
     return 0;
 }

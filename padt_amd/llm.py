@@ -303,7 +303,7 @@ class DecodeSession:
         self.vtc = [z(B, Hkv, hd, s_max) for _ in range(nl)]
         self.proto = z(np_max, D)
         self.vrt_off = z(B + 1, dt=I32)
-        self.batch_row0 = z(B, dt=I32)     # per row: the first row of its batch in a merged decode group (the warper kernel's generator key)
+        self.batch_row0 = z(B, dt=I32)     # per row: the first row of its batch in a merged decode group (the sampling kernels' generator key)
         self.mode_table = z(t_max + 1, dt=I32)
         self.step = z(1, dt=I32)
         self.unfinished = z(B, dt=I32)
@@ -538,7 +538,9 @@ class DecodeSession:
         if m.sampling:                                       # padt.py:740-743: multinomial over softmax of the warped scores
             # with keep_scores (or token_logprobs) the session's gen_cfg has write_back set: lg then holds the warped rows (l / T, -inf outside top-k / top-p),
             # HF's next_token_scores — the warpers are part of its logits_processor (padt.py:717)
-            ops.sample_token(lg, cfg.vocab_size + self.np_max, self.gen_cfg, self.step, self.part_val, self.part_idx, self.B)
+            # keyed by each row's place in its own batch (batch_row0), so a batch of a merged decode group draws what it draws alone
+            ops.sample_token(lg, cfg.vocab_size + self.np_max, self.gen_cfg, self.step, self.part_val, self.part_idx, self.B,
+                             vocab=cfg.vocab_size, vrt_off=self.vrt_off, row_base=self.batch_row0)
             if m.warpers:
                 # min_p / typical_p / epsilon_cutoff / eta_cutoff (HF's warpers after top-p): write_back is set, so lg holds the row after
                 # temperature / top-k / top-p; the kernel warps it further in place and draws from what stays, replacing sample_token's draw —

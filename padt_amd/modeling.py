@@ -267,7 +267,8 @@ class PaDTForConditionalGeneration:
         objects or plain lists of callables ``f(input_ids, scores)``.  They run where the reference runs them — the processors on the step's fp32
         score rows AFTER the logit mask and the built-in processors (repetition penalty), before the arg-max / the sampler; the criteria on the
         sequences including the step's token, OR-ed into the stop state next to EOS and the length limit — on the HOOKED loop: decode steps launched
-        kernel by kernel (no captured graph: the callables are host code), one host sync per step, ``.scores`` = the processed rows.  Not available
+        kernel by kernel (no captured graph: the callables are host code), one host sync per step, ``.scores`` = the processed rows.  A row whose
+        every score the processors set to ``-inf`` continues with the pad token, like a row the built-in bans emptied.  Not available
         inside ``pipeline.PipelinedRunner``'s merged decode groups.
 
         Arguments of the reference's ``generate`` (padt.py:414-434 + the HF generation kwargs it forwards) that this path does not
@@ -594,8 +595,8 @@ class PaDTForConditionalGeneration:
             sess.pos3.zero_()
             sess.cur_tok.fill_(cfg.pad_token_id)
             sess.vrt_off.zero_()
-            if opts.sampling is not None and opts.sampling.warpers:
-                sess.batch_row0.zero_()                           # read by the warper kernel alone
+            if opts.sampling is not None:
+                sess.batch_row0.zero_()                           # read by the sampling kernels alone
             if self.ref is not None and (sess.hid32 is None or sess.hid32.shape[0] < T_max):
                 sess.hid32 = torch.zeros((sess.t_max, sess.B, cfg.hidden_size), device=dev, dtype=torch.float32)
         else:
@@ -645,7 +646,7 @@ class PaDTForConditionalGeneration:
         sess.vrt_off[row0: row0 + B + 1].copy_(off.to(dev, non_blocking=True))
         if row0 + B + 1 < sess.vrt_off.numel():
             sess.vrt_off[row0 + B + 1:].fill_(proto_row0 + n_proto)     # rows not (yet) in use: empty VRT range
-        if opts.sampling is not None and opts.sampling.warpers:
+        if opts.sampling is not None:
             sess.batch_row0[rows].fill_(row0)
         sess.unfinished[rows].fill_(1)
         lens_t = torch.tensor(plan.lens, dtype=torch.int32)

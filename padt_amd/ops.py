@@ -927,12 +927,22 @@ def gen_cfg_tensor(repetition_penalty=1.0, eos_ids=(), device="cuda", do_sample=
     return torch.frombuffer(bytearray(raw), dtype=torch.int32).clone().to(device)
 
 
-def sample_token(logits, n_rows_table, gen_cfg, step, part_val, part_idx, batch):
+def sample_token(logits, n_rows_table, gen_cfg, step, part_val, part_idx, batch, vocab=0, vrt_off=None, row_base=None):
     """One multinomial draw per row from the warped fp32 logits (padt_sample_token) into the (value, index) partial layout; with gen_cfg's
-    write_back the rows [0, n_rows_table) are overwritten with the warped scores (l / T kept, -inf elsewhere)."""
+    write_back the rows [0, n_rows_table) are overwritten with the warped scores (l / T kept, -inf elsewhere).  row_base int32 [>= batch]
+    (with vrt_off int32 [>= batch + 1] and vocab; padt_sample_token_keyed): the first row of each row's own batch in a merged decode group —
+    the generator is then keyed by the row and column numbers the batch has alone, as warp_sample_rows keys its own."""
     assert logits.dtype == torch.float32 and logits.stride(-1) == 1
-    _lib.check(_lib.load().padt_sample_token(_stream(), _p(logits), logits.stride(0), int(n_rows_table), _p(gen_cfg), _p(step), _p(part_val),
-                                             _p(part_idx), int(batch)), "padt_sample_token")
+    if row_base is None:
+        assert vrt_off is None and vocab == 0, "vocab / vrt_off key the generator through row_base only: pass all three or none"
+        _lib.check(_lib.load().padt_sample_token(_stream(), _p(logits), logits.stride(0), int(n_rows_table), _p(gen_cfg), _p(step), _p(part_val),
+                                                 _p(part_idx), int(batch)), "padt_sample_token")
+        return
+    assert row_base.dtype == torch.int32 and row_base.is_contiguous() and row_base.numel() >= batch
+    assert vrt_off is not None and vrt_off.dtype == torch.int32 and vrt_off.is_contiguous() and vrt_off.numel() >= batch + 1
+    _lib.check(_lib.load().padt_sample_token_keyed(_stream(), _p(logits), logits.stride(0), int(n_rows_table), _p(gen_cfg), _p(step),
+                                                   _p(part_val), _p(part_idx), int(batch), int(vocab), _p(vrt_off), _p(row_base)),
+               "padt_sample_token_keyed")
 
 
 def warp_sample_rows(rows, n_cols, gen_cfg, step, part_val, part_idx, batch, vocab=0, vrt_off=None, row_base=None):
