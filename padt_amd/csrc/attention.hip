@@ -358,13 +358,11 @@ struct DecodeArgs {
     int out_packed = 0;     // out in the 16-row fragment-packed activation layout (row length Hq*D)
 };
 
-// decode_attn_kernel and decode_attn_rope_kernel run the SAME softmax arithmetic (the fused kernel is what a decode step launches, the
-// unfused pair llm_qkv_post + decode_attn is its test reference).  `#pragma clang fp contract(off)` pins `s * scale` and the later `x - m` as
-// two roundings in both (hipcc is otherwise free to contract one of them).  K / V appends and the attention outputs are bit-identical between
-// the two paths in both operand types.  (Until the end of round 4 the fp16 instantiation differed in a fraction of a per cent of the outputs
-// at D = 128: the fused kernel's scalar rotation was compiled to v_fma_mixlo_f16 — one rounding — where llm_qkv_post's vector path rounds
-// twice; see rounded32() in common.h.)  Only the fused kernel runs in a decode step, so no product invariant (merged == un-merged decode,
-// graph == eager) ever depended on it.
+// decode_attn_kernel and decode_attn_rope_kernel (the fused kernel is what a decode step launches, the unfused pair llm_qkv_post + decode_attn
+// is its test reference) share ONE definition of a split's arithmetic, decode_split below: they differ only in where its Q, K and V^T
+// fragments come from.  `#pragma clang fp contract(off)` in that body pins `s * scale` and the later `x - m` as two roundings (hipcc is otherwise
+// free to contract one of them).  K / V appends and the attention outputs are bit-identical between the two paths in both operand types: what
+// remains to keep equal by hand is the rotation in the fused kernel's prologue, which rounds as llm_qkv_post does (rounded32() in common.h).
 // Keys >= len of the split that contains len: their probabilities are exactly 0, but 0 x inf is NaN, and a reused cache holds whatever an earlier
 // (possibly overflowed) batch wrote there.  The V^T fragment of such keys is zeroed: element e of the 16-bit pair word w sits at key offset off(w) + e.
 PADT_DEV unsigned keep_keys2(unsigned w, int off, int n) {
@@ -377,38 +375,27 @@ PADT_DEV u32x4 keep_keys8(u32x4 v, int n) {
     return v;
 }
 
-template <int D>
-__global__ __launch_bounds__(64) void decode_attn_kernel(DecodeArgs p) {
+// One 64-key split [k0, k0 + 64) of decode attention, k0 < len: scores of the 16 q rows over four 16-key blocks, the scaled and masked row
+// maximum, exp2f and the row sum, P through LDS, P·V in two 32-key steps, the partial stores.  The sources are callables, each returning what
+// this lane (frow = lane & 15, fq = lane >> 4) feeds the MFMA:
+//   q_frag(kk)     q row frow, elements [32 kk + 8 fq, + 8)                       (zero beyond the GQA group)
+//   k_frag(kb, kk) the same elements of key k0 + 16 kb + frow
+//   v_frag(ks, i)  V^T row d = 16 i + frow, keys [k0 + 32 ks + 8 fq, + 8) as 16 bytes, stale keys >= len included: the body zeroes them
+template <int D, class QF, class KF, class VF>
+PADT_DEV void decode_split(int k0, int len, float scale_log2, float* part_o, float* part_ml, long pbase, QF q_frag, KF k_frag, VF v_frag) {
 #pragma clang fp contract(off)
     __shared__ __attribute__((aligned(16))) x16_t Pw[16 * 72];
-    const int lane = threadIdx.x, frow = lane & 15, fq = lane >> 4;
-    const int split = blockIdx.x, g = blockIdx.y, b = blockIdx.z;
-    const int group = p.Hq / p.Hkv;
-    const int len = p.lens[b];
-    const int k0 = split * 64;
-    const long pbase = (((long)b * p.Hkv + g) * p.nsplit + split) * 16;
     constexpr int KQ = D / 32, NB = D / 16;
-
-    if (k0 >= len) {                                              // empty split: neutral partial
-        if (lane < 16) { p.part_ml[(pbase + lane) * 2] = -INFINITY; p.part_ml[(pbase + lane) * 2 + 1] = 0.f; }
-        return;
-    }
+    const int lane = threadIdx.x, frow = lane & 15, fq = lane >> 4;
     x16x8 qf[KQ];
 #pragma unroll
-    for (int kk = 0; kk < KQ; ++kk)
-        qf[kk] = (frow < group) ? ld_frag(p.q + (long)b * p.Hq * D + (g * group + frow) * D + kk * 32 + fq * 8) : zero_frag();
-
-    const x16_t* kbase = p.kc + ((long)b * p.Hkv + g) * p.S_max * D;
-    const x16_t* vbase = p.vtc + ((long)b * p.Hkv + g) * D * (long)p.S_max;
-
+    for (int kk = 0; kk < KQ; ++kk) qf[kk] = q_frag(kk);
     f32x4 s[4];
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) {
         s[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
-        int key = k0 + kb * 16 + frow;
-        key = key < p.S_max ? key : p.S_max - 1;
 #pragma unroll
-        for (int kk = 0; kk < KQ; ++kk) s[kb] = mfma16(qf[kk], ld_frag(kbase + (long)key * D + kk * 32 + fq * 8), s[kb]);
+        for (int kk = 0; kk < KQ; ++kk) s[kb] = mfma16(qf[kk], k_frag(kb, kk), s[kb]);
     }
     float mrow[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
 #pragma unroll
@@ -416,7 +403,7 @@ __global__ __launch_bounds__(64) void decode_attn_kernel(DecodeArgs p) {
         const int key = k0 + kb * 16 + frow;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            float x = (key < len) ? s[kb][r] * p.scale_log2 : -INFINITY;
+            const float x = (key < len) ? s[kb][r] * scale_log2 : -INFINITY;
             s[kb][r] = x;
             mrow[r] = fmaxf(mrow[r], x);
         }
@@ -453,15 +440,14 @@ __global__ __launch_bounds__(64) void decode_attn_kernel(DecodeArgs p) {
     f32x4 o[NB];
 #pragma unroll
     for (int i = 0; i < NB; ++i) o[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const bool tail = len - k0 < 64;                              // the split that contains len: keys >= len must not reach P·V
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
         const x16x8 pf = ld_frag(Pw + frow * 72 + ks * 32 + fq * 8);
-        int kk0 = k0 + ks * 32 + fq * 8;                          // 8 keys, 16-byte aligned in the V^T row
-        kk0 = (kk0 + 8 <= p.S_max) ? kk0 : p.S_max - 8;           // (S_max % 64 == 0, so this never actually clamps)
-        const bool tail = len - k0 < 64;                          // the split that contains len: keys >= len must not reach P·V
+        const int kk0 = k0 + ks * 32 + fq * 8;
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
-            u32x4 vv = *reinterpret_cast<const u32x4*>(vbase + (long)(i * 16 + frow) * p.S_max + kk0);
+            u32x4 vv = v_frag(ks, i);
             if (tail) vv = keep_keys8(vv, len - kk0);
             o[i] = mfma16(pf, __builtin_bit_cast(x16x8, vv), o[i]);
         }
@@ -470,11 +456,42 @@ __global__ __launch_bounds__(64) void decode_attn_kernel(DecodeArgs p) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int hrow = fq * 4 + r;
-        float* po = p.part_o + (pbase + hrow) * D;
+        float* po = part_o + (pbase + hrow) * D;
 #pragma unroll
         for (int i = 0; i < NB; ++i) po[i * 16 + frow] = o[i][r];
-        if (frow == 0) { p.part_ml[(pbase + hrow) * 2] = mrow[r]; p.part_ml[(pbase + hrow) * 2 + 1] = lrow[r]; }
+        if (frow == 0) { part_ml[(pbase + hrow) * 2] = mrow[r]; part_ml[(pbase + hrow) * 2 + 1] = lrow[r]; }
     }
+}
+
+template <int D>
+__global__ __launch_bounds__(64) void decode_attn_kernel(DecodeArgs p) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x, frow = lane & 15, fq = lane >> 4;
+    const int split = blockIdx.x, g = blockIdx.y, b = blockIdx.z;
+    const int group = p.Hq / p.Hkv;
+    const int len = p.lens[b];
+    const int k0 = split * 64;
+    const long pbase = (((long)b * p.Hkv + g) * p.nsplit + split) * 16;
+
+    if (k0 >= len) {                                              // empty split: neutral partial
+        if (lane < 16) { p.part_ml[(pbase + lane) * 2] = -INFINITY; p.part_ml[(pbase + lane) * 2 + 1] = 0.f; }
+        return;
+    }
+    const x16_t* kbase = p.kc + ((long)b * p.Hkv + g) * p.S_max * D;
+    const x16_t* vbase = p.vtc + ((long)b * p.Hkv + g) * D * (long)p.S_max;
+    decode_split<D>(
+        k0, len, p.scale_log2, p.part_o, p.part_ml, pbase,
+        [&](int kk) { return (frow < group) ? ld_frag(p.q + (long)b * p.Hq * D + (g * group + frow) * D + kk * 32 + fq * 8) : zero_frag(); },
+        [&](int kb, int kk) {
+            int key = k0 + kb * 16 + frow;
+            key = key < p.S_max ? key : p.S_max - 1;
+            return ld_frag(kbase + (long)key * D + kk * 32 + fq * 8);
+        },
+        [&](int ks, int i) {
+            int kk0 = k0 + ks * 32 + fq * 8;                      // 8 keys, 16-byte aligned in the V^T row
+            kk0 = (kk0 + 8 <= p.S_max) ? kk0 : p.S_max - 8;       // (S_max % 64 == 0, so this never actually clamps)
+            return *reinterpret_cast<const u32x4*>(vbase + (long)(i * 16 + frow) * p.S_max + kk0);
+        });
 }
 
 template <int D>
@@ -547,7 +564,6 @@ __global__ __launch_bounds__(64) void decode_attn_rope_kernel(DecodeRopeArgs p) 
     __shared__ __attribute__((aligned(16))) x16_t Qs[16 * QROW];
     __shared__ __attribute__((aligned(16))) x16_t Knew[D];
     __shared__ __attribute__((aligned(16))) x16_t Vnew[D];
-    __shared__ __attribute__((aligned(16))) x16_t Pw[16 * 72];
     __shared__ __attribute__((aligned(16))) x16_t Raw[18 * D];
     __shared__ __attribute__((aligned(16))) float Cs[D];
     const int lane = threadIdx.x, frow = lane & 15, fq = lane >> 4;
@@ -634,76 +650,20 @@ __global__ __launch_bounds__(64) void decode_attn_rope_kernel(DecodeRopeArgs p) 
     }
     __syncthreads();
 
-    x16x8 qf[KQ];
-#pragma unroll
-    for (int kk = 0; kk < KQ; ++kk) qf[kk] = ld_frag(Qs + frow * QROW + kk * 32 + fq * 8);
-    f32x4 s[4];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-        s[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int key = k0 + kb * 16 + frow;
-#pragma unroll
-        for (int kk = 0; kk < KQ; ++kk) {
+    // the fresh token's K row and V^T column come from LDS; every other key from the registers loaded above
+    decode_split<D>(
+        k0, len, p.scale_log2, p.part_o, p.part_ml, pbase,
+        [&](int kk) { return ld_frag(Qs + frow * QROW + kk * 32 + fq * 8); },
+        [&](int kb, int kk) {
+            const int key = k0 + kb * 16 + frow;
             const x16x8 kn = ld_frag(Knew + kk * 32 + fq * 8);
-            const x16x8 kf = (key == slot) ? kn : __builtin_bit_cast(x16x8, kraw[kb][kk]);
-            s[kb] = mfma16(qf[kk], kf, s[kb]);
-        }
-    }
-    float mrow[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-        const int key = k0 + kb * 16 + frow;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float x = (key < len) ? s[kb][r] * p.scale_log2 : -INFINITY;
-            s[kb][r] = x;
-            mrow[r] = fmaxf(mrow[r], x);
-        }
-    }
-    float lrow[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        float m = mrow[r];
-        m = fmaxf(m, __shfl_xor(m, 1, 64));
-        m = fmaxf(m, __shfl_xor(m, 2, 64));
-        m = fmaxf(m, __shfl_xor(m, 4, 64));
-        m = fmaxf(m, __shfl_xor(m, 8, 64));
-        mrow[r] = m;
-        lrow[r] = 0.f;
-    }
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float pv = exp2f(s[kb][r] - mrow[r]);
-            lrow[r] += pv;
-            Pw[(fq * 4 + r) * 72 + kb * 16 + frow] = f2x(pv);
-        }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        float t = lrow[r];
-        t += __shfl_xor(t, 1, 64);
-        t += __shfl_xor(t, 2, 64);
-        t += __shfl_xor(t, 4, 64);
-        t += __shfl_xor(t, 8, 64);
-        lrow[r] = t;
-    }
-    __syncthreads();
-    f32x4 o[NB];
-#pragma unroll
-    for (int i = 0; i < NB; ++i) o[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        const x16x8 pf = ld_frag(Pw + frow * 72 + ks * 32 + fq * 8);
-        const int kk0 = k0 + ks * 32 + fq * 8;                     // 8 consecutive keys of the V^T row
-        const int j = slot - kk0;                                  // position of the fresh token inside this fragment
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            const int d = i * 16 + frow;
+            return (key == slot) ? kn : __builtin_bit_cast(x16x8, kraw[kb][kk]);
+        },
+        [&](int ks, int i) {
+            const int j = slot - (k0 + ks * 32 + fq * 8);         // position of the fresh token inside this fragment's 8 keys
             u32x4 vv = vraw[ks][i];
-            if (owner) vv = keep_keys8(vv, len - kk0);             // stale keys past len (keep_keys2)
             if (j >= 0 && j < 8) {
-                const unsigned nv = Vnew[d];
+                const unsigned nv = Vnew[i * 16 + frow];
                 const int wsel = j >> 1;
 #pragma unroll
                 for (int w2 = 0; w2 < 4; ++w2) {
@@ -712,17 +672,8 @@ __global__ __launch_bounds__(64) void decode_attn_rope_kernel(DecodeRopeArgs p) 
                     vv[w2] = (w2 == wsel) ? pat : cur;
                 }
             }
-            o[i] = mfma16(pf, __builtin_bit_cast(x16x8, vv), o[i]);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int hrow = fq * 4 + r;
-        float* po = p.part_o + (pbase + hrow) * D;
-#pragma unroll
-        for (int i = 0; i < NB; ++i) po[i * 16 + frow] = o[i][r];
-        if (frow == 0) { p.part_ml[(pbase + hrow) * 2] = mrow[r]; p.part_ml[(pbase + hrow) * 2 + 1] = lrow[r]; }
-    }
+            return vv;
+        });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1173,10 +1124,9 @@ __global__ void rope_table_kernel(const int* __restrict__ pos3, const float* __r
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * half) return;
     const int b = i / half, d = i % half;
-    const int axis = d < sec0 ? 0 : (d < sec0 + sec1 ? 1 : 2);
-    const float ang = (float)pos3[axis * B + b] * inv_freq[d];
-    cs[2 * i] = cosf(ang);
-    cs[2 * i + 1] = sinf(ang);
+    const float2 a = mrope_cs(d, pos3 + b, B, inv_freq, sec0, sec1);
+    cs[2 * i] = a.x;
+    cs[2 * i + 1] = a.y;
 }
 
 extern "C" int padt_rope_table(void* stream, const int* pos3, const void* inv_freq, void* rope_cs, int batch, int head_dim,

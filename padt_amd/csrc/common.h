@@ -225,6 +225,14 @@ PADT_DEV float rope_fin(float r) { return r; }
 PADT_DEV float rope_lo(float x1, float x2, float c, float s) { return rope_fin(__builtin_fmaf(-x2, s, x1 * c)); }   // x1 cos - x2 sin
 PADT_DEV float rope_hi(float x1, float x2, float c, float s) { return rope_fin(__builtin_fmaf(x1, s, x2 * c)); }    // x2 cos + x1 sin
 
+// (cos, sin) of rotation pair d (< D/2) at one token of an mRoPE position table [3][stride]: pos = &table[0][token]; the two section
+// bounds pick the (t, h, w) axis (HF:557-599).  The one place the angle is formed: the prompt's post-pass and the decode step's table agree.
+PADT_DEV float2 mrope_cs(int d, const int* pos, long stride, const float* inv_freq, int sec0, int sec1) {
+    const int axis = d < sec0 ? 0 : (d < sec0 + sec1 ? 1 : 2);
+    const float ang = (float)pos[(long)axis * stride] * inv_freq[d];
+    return float2{cosf(ang), sinf(ang)};
+}
+
 PADT_DEV void rope_pairs(float* o, int m, int n, const RopeEpi& r) {
     if (r.cos == nullptr || n >= r.cols) return;
     const int i = (n % r.D) >> 1;                  // pair index of columns (n, n+1); (n+2, n+3) is pair i + 1
@@ -265,6 +273,34 @@ PADT_DEV float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+
+// PaDT mask head tail (padt_decoder.py:241-274): e2[(n,a,b)][(c,d,:)] · mask_tok[obj(n)] → masks[obj][4*row+2a+c][4*col+2b+d]
+// e2: [4*Np][4*dm] (row = patch*4 + a*2 + b, col = (c*2+d)*dm + k), tok: [n_obj][dm]; T = x16_t (elementwise.hip, bf16) or float
+// (decoder_hp.hip) — each instantiated in one translation unit.  Products and their sum are fp32 in k order for either T.
+template <class T>
+__global__ __launch_bounds__(256) void mask_scatter_kernel(const T* __restrict__ e2, long ld_e2, const T* __restrict__ tok, long ld_tok,
+                                                           const int* __restrict__ cu_patch, const int* __restrict__ obj_w,
+                                                           float* __restrict__ masks, int n_obj, int Hm4, int Wm4, int dm) {
+    auto f32 = [](T v) { if constexpr (sizeof(T) == 2) return x2f(v); else return v; };
+    // one thread per output logit: index = ((patch*4 + ab)*4 + cd)
+    const long total = (long)cu_patch[n_obj] * 16;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int cd = (int)(i & 3), ab = (int)((i >> 2) & 3);
+        const long patch = i >> 4;
+        int lo = 0, hi = n_obj;                                    // obj = last o with cu_patch[o] <= patch
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (cu_patch[mid] <= patch) lo = mid; else hi = mid; }
+        const int obj = lo;
+        const int pin = (int)(patch - cu_patch[obj]);
+        const int W = obj_w[obj];
+        const int prow = pin / W, pcol = pin % W;
+        const T* e = e2 + (patch * 4 + ab) * ld_e2 + (long)cd * dm;
+        const T* tk = tok + (long)obj * ld_tok;
+        float acc = 0.f;
+        for (int k = 0; k < dm; ++k) acc += f32(e[k]) * f32(tk[k]);
+        const int a = ab >> 1, bb = ab & 1, c = cd >> 1, d = cd & 1;
+        masks[((long)obj * Hm4 + prow * 4 + a * 2 + c) * Wm4 + pcol * 4 + bb * 2 + d] = acc;
+    }
 }
 
 // XCD-aware, bijective remap of a 1-D block id (guide T1): each of the 8 XCDs (private L2) gets a contiguous chunk of

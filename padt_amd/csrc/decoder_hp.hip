@@ -375,30 +375,6 @@ __global__ __launch_bounds__(256) void attn_f32_kfew_kernel(AttnF32Args p) {
     }
 }
 
-// mask head tail (padt_decoder.py:241-274) on fp32 operands: e2[(n,a,b)][(c,d,:)] · mask_tok[obj(n)] → masks[obj][4*row+2a+c][4*col+2b+d]
-__global__ __launch_bounds__(256) void mask_scatter_f32_kernel(const float* __restrict__ e2, long ld_e2, const float* __restrict__ tok,
-                                                               long ld_tok, const int* __restrict__ cu_patch,
-                                                               const int* __restrict__ obj_w, float* __restrict__ masks, int n_obj,
-                                                               int Hm4, int Wm4, int dm) {
-    const long total = (long)cu_patch[n_obj] * 16;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int cd = (int)(i & 3), ab = (int)((i >> 2) & 3);
-        const long patch = i >> 4;
-        int lo = 0, hi = n_obj;
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (cu_patch[mid] <= patch) lo = mid; else hi = mid; }
-        const int obj = lo;
-        const int pin = (int)(patch - cu_patch[obj]);
-        const int W = obj_w[obj];
-        const int prow = pin / W, pcol = pin % W;
-        const float* e = e2 + (patch * 4 + ab) * ld_e2 + (long)cd * dm;
-        const float* tk = tok + (long)obj * ld_tok;
-        float acc = 0.f;
-        for (int k = 0; k < dm; ++k) acc += e[k] * tk[k];
-        const int a = ab >> 1, bb = ab & 1, c = cd >> 1, d = cd & 1;
-        masks[((long)obj * Hm4 + prow * 4 + a * 2 + c) * Wm4 + pcol * 4 + bb * 2 + d] = acc;
-    }
-}
-
 }  // namespace
 
 // y0 = f(x) and/or y1 = f(x) + pos[r % pos_rows], f(x) = act(RMSNorm_w(x[idx[r]] + add[r / add_div])) with every stage optional;
@@ -774,7 +750,7 @@ extern "C" int padt_mask_scatter_f32(void* stream, const void* e2, long ld_e2, c
     if (n_obj <= 0 || total_patches <= 0) return 0;
     long blocks = (total_patches * 16 + 255) / 256;
     if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(mask_scatter_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)e2, ld_e2,
+    hipLaunchKernelGGL(mask_scatter_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)e2, ld_e2,
                        (const float*)mask_tok, ld_tok, cu_patch, obj_w, (float*)masks_f32, n_obj, Hm4, Wm4, dm);
     PADT_CHECK_LAUNCH();
     return 0;

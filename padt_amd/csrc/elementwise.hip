@@ -577,22 +577,43 @@ PADT_DEV long vtc_offset(int slot, int d, int S_max, int packed) {      // V^T: 
                   : (long)d * S_max + slot;
 }
 
-__global__ __launch_bounds__(256) void llm_qkv_post_kernel(QkvPostArgs p) {
+// a pair (r1 at o1, r2 at o2) of 16-byte chunks or of single elements
+template <class V> PADT_DEV void put2(x16_t* base, long o1, long o2, V r1, V r2) {
+    *reinterpret_cast<V*>(base + o1) = r1;
+    *reinterpret_cast<V*>(base + o2) = r2;
+}
+
+// The post-pass of token t, written once: angles per token, rotation of the q and k heads (16-byte path: pack8; scalar path: one rounding
+// through rounded32), the q row, and the roped K row / the V row handed to the destinations of a Sink.  A sink lists destinations
+// n in [n0, n1) and says of each
+//   cache(n, b, slot): whether it has a cache image (both cache forms), and if so of which sample at which slot;
+//   k_row(n), v_row(n): its row-major [Hkv * D] K row / V row, or null.
+// A = QkvPostArgs or QkvPostSharedArgs: the fields read here carry the same names in both.
+template <class A, class Sink>
+PADT_DEV void qkv_post_token(const A& p, int t, const Sink& sink) {
     __shared__ float cs[2][128];                                  // cos / sin of this token's D/2 angles (D <= 256)
-    const int t = blockIdx.x;
     const int half = p.D >> 1;
-    const int b = p.sample ? p.sample[t] : t;
-    const int slot = p.slot ? p.slot[t] : p.lens[b];
     const x16_t* row = p.qkv + (long)t * p.ld;
     // the angle depends on (token, d) only: computed once per token, not once per head
     for (int d = threadIdx.x; d < half; d += blockDim.x) {
-        const int axis = d < p.sec0 ? 0 : (d < p.sec0 + p.sec1 ? 1 : 2);
-        const float ang = (float)p.pos[(long)axis * p.T + t] * p.inv_freq[d];
-        cs[0][d] = cosf(ang);
-        cs[1][d] = sinf(ang);
+        const float2 a = mrope_cs(d, p.pos + t, p.T, p.inv_freq, p.sec0, p.sec1);
+        cs[0][d] = a.x;
+        cs[1][d] = a.y;
     }
     __syncthreads();
-    if (p.vec) {
+    // elements [d, d + |V|) of kv head g's roped row (r1) and their partners D/2 further (r2); a 16-byte chunk (d % 8 == 0) is contiguous in both images
+    auto put_k = [&](int g, int d, auto r1, auto r2) {
+        for (int n = sink.n0; n < sink.n1; ++n) {
+            int b, slot;
+            if (sink.cache(n, b, slot)) {
+                x16_t* kc = p.kc + ((long)b * p.Hkv + g) * p.S_max * p.D;
+                put2(kc, kc_offset(slot, d, p.D, p.cache_packed), kc_offset(slot, d + half, p.D, p.cache_packed), r1, r2);
+            }
+            if (x16_t* kr = sink.k_row(n)) put2(kr + (long)g * p.D, d, d + half, r1, r2);
+        }
+    };
+    const bool vec = p.vec != 0;
+    if (vec) {
         // 16-byte path: item = (head, 8-wide chunk of the first half); its partner chunk sits D/2 further
         const int cph = half >> 3;
         const int items = (p.Hq + p.Hkv) * cph;
@@ -609,21 +630,8 @@ __global__ __launch_bounds__(256) void llm_qkv_post_kernel(QkvPostArgs p) {
                 o2[e] = rope_hi(x1[e], x2[e], c, sn);
             }
             const u32x4 r1 = pack8(o1), r2 = pack8(o2);
-            if (h < p.Hq) {
-                x16_t* q = p.q_out + (long)t * p.ld_q + (long)h * p.D + d;
-                *reinterpret_cast<u32x4*>(q) = r1;
-                *reinterpret_cast<u32x4*>(q + half) = r2;
-            } else {
-                const int g = h - p.Hq;
-                x16_t* kc = p.kc + ((long)b * p.Hkv + g) * p.S_max * p.D;         // an 8-wide chunk (d % 8 == 0) is contiguous in both images
-                *reinterpret_cast<u32x4*>(kc + kc_offset(slot, d, p.D, p.cache_packed)) = r1;
-                *reinterpret_cast<u32x4*>(kc + kc_offset(slot, d + half, p.D, p.cache_packed)) = r2;
-                if (p.k_pack) {
-                    x16_t* kp = p.k_pack + (long)t * p.ld_kp + (long)g * p.D + d;
-                    *reinterpret_cast<u32x4*>(kp) = r1;
-                    *reinterpret_cast<u32x4*>(kp + half) = r2;
-                }
-            }
+            if (h < p.Hq) put2(p.q_out + (long)t * p.ld_q + (long)h * p.D, d, d + half, r1, r2);
+            else put_k(h - p.Hq, d, r1, r2);
         }
     } else {
         const int nqk = (p.Hq + p.Hkv) * half;
@@ -633,25 +641,46 @@ __global__ __launch_bounds__(256) void llm_qkv_post_kernel(QkvPostArgs p) {
             const x16_t* x = row + (long)h * p.D;
             const float x1 = x2f(x[d]), x2 = x2f(x[d + half]);
             const x16_t o1 = f2x(rounded32(rope_lo(x1, x2, c, s))), o2 = f2x(rounded32(rope_hi(x1, x2, c, s)));
-            if (h < p.Hq) {
-                x16_t* q = p.q_out + (long)t * p.ld_q + (long)h * p.D;
-                q[d] = o1; q[d + half] = o2;
-            } else {
-                const int g = h - p.Hq;
-                x16_t* kc = p.kc + ((long)b * p.Hkv + g) * p.S_max * p.D;
-                kc[kc_offset(slot, d, p.D, p.cache_packed)] = o1; kc[kc_offset(slot, d + half, p.D, p.cache_packed)] = o2;
-                if (p.k_pack) {
-                    x16_t* kp = p.k_pack + (long)t * p.ld_kp + (long)g * p.D;
-                    kp[d] = o1; kp[d + half] = o2;
-                }
-            }
+            if (h < p.Hq) put2(p.q_out + (long)t * p.ld_q + (long)h * p.D, d, d + half, o1, o2);
+            else put_k(h - p.Hq, d, o1, o2);
         }
     }
     const x16_t* v = row + (long)(p.Hq + p.Hkv) * p.D;
-    for (int i = threadIdx.x; i < p.Hkv * p.D; i += blockDim.x) {
-        const int g = i / p.D, d = i % p.D;
-        p.vtc[((long)b * p.Hkv + g) * p.D * p.S_max + vtc_offset(slot, d, p.S_max, p.cache_packed)] = v[i];
+    const int nv = p.Hkv * p.D;
+    for (int n = sink.n0; n < sink.n1; ++n) {
+        int b, slot;
+        if (sink.cache(n, b, slot)) {
+            for (int i = threadIdx.x; i < nv; i += blockDim.x) {
+                const int g = i / p.D, d = i % p.D;
+                p.vtc[((long)b * p.Hkv + g) * p.D * p.S_max + vtc_offset(slot, d, p.S_max, p.cache_packed)] = v[i];
+            }
+        }
+        if (x16_t* vr = sink.v_row(n)) {
+            if (vec) {                                            // D % 16 == 0 here: the V part of the row starts on a 16-byte boundary
+                for (int i = threadIdx.x * 8; i < nv; i += blockDim.x * 8)
+                    *reinterpret_cast<u32x4*>(vr + i) = *reinterpret_cast<const u32x4*>(v + i);
+            } else {
+                for (int i = threadIdx.x; i < nv; i += blockDim.x) vr[i] = v[i];
+            }
+        }
     }
+}
+
+// one destination: the cache images of `sample` at `slot` (or lens[sample]) and, in a prefill, row t of k_pack
+struct QkvPostOneDst {
+    static constexpr int n0 = 0, n1 = 1;
+    int b, slot;
+    x16_t* kp;
+    PADT_DEV QkvPostOneDst(const QkvPostArgs& p, int t)
+        : b(p.sample ? p.sample[t] : t), slot(p.slot ? p.slot[t] : p.lens[b]), kp(p.k_pack ? p.k_pack + (long)t * p.ld_kp : nullptr) {}
+    PADT_DEV bool cache(int, int& b_, int& slot_) const { b_ = b; slot_ = slot; return true; }
+    PADT_DEV x16_t* k_row(int) const { return kp; }
+    PADT_DEV x16_t* v_row(int) const { return nullptr; }
+};
+
+__global__ __launch_bounds__(256) void llm_qkv_post_kernel(QkvPostArgs p) {
+    const int t = blockIdx.x;
+    qkv_post_token(p, t, QkvPostOneDst(p, t));
 }
 
 extern "C" int PADT_TWIN(padt_llm_qkv_post)(void* stream, const void* qkv, long ld_qkv, const int* pos3, const int* sample,
@@ -675,12 +704,12 @@ extern "C" int PADT_TWIN(padt_llm_qkv_post)(void* stream, const void* qkv, long 
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The same post-processing with FAN-OUT (prompt pass over a shared token set: one image's prompt prefix computed once for every query on
-// it, llm.plan_prompt_shared).  Token t is rotated ONCE — the angles, rope_lo / rope_hi expressions and the single rounding of
-// llm_qkv_post_kernel — its q row is written once, and its roped K row / V row go to every destination n in [dst_off[t], dst_off[t+1]):
+// it, llm.plan_prompt_shared).  Token t is rotated ONCE, by the routine llm_qkv_post_kernel runs (qkv_post_token above), its q row is
+// written once, and its roped K row / V row go to every destination n in [dst_off[t], dst_off[t+1]):
 //   * cache image of session row dst_sample[n] at slot dst_slot[n] (both cache forms), skipped when either is out of range;
 //   * row dst_row[n] of the row-major join buffers k_join / v_join (the k / v operands of the prompt pass's attn_varlen), skipped when
 //     the row is outside [0, n_join).
-// What a destination receives is bit for bit what llm_qkv_post_kernel writes for a copy of the token's qkv row: pure data movement.
+// What a destination receives is bit for bit what llm_qkv_post_kernel writes for a copy of the token's qkv row: the two differ in their sink only.
 struct QkvPostSharedArgs {
     const x16_t* qkv; long ld;
     const int* pos;            // [3][T]
@@ -695,107 +724,23 @@ struct QkvPostSharedArgs {
     int vec;                   // as QkvPostArgs::vec
 };
 
+// the fan-out: destinations [dst_off[t], dst_off[t+1]) of the CSR lists, each range-checked
+struct QkvPostFanOut {
+    const QkvPostSharedArgs& p;
+    int n0, n1;
+    PADT_DEV QkvPostFanOut(const QkvPostSharedArgs& p_, int t) : p(p_), n0(p_.dst_off[t]), n1(p_.dst_off[t + 1]) {}
+    PADT_DEV bool cache(int n, int& b, int& slot) const {
+        b = p.dst_sample[n]; slot = p.dst_slot[n];
+        return (unsigned)b < (unsigned)p.B && (unsigned)slot < (unsigned)p.S_max;
+    }
+    PADT_DEV bool join_ok(int n) const { return (unsigned)p.dst_row[n] < (unsigned)p.n_join; }
+    PADT_DEV x16_t* k_row(int n) const { return join_ok(n) ? p.k_join + (long)p.dst_row[n] * p.ld_kj : nullptr; }
+    PADT_DEV x16_t* v_row(int n) const { return join_ok(n) ? p.v_join + (long)p.dst_row[n] * p.ld_vj : nullptr; }
+};
+
 __global__ __launch_bounds__(256) void llm_qkv_post_shared_kernel(QkvPostSharedArgs p) {
-    __shared__ float cs[2][128];                                  // cos / sin of this token's D/2 angles (D <= 256)
     const int t = blockIdx.x;
-    const int half = p.D >> 1;
-    const int n0 = p.dst_off[t], n1 = p.dst_off[t + 1];
-    const x16_t* row = p.qkv + (long)t * p.ld;
-    for (int d = threadIdx.x; d < half; d += blockDim.x) {
-        const int axis = d < p.sec0 ? 0 : (d < p.sec0 + p.sec1 ? 1 : 2);
-        const float ang = (float)p.pos[(long)axis * p.T + t] * p.inv_freq[d];
-        cs[0][d] = cosf(ang);
-        cs[1][d] = sinf(ang);
-    }
-    __syncthreads();
-    auto cache_ok = [&](int n) { return (unsigned)p.dst_sample[n] < (unsigned)p.B && (unsigned)p.dst_slot[n] < (unsigned)p.S_max; };
-    auto join_ok = [&](int n) { return (unsigned)p.dst_row[n] < (unsigned)p.n_join; };
-    const bool vec = p.vec != 0;
-    if (vec) {
-        // 16-byte path: item = (head, 8-wide chunk of the first half); its partner chunk sits D/2 further
-        const int cph = half >> 3;
-        const int items = (p.Hq + p.Hkv) * cph;
-        for (int i = threadIdx.x; i < items; i += blockDim.x) {
-            const int h = i / cph, d = (i % cph) * 8;
-            const x16_t* x = row + (long)h * p.D + d;
-            float x1[8], x2[8], o1[8], o2[8];
-            unpack8(*reinterpret_cast<const u32x4*>(x), x1);
-            unpack8(*reinterpret_cast<const u32x4*>(x + half), x2);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float c = cs[0][d + e], sn = cs[1][d + e];
-                o1[e] = rope_lo(x1[e], x2[e], c, sn);
-                o2[e] = rope_hi(x1[e], x2[e], c, sn);
-            }
-            const u32x4 r1 = pack8(o1), r2 = pack8(o2);
-            if (h < p.Hq) {
-                x16_t* q = p.q_out + (long)t * p.ld_q + (long)h * p.D + d;
-                *reinterpret_cast<u32x4*>(q) = r1;
-                *reinterpret_cast<u32x4*>(q + half) = r2;
-                continue;
-            }
-            const int g = h - p.Hq;
-            for (int n = n0; n < n1; ++n) {
-                if (cache_ok(n)) {
-                    const int slot = p.dst_slot[n];
-                    x16_t* kc = p.kc + ((long)p.dst_sample[n] * p.Hkv + g) * p.S_max * p.D;
-                    *reinterpret_cast<u32x4*>(kc + kc_offset(slot, d, p.D, p.cache_packed)) = r1;
-                    *reinterpret_cast<u32x4*>(kc + kc_offset(slot, d + half, p.D, p.cache_packed)) = r2;
-                }
-                if (join_ok(n)) {
-                    x16_t* kj = p.k_join + (long)p.dst_row[n] * p.ld_kj + (long)g * p.D + d;
-                    *reinterpret_cast<u32x4*>(kj) = r1;
-                    *reinterpret_cast<u32x4*>(kj + half) = r2;
-                }
-            }
-        }
-    } else {
-        const int nqk = (p.Hq + p.Hkv) * half;
-        for (int i = threadIdx.x; i < nqk; i += blockDim.x) {
-            const int h = i / half, d = i % half;
-            const float c = cs[0][d], s = cs[1][d];
-            const x16_t* x = row + (long)h * p.D;
-            const float x1 = x2f(x[d]), x2 = x2f(x[d + half]);
-            const x16_t o1 = f2x(rounded32(rope_lo(x1, x2, c, s))), o2 = f2x(rounded32(rope_hi(x1, x2, c, s)));
-            if (h < p.Hq) {
-                x16_t* q = p.q_out + (long)t * p.ld_q + (long)h * p.D;
-                q[d] = o1; q[d + half] = o2;
-                continue;
-            }
-            const int g = h - p.Hq;
-            for (int n = n0; n < n1; ++n) {
-                if (cache_ok(n)) {
-                    const int slot = p.dst_slot[n];
-                    x16_t* kc = p.kc + ((long)p.dst_sample[n] * p.Hkv + g) * p.S_max * p.D;
-                    kc[kc_offset(slot, d, p.D, p.cache_packed)] = o1; kc[kc_offset(slot, d + half, p.D, p.cache_packed)] = o2;
-                }
-                if (join_ok(n)) {
-                    x16_t* kj = p.k_join + (long)p.dst_row[n] * p.ld_kj + (long)g * p.D;
-                    kj[d] = o1; kj[d + half] = o2;
-                }
-            }
-        }
-    }
-    const x16_t* v = row + (long)(p.Hq + p.Hkv) * p.D;
-    const int nv = p.Hkv * p.D;
-    for (int n = n0; n < n1; ++n) {
-        if (cache_ok(n)) {
-            const int b = p.dst_sample[n], slot = p.dst_slot[n];
-            for (int i = threadIdx.x; i < nv; i += blockDim.x) {
-                const int g = i / p.D, d = i % p.D;
-                p.vtc[((long)b * p.Hkv + g) * p.D * p.S_max + vtc_offset(slot, d, p.S_max, p.cache_packed)] = v[i];
-            }
-        }
-        if (join_ok(n)) {
-            x16_t* vj = p.v_join + (long)p.dst_row[n] * p.ld_vj;
-            if (vec) {                                            // D % 16 == 0 here: the V part of the row starts on a 16-byte boundary
-                for (int i = threadIdx.x * 8; i < nv; i += blockDim.x * 8)
-                    *reinterpret_cast<u32x4*>(vj + i) = *reinterpret_cast<const u32x4*>(v + i);
-            } else {
-                for (int i = threadIdx.x; i < nv; i += blockDim.x) vj[i] = v[i];
-            }
-        }
-    }
+    qkv_post_token(p, t, QkvPostFanOut(p, t));
 }
 
 extern "C" int PADT_TWIN(padt_llm_qkv_post_shared)(void* stream, const void* qkv, long ld_qkv, const int* pos3, const void* inv_freq,
@@ -833,39 +778,14 @@ extern "C" int PADT_TWIN(padt_llm_qkv_post_shared)(void* stream, const void* qkv
 
 #if !PADT_OP16_F16   // type-independent (or bf16-decoder-only): compiled once
 // ---------------------------------------------------------------------------------------------------------------------
-// PaDT mask head tail (padt_decoder.py:241-274): e2[(n,a,b)][(c,d,:)] · mask_tok[obj(n)] → masks[obj][4*row+2a+c][4*col+2b+d]
-// e2: [4*Np][4*dm] bf16 (row = patch*4 + a*2 + b, col = (c*2+d)*dm + k), tok: [n_obj][dm] bf16.
-__global__ __launch_bounds__(256) void mask_scatter_kernel(const x16_t* __restrict__ e2, long ld_e2,
-                                                           const x16_t* __restrict__ tok, long ld_tok,
-                                                           const int* __restrict__ cu_patch, const int* __restrict__ obj_w,
-                                                           float* __restrict__ masks, int n_obj, int Hm4, int Wm4, int dm) {
-    // one thread per output logit: index = ((patch*4 + ab)*4 + cd)
-    const long total = (long)cu_patch[n_obj] * 16;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int cd = (int)(i & 3), ab = (int)((i >> 2) & 3);
-        const long patch = i >> 4;
-        int lo = 0, hi = n_obj;                                    // obj = last o with cu_patch[o] <= patch
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (cu_patch[mid] <= patch) lo = mid; else hi = mid; }
-        const int obj = lo;
-        const int pin = (int)(patch - cu_patch[obj]);
-        const int W = obj_w[obj];
-        const int prow = pin / W, pcol = pin % W;
-        const x16_t* e = e2 + (patch * 4 + ab) * ld_e2 + (long)cd * dm;
-        const x16_t* tk = tok + (long)obj * ld_tok;
-        float acc = 0.f;
-        for (int k = 0; k < dm; ++k) acc += x2f(e[k]) * x2f(tk[k]);
-        const int a = ab >> 1, bb = ab & 1, c = cd >> 1, d = cd & 1;
-        masks[((long)obj * Hm4 + prow * 4 + a * 2 + c) * Wm4 + pcol * 4 + bb * 2 + d] = acc;
-    }
-}
-
+// PaDT mask head tail (padt_decoder.py:241-274) on bf16 operands: mask_scatter_kernel<x16_t>, common.h
 extern "C" int padt_mask_scatter(void* stream, const void* e2, long ld_e2, const void* mask_tok, long ld_tok,
                                  const int* cu_patch, const int* obj_w, void* masks_f32, int n_obj, long total_patches,
                                  int Hm4, int Wm4, int dm) {
     if (n_obj <= 0 || total_patches <= 0) return 0;
     long blocks = (total_patches * 16 + 255) / 256;
     if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(mask_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const x16_t*)e2,
+    hipLaunchKernelGGL(mask_scatter_kernel<x16_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const x16_t*)e2,
                        ld_e2, (const x16_t*)mask_tok, ld_tok, cu_patch, obj_w, (float*)masks_f32, n_obj, Hm4, Wm4, dm);
     PADT_CHECK_LAUNCH();
     return 0;

@@ -142,6 +142,27 @@ def test_mask_scatter_on_windows(ops, dt, dm):
     fails.done()
 
 
+@pytest.mark.parametrize("dm", [8, 260])
+def test_mask_scatter_f32_of_upcast_bf16_is_mask_scatter(ops, dm):
+    """The two entry points are one kernel over the element type: on the fp32 upcast of bf16 inputs mask_scatter_f32 forms the same fp32
+    products and adds them in the same order as mask_scatter on the bf16 inputs, so the planes are equal bit for bit — no tolerance.
+    Three objects 1, 2 and 3 patches wide (3 x 1, 1 x 2, 2 x 3) in (3, 3) planes."""
+    grids = [(3, 1), (1, 2), (2, 3)]
+    n_obj, Hm, Wm = len(grids), 3, 3
+    cu = [0]
+    for h, w in grids:
+        cu.append(cu[-1] + h * w)
+    N = cu[-1]
+    g = torch.Generator().manual_seed(22)
+    e2, tok = torch.randn(4 * N, 4 * dm, generator=g).to(BF).cuda(), torch.randn(n_obj, dm, generator=g).to(BF).cuda()
+    cu_t, w_t = i32(cu), i32([w for _, w in grids])
+    m16 = ops.mask_scatter(e2, tok, cu_t, w_t, torch.full((n_obj, 4 * Hm, 4 * Wm), 7.0, device="cuda"), n_obj, N, dm)
+    m32 = ops.mask_scatter_f32(e2.float(), tok.float(), cu_t, w_t, torch.full((n_obj, 4 * Hm, 4 * Wm), 7.0, device="cuda"), n_obj, N, dm)
+    written = m16 != 7.0
+    assert int(written.sum()) == 16 * N, "every patch writes its 16 logits (none of which is exactly the fill value)"
+    assert same_bits(m32, m16), f"mask_scatter_f32 on upcast inputs differs from mask_scatter in {int((m32 != m16).sum())} logits"
+
+
 @pytest.mark.parametrize("odt", [F32, BF, F16], ids=["fp32", "bf16", "fp16"])
 def test_patchify_normalize_on_windows(ops, odt):
     """Images 28 x 28, 28 x 56 and 56 x 28 (a swap of H and W shows) as byte slabs — 0x7F and then 0 around them —, the table a slab, `out`
