@@ -497,6 +497,28 @@ int  padt_gen_rules(void* stream, const int* rules, const int* hist, long ld_his
 int  padt_token_automaton(void* stream, const int* table, long table_ints, const void* gen_cfg, const int* vrt_off, const long* tokens,
                           long ld_tokens, const int* step, const int* unfinished, int* state, void* ban, long ban_words,
                           const void* rules_ban, long n_cols, long vocab, long batch);
+/* generate(stop_sequences=, min_tokens=, max_tokens=) (stop_rules.hip): how a row ends, decided inside the decode step.
+ * padt_stop_ban, before the head: min_tokens as a pure ban, HF's MinNewTokensLengthLogitsProcessor(prompt_len, n, eos_ids).  One block per
+ * row writes ban_out[b][0..ban_words) from scratch: ban_in[b] (nullable: zeros; padt_gen_rules' / padt_token_automaton's bitmap of this
+ * step, another buffer) and, while *step < min_tokens[b], the bits of `eos` and of gen_cfg's EOS list.  An id outside [0, n_cols) sets
+ * nothing; n_cols <= 32 ban_words. */
+int  padt_stop_ban(void* stream, const void* gen_cfg, int eos, const int* step, const int* min_tokens, const void* ban_in, void* ban_out,
+                   long ban_words, long n_cols, long batch);
+/* padt_stop_match, after padt_greedy_step / padt_forced_step (whose step-counter bump it follows): with n = *step tokens in row b, for every
+ * row with finish_reason[b] == 0, in this order: tokens[b][n - 1] is an EOS id (eos or gen_cfg's list) → reason 1; n >= min_tokens[b] and
+ * sequence i equals tokens[b][n - m_i .. n) (m_i <= n) → reason 2 with the lowest such i; n >= max_tokens[b] → reason 3.  A finish writes
+ * unfinished[b] = 0, finish_step[b] = n - 1, finish_reason[b], stop_index[b] = i or -1; a row with a recorded finish is never touched again.
+ * Nothing is written unless 1 <= n <= ld_tokens.  table: 2 + 32 + 32 * 32 int32 in DEVICE memory, packed by generation.stop_table:
+ *   [0] magic 0x53523031 [1] n <= 32 sequences [2 .. 34) lengths 1 .. 32 [34 + 32 i ..) the ids of sequence i.
+ * A table that fails the header's checks writes nothing; a length outside 1 .. 32 never matches. */
+int  padt_stop_match(void* stream, const int* table, long table_ints, const void* gen_cfg, int eos, const long* tokens, long ld_tokens,
+                     const int* step, const int* min_tokens, const int* max_tokens, int* unfinished, int* finish_step, int* finish_reason,
+                     int* stop_index, long batch);
+/* padt_collect_summary followed by the rows' finish records: out holds 2 + 5 n_rows + n_batch int32 — padt_collect_summary's
+ * 2 + 2 n_rows + n_batch, then finish_step[n_rows], finish_reason[n_rows], stop_index[n_rows]. */
+int  padt_collect_summary_stop(void* stream, const int* err, const int* unfinished, const int* nf_rows, const int* nf_batch, long n_rows,
+                               long n_batch, const long* tokens, long t_max, long done, int eos, const void* gen_cfg,
+                               const int* finish_step, const int* finish_reason, const int* stop_index, int* out);
 
 /* ---- caller-side post-processing --------------------------------------------------------------- */
 /* out[o][y][x] = sigmoid(bilinear(masks[o][:src_h[o]][:src_w[o]] → dst_h[o] x dst_w[o], align_corners=False))[y][x] > 0.5,

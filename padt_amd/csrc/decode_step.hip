@@ -211,10 +211,14 @@ extern "C" int padt_forced_override(void* stream, void* part_idx, const int* for
 // batch): out = [err, any(unfinished), nf_rows[n_rows], nf_batch[n_batch], first_eos[n_rows]] with first_eos[r] = the first step t < done whose
 // token is one of the EOS ids (config eos or gen->eos[0..3]), -1 if none — the reference stops right after the step in which the last
 // sequence finished (padt.py:756-757), so a batch's length is max over its rows of first_eos + 1.
+// STOP (padt_collect_summary_stop; generate(stop_sequences=, min_tokens=, max_tokens=)): behind that record, what padt_stop_match recorded per
+// row — finish_step[n_rows], finish_reason[n_rows], stop_index[n_rows] — so that a row ended by anything but an EOS id has an end too.
 struct CollectArgs {
     const int* err; const int* unfinished; const int* nf_rows; const int* nf_batch; int n_rows, n_batch;
     const long* tokens; int T_max, done, eos; const GenCfg* gen; int* out;
+    const int* finish_step; const int* finish_reason; const int* stop_index;      // STOP
 };
+template <bool STOP>
 __global__ __launch_bounds__(256) void collect_summary_kernel(CollectArgs p) {
     const int tid = threadIdx.x;
     int unf = 0;
@@ -227,6 +231,12 @@ __global__ __launch_bounds__(256) void collect_summary_kernel(CollectArgs p) {
             if (gen_is_eos(p.gen, row[t], p.eos)) first = t;
         }
         p.out[2 + p.n_rows + p.n_batch + r] = first;
+        if constexpr (STOP) {
+            int* tail = p.out + 2 + 2 * p.n_rows + p.n_batch;
+            tail[r] = p.finish_step[r];
+            tail[p.n_rows + r] = p.finish_reason[r];
+            tail[2 * p.n_rows + r] = p.stop_index[r];
+        }
     }
     for (int b = tid; b < p.n_batch; b += 256) p.out[2 + p.n_rows + b] = p.nf_batch[b];
     const int any = __syncthreads_or(unf);
@@ -236,8 +246,23 @@ __global__ __launch_bounds__(256) void collect_summary_kernel(CollectArgs p) {
 extern "C" int padt_collect_summary(void* stream, const int* err, const int* unfinished, const int* nf_rows, const int* nf_batch, long n_rows,
                                     long n_batch, const long* tokens, long t_max, long done, int eos, const void* gen_cfg, int* out) {
     if (n_rows <= 0 || n_batch < 0 || done < 0 || done > t_max || out == nullptr) { padt_set_error("padt_collect_summary: bad arguments"); return -1; }
-    CollectArgs a{err, unfinished, nf_rows, nf_batch, (int)n_rows, (int)n_batch, tokens, (int)t_max, (int)done, eos, (const GenCfg*)gen_cfg, out};
-    hipLaunchKernelGGL(collect_summary_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    CollectArgs a{err, unfinished, nf_rows, nf_batch, (int)n_rows, (int)n_batch, tokens, (int)t_max, (int)done, eos, (const GenCfg*)gen_cfg, out,
+                  nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(collect_summary_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    PADT_CHECK_LAUNCH();
+    return 0;
+}
+
+// padt_collect_summary with the rows' finish records behind its record: out holds 2 + 5 n_rows + n_batch int32.
+extern "C" int padt_collect_summary_stop(void* stream, const int* err, const int* unfinished, const int* nf_rows, const int* nf_batch,
+                                         long n_rows, long n_batch, const long* tokens, long t_max, long done, int eos, const void* gen_cfg,
+                                         const int* finish_step, const int* finish_reason, const int* stop_index, int* out) {
+    if (n_rows <= 0 || n_batch < 0 || done < 0 || done > t_max || out == nullptr || !finish_step || !finish_reason || !stop_index) {
+        padt_set_error("padt_collect_summary_stop: bad arguments"); return -1;
+    }
+    CollectArgs a{err, unfinished, nf_rows, nf_batch, (int)n_rows, (int)n_batch, tokens, (int)t_max, (int)done, eos, (const GenCfg*)gen_cfg, out,
+                  finish_step, finish_reason, stop_index};
+    hipLaunchKernelGGL(collect_summary_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
     PADT_CHECK_LAUNCH();
     return 0;
 }

@@ -542,6 +542,148 @@ def score_bias_row(logits, bias=None, penalty=1.0, seen=None, banned=None, eos_i
     return x
 
 
+# ------------------------------------------------------------------------------------------------ generate(stop_sequences=, min_tokens=, max_tokens=)
+# How a row ENDS.  The specification (stop_ban_ids / stop_state below are its plain statement; padt_stop_ban and padt_stop_match are compared
+# against them bit for bit), for a row that holds n generated tokens after a step:
+#   * before the step's head, with t = n tokens so far: while t < min_tokens every EOS id (the config's and the call's list) is banned —
+#     HF's MinNewTokensLengthLogitsProcessor(prompt_len, min_tokens, eos_ids); a pure ban, so its place among the processors does not matter;
+#   * after the step: 1. token n - 1 is an EOS id → "eos" (a forced EOS still ends the row, whatever min_tokens says);  2. n >= min_tokens
+#     and one of the sequences equals the row's last tokens → "stop", the lowest index among those completing (vLLM's rule: a sequence
+#     completing below min_tokens is ignored, and not matched retroactively later);  3. n >= max_tokens → "length".
+# The prompt is never matched; the sequence's tokens stay in the output, as an EOS does.
+# NOT HF's min_new_tokens / min_length / stop_strings / max_time: those names stay refused exactly as they are.
+STOP_MAX_SEQS, STOP_MAX_LEN = ops.STOP_RULES_MAX_SEQS, ops.STOP_RULES_MAX_LEN
+NO_BUDGET = 2 ** 31 - 1          # max_tokens of a row without a budget: never reached
+
+
+def check_stop_sequences(stop_sequences, vocab_size=None):
+    """generate(stop_sequences=) → its normal form: a tuple of id tuples in the caller's order (``stop_index`` names a position in it; a
+    repeated sequence keeps both places); None for None.  Text ids only: a VRT id raises NotImplementedError with the rule table's wording, an
+    empty list, an empty sequence or a malformed id ValueError, more than STOP_MAX_SEQS sequences or STOP_MAX_LEN ids in one
+    NotImplementedError naming the argument and the cap."""
+    name = "stop_sequences"
+    if stop_sequences is None:
+        return None
+    if isinstance(stop_sequences, (str, bytes, numbers.Integral)):
+        raise ValueError(f"generate({name}=...): a list of token-id lists is required, got {stop_sequences!r} (strings need the tokenizer: "
+                         "stop_strings stays refused)")
+    try:
+        seqs = [s.tolist() if isinstance(s, torch.Tensor) else s for s in stop_sequences]
+        seqs = [list(s) for s in seqs]
+    except TypeError:
+        raise ValueError(f"generate({name}=...): a list of token-id lists is required, got {stop_sequences!r}") from None
+    if not seqs:
+        raise ValueError(f"generate({name}=[]): an empty list stops nothing — pass None")
+    if len(seqs) > STOP_MAX_SEQS:
+        raise NotImplementedError(f"generate({name}=...): {len(seqs)} sequences; at most {STOP_MAX_SEQS} on the MI355X path")
+    out = []
+    for i, s in enumerate(seqs):
+        if not s:
+            raise ValueError(f"generate({name}=...): sequence {i} is empty")
+        if len(s) > STOP_MAX_LEN:
+            raise NotImplementedError(f"generate({name}=...): sequence {i} has {len(s)} ids; at most {STOP_MAX_LEN} on the MI355X path")
+        out.append(tuple(ops._rule_ids(name, s, vocab_size)))
+    return tuple(out)
+
+
+def stop_table(sequences) -> torch.Tensor:
+    """The packed int32 CPU table padt_stop_match reads (ops.STOP_RULES_INTS ints, fixed size; layout in include/padt_hip.h) for stop
+    sequences in check_stop_sequences' normal form; None / (): no sequence."""
+    seqs = check_stop_sequences(sequences) if sequences else ()
+    t = [ops.STOP_RULES_MAGIC, len(seqs)] + [len(s) for s in seqs] + [0] * (STOP_MAX_SEQS - len(seqs))
+    for s in seqs:
+        t += list(s) + [0] * (STOP_MAX_LEN - len(s))
+    t += [0] * (ops.STOP_RULES_INTS - len(t))
+    return torch.tensor(t, dtype=torch.int32)
+
+
+def _row_counts(name, value, B):
+    """an int, or one int per row → (is_scalar, list of B ints)"""
+    if isinstance(value, torch.Tensor):
+        if value.dtype.is_floating_point or value.dtype.is_complex or value.dtype == torch.bool or value.dim() > 1:
+            raise ValueError(f"generate({name}=...): an integer or one integer per row is required, got a {value.dtype} tensor of shape {tuple(value.shape)}")
+        value = int(value) if value.dim() == 0 else value.tolist()
+    if isinstance(value, numbers.Integral) and not isinstance(value, bool):
+        return True, [int(value)] * int(B)
+    try:
+        vals = list(value)
+    except TypeError:
+        raise ValueError(f"generate({name}=...): an integer or one integer per row is required, got {value!r}") from None
+    for v in vals:
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError(f"generate({name}=...): an integer or one integer per row is required, got {v!r}")
+    if len(vals) != int(B):
+        raise ValueError(f"generate({name}=...): {len(vals)} entries for a batch of {int(B)} samples")
+    return False, [int(v) for v in vals]
+
+
+def check_max_tokens(max_tokens, B, max_new_tokens):
+    """generate(max_tokens=) → a list of B budgets (an int applies to every row), None for None.  ValueError naming the argument and the row
+    unless 1 <= max_tokens[b] <= max_new_tokens."""
+    if max_tokens is None:
+        return None
+    _, vals = _row_counts("max_tokens", max_tokens, B)
+    for b, v in enumerate(vals):
+        if not 1 <= v <= int(max_new_tokens):
+            raise ValueError(f"generate(max_tokens=...): row {b}: {v} is outside [1, max_new_tokens={int(max_new_tokens)}]")
+    return vals
+
+
+def check_min_tokens(min_tokens, B, max_new_tokens, max_tokens=None):
+    """generate(min_tokens=) → an int (one value for the call: part of GenOptions) or a list of B ints (per-batch data), None for None.
+    max_tokens: check_max_tokens' list or None — a row's budget is its entry, or max_new_tokens.  ValueError naming the argument and the row
+    for a negative value or one above the row's budget."""
+    if min_tokens is None:
+        return None
+    scalar, vals = _row_counts("min_tokens", min_tokens, B)
+    for b, v in enumerate(vals):
+        budget = int(max_new_tokens) if max_tokens is None else int(max_tokens[b])
+        if v < 0:
+            raise ValueError(f"generate(min_tokens=...): row {b}: {v} is negative")
+        if v > budget:
+            raise ValueError(f"generate(min_tokens=...): row {b}: {v} tokens are more than the row's budget of {budget} "
+                             f"({'max_new_tokens' if max_tokens is None else 'its max_tokens'})")
+    return vals[0] if scalar and vals else (None if scalar else vals)
+
+
+def stop_ban_ids(step, min_tokens, eos_ids):
+    """The ids generate(min_tokens=) bans at the step that selects token `step` (the row holds `step` generated tokens): every id of eos_ids
+    while step < min_tokens, nothing afterwards — sorted, without duplicates or negative (unused) entries."""
+    return sorted({int(e) for e in eos_ids if int(e) >= 0}) if int(step) < int(min_tokens) else []
+
+
+def stop_state(tokens, n, sequences, min_tokens, max_tokens, eos_ids):
+    """Does the row's n-th generated token end it?  → (finished, reason, index): reason "eos" / "stop" / "length" (None: not finished), index
+    the matched sequence or -1.  tokens: the row's generated tokens (the first n are read); sequences: check_stop_sequences' normal form or
+    None; eos_ids: every id that ends a row.  Precedence: EOS, then the lowest-indexed sequence equal to tokens[n - m : n] (only when
+    n >= min_tokens and m <= n), then the budget (n >= max_tokens; None: no budget).  The state of a row over a whole run is the FIRST n at
+    which this holds (stop_scan): a row is not looked at again after it finished."""
+    n = int(n)
+    if n < 1:
+        return False, None, -1
+    row = [int(x) for x in tokens[:n]]
+    if row[-1] in {int(e) for e in eos_ids}:
+        return True, "eos", -1
+    if n >= int(min_tokens):
+        for i, s in enumerate(sequences or ()):
+            m = len(s)
+            if 1 <= m <= n and row[n - m:] == [int(x) for x in s]:
+                return True, "stop", i
+    if max_tokens is not None and n >= int(max_tokens):
+        return True, "length", -1
+    return False, None, -1
+
+
+def stop_scan(tokens, sequences, min_tokens, max_tokens, eos_ids):
+    """The first n at which stop_state(tokens, n, ...) finishes the row → (finish_step = n - 1, reason, index); (-1, "length", -1) for a
+    row still running after all of `tokens`."""
+    for n in range(1, len(tokens) + 1):
+        fin, reason, index = stop_state(tokens, n, sequences, min_tokens, max_tokens, eos_ids)
+        if fin:
+            return n - 1, reason, index
+    return -1, "length", -1
+
+
 # generate()'s named parameters a generation_config may carry: an explicit argument (not None) wins, as in HF (padt.py:436)
 _GENERATE_CONFIG_NAMED = ("max_new_tokens", "max_length", "do_sample", "repetition_penalty", "eos_token_id", "pad_token_id", "temperature", "top_k",
                           "top_p", "no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens", "min_p", "typical_p",
@@ -632,6 +774,7 @@ class StepMode(NamedTuple):
     forced: bool = False             # generate(forced_tokens=): the probe head / padt_forced_step / padt_forced_override read the session's table
     automaton: bool = False          # generate(token_automaton=): padt_token_automaton writes the bitmap the head reads (the union with the rules')
     bias: bool = False               # logit_bias / patch_bias / exponential_decay_length_penalty: padt_vrt_head_bias reads the session's bias vector and decay table
+    stop: bool = False               # stop_sequences / min_tokens / max_tokens: padt_stop_ban in front of the head, padt_stop_match behind the bookkeeping kernel
 
 
 @dataclass(frozen=True)
@@ -661,8 +804,17 @@ class GenOptions:
     logit_bias: InitVar[Optional[tuple]] = None
     decay: InitVar[Optional[tuple]] = None
     patch_bias: InitVar[bool] = False
+    # generate(stop_sequences=) in check_stop_sequences' normal form, generate(min_tokens=) when it is ONE value for the call, and "this batch
+    # carries per-row min_tokens / max_tokens" (the lists travel with their batch like the forced table).  Init-only attributes like those
+    # above — part of equality, hash and repr; spelled for a re-run by stop_kwargs().
+    stop_sequences: InitVar[Optional[tuple]] = None
+    min_tokens: InitVar[Optional[int]] = None
+    row_limits: InitVar[bool] = False
 
-    def __post_init__(self, forced, automaton, logit_bias, decay, patch_bias):
+    def __post_init__(self, forced, automaton, logit_bias, decay, patch_bias, stop_sequences, min_tokens, row_limits):
+        object.__setattr__(self, "stop_sequences", None if stop_sequences is None else tuple(tuple(int(i) for i in q) for q in stop_sequences))
+        object.__setattr__(self, "min_tokens", None if min_tokens is None else int(min_tokens))
+        object.__setattr__(self, "row_limits", bool(row_limits))
         object.__setattr__(self, "forced", bool(forced))
         object.__setattr__(self, "automaton", automaton)
         object.__setattr__(self, "logit_bias", logit_bias or None)
@@ -671,7 +823,8 @@ class GenOptions:
 
     def _key(self):
         # every field, whatever is added later, and the init-only attributes
-        return tuple(getattr(self, f.name) for f in fields(self)) + (self.forced, self.automaton, self.logit_bias, self.decay, self.patch_bias)
+        return tuple(getattr(self, f.name) for f in fields(self)) + (self.forced, self.automaton, self.logit_bias, self.decay, self.patch_bias,
+                                                                          self.stop_sequences, self.min_tokens, self.row_limits)
 
     def __eq__(self, other):
         return self._key() == other._key() if isinstance(other, GenOptions) else NotImplemented
@@ -686,6 +839,9 @@ class GenOptions:
         lb = self.logit_bias
         args += [f"logit_bias={lb!r}" if lb is None or len(lb) <= 8 else f"logit_bias=<{len(lb)} ids, #{hash(lb) & 0xffffffff:08x}>",
                  f"decay={self.decay!r}", f"patch_bias={self.patch_bias!r}"]
+        sq = self.stop_sequences
+        args += [f"stop_sequences={sq!r}" if sq is None or sum(len(q) for q in sq) <= 16 else f"stop_sequences=<{len(sq)} sequences, #{hash(sq) & 0xffffffff:08x}>",
+                 f"min_tokens={self.min_tokens!r}", f"row_limits={self.row_limits!r}"]
         return f"GenOptions({', '.join(args)})"
 
     @property
@@ -704,6 +860,12 @@ class GenOptions:
         return self.logit_bias is not None or self.decay is not None or self.patch_bias
 
     @property
+    def stop(self) -> bool:
+        """One of stop_sequences / min_tokens / max_tokens was given: the step runs padt_stop_ban and padt_stop_match, and the output
+        object carries finish_reason / stop_index / finish_step."""
+        return self.stop_sequences is not None or self.min_tokens is not None or self.row_limits
+
+    @property
     def reads_prompt(self) -> bool:
         """A ban or the repetition penalty is active: the built-in processors see the caller's full (B, L) input_ids."""
         return self.repetition_penalty != 1.0 or self.rules is not None
@@ -719,7 +881,7 @@ class GenOptions:
         return StepMode(sampling=self.sampling is not None, keep_scores=self.keep_scores, keep_logits=self.keep_logits, rules=self.rules is not None,
                         token_logprobs=self.token_logprobs, top_k=self.top_logprobs, patches=self.patch_logprobs, processors=bool(processors),
                         reference=bool(reference), warpers=self.sampling is not None and self.sampling.warpers, forced=self.forced,
-                        automaton=self.automaton is not None, bias=self.score_bias)
+                        automaton=self.automaton is not None, bias=self.score_bias, stop=self.stop)
 
     def warper_kwargs(self) -> dict:
         """min_p / typical_p / epsilon_cutoff / eta_cutoff as explicit generate() keywords (with_warpers values), next to generate_kwargs():
@@ -732,6 +894,12 @@ class GenOptions:
         Off is spelled as off ({} / (0, 1.0): no entry, a factor whose table is all 0), never None, so that no generation_config can switch
         the decay back on.  The patch_bias tensors travel with their batch."""
         return dict(logit_bias=dict(self.logit_bias or ()), exponential_decay_length_penalty=self.decay or DECAY_OFF)
+
+    def stop_kwargs(self) -> dict:
+        """stop_sequences / min_tokens as explicit generate() keywords, next to generate_kwargs(), warper_kwargs() and bias_kwargs().  No
+        generation_config carries either, so off is None.  Per-row min_tokens / max_tokens travel with their batch."""
+        sq = self.stop_sequences
+        return dict(stop_sequences=None if sq is None else [list(q) for q in sq], min_tokens=self.min_tokens)
 
     def generate_kwargs(self) -> dict:
         """Explicit generate() arguments that resolve back to these options under ANY generation_config: what is off is spelled as off (0, [],

@@ -9,7 +9,8 @@ Tokenisation / chat templating is the caller's (`prepare`): it needs the checkpo
 this repository.  `prepare(samples) -> dict(input_ids (local VRT ids), attention_mask, pixel_values, image_grid_thw,
 image_sizes [(w, h)], ids [image_id])`; optionally `image_index` (several samples on one image: generate(image_index=), with
 `pixel_values` / `image_grid_thw` holding each image once), `forced_tokens` (the batch's completion tokens to force:
-generate(forced_tokens=)) and `patch_bias` (one entry per sample over its own patches: generate(patch_bias=)).
+generate(forced_tokens=)), `patch_bias` (one entry per sample over its own patches: generate(patch_bias=)) and `min_tokens` / `max_tokens`
+(one int per sample: generate(min_tokens=, max_tokens=)).
 """
 import json
 import os
@@ -22,11 +23,14 @@ from .postprocess import postprocess_results
 def infer_dataset(model, processor, dataset: Sequence, prepare: Callable, output_dir: str, batch_size: int = 1,
                   datasetname: str = "coco", suffix: str = "", rank: int = 0, world: int = 1, max_new_tokens: int = 1024,
                   depth: int = 2, merge: int = 4, schedule=None, repetition_penalty=None, eos_token_id=None,
-                  token_automaton=None, logit_bias=None, exponential_decay_length_penalty=None):
+                  token_automaton=None, logit_bias=None, exponential_decay_length_penalty=None, stop_sequences=None, min_tokens=None,
+                  max_tokens=None):
     """repetition_penalty / eos_token_id: None = the checkpoint's generation_config.json (model.generation_config), as HF's
     generate() inside the reference's loop applies it (utils.py:230-236 → padt.py:436).
     token_automaton: generate(token_automaton=) for every batch of the run (e.g. the dataset's category names followed by their VRTs).
-    logit_bias / exponential_decay_length_penalty: generate()'s, for every batch of the run; a batch's own patch prior comes from `prepare`."""
+    logit_bias / exponential_decay_length_penalty: generate()'s, for every batch of the run; a batch's own patch prior comes from `prepare`.
+    stop_sequences / min_tokens / max_tokens: generate()'s, for every batch of the run (one value each; `prepare` may return per-row
+    `min_tokens` / `max_tokens` lists of its batch, which win)."""
     os.makedirs(output_dir, exist_ok=True)
     f_res = os.path.join(output_dir, f"{datasetname}_{rank}_pred_results_{suffix}.json")
     f_comp = os.path.join(output_dir, f"{datasetname}_{rank}_pred_comp_{suffix}.json")
@@ -58,10 +62,12 @@ def infer_dataset(model, processor, dataset: Sequence, prepare: Callable, output
         extra = {"image_index": b["image_index"]} if b.get("image_index") is not None else {}
         extra["forced_tokens"] = b.get("forced_tokens")           # None: nothing forced
         extra["patch_bias"] = b.get("patch_bias")                 # None: no prior over the patches
+        extra["min_tokens"] = b.get("min_tokens", min_tokens)     # the batch's own rows, else the run's value
+        extra["max_tokens"] = b.get("max_tokens", max_tokens)
         drain(runner.submit(b["input_ids"], b["attention_mask"], b["pixel_values"], b["image_grid_thw"],
                             max_new_tokens=max_new_tokens, schedule=schedule, repetition_penalty=repetition_penalty,
                             eos_token_id=eos_token_id, token_automaton=token_automaton, logit_bias=logit_bias,
-                            exponential_decay_length_penalty=exponential_decay_length_penalty, **extra))
+                            exponential_decay_length_penalty=exponential_decay_length_penalty, stop_sequences=stop_sequences, **extra))
         n += len(b["ids"])
     drain(runner.flush())
     return {"samples": n, "results_file": f_res, "completions_file": f_comp}

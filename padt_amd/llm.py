@@ -19,7 +19,7 @@ import torch
 
 from . import ops
 from .config import PaDTConfig
-from .generation import GenOptions, StepMode, decay_table
+from .generation import GenOptions, StepMode, decay_table, stop_table
 
 I32 = torch.int32
 
@@ -374,6 +374,11 @@ class DecodeSession:
         self.aban = None                 # ... and the bitmap padt_token_automaton writes for the head (with rules: its union with `ban`) [B][words]
         self.bias = None                 # mode.bias (generate(logit_bias=, patch_bias=)): fp32 [V + np_max] added to the raw logit of its column ...
         self.decay = None                # ... and exponential_decay_length_penalty's a[t] fp32 [t_max], read at the device step counter (generation.decay_table)
+        self.stab = None                 # mode.stop (generate(stop_sequences=, min_tokens=, max_tokens=)): the packed sequences, ops.STOP_RULES_INTS int32 (fixed size) ...
+        self.min_tok = self.max_tok = None       # ... each row's minimum and budget [B] ...
+        self.finish_step = self.finish_reason = self.stop_index = None      # ... what padt_stop_match records per row [B] (-1 / 0 / -1: no finish yet) ...
+        self.sban = None                 # ... the bitmap padt_stop_ban writes for the head (the rules' / the automaton's plus the EOS ids below min_tokens) [B][words] ...
+        self.summary_stop = self.summary_stop_host = None      # ... and generate_collect's read-back with the three finish arrays behind it
         self.rope_cs = z(B, hd // 2, 2, dt=torch.float32)
         self.n_qkv = (cfg.num_attention_heads + 2 * Hkv) * hd
         self.graphs = {}                 # captured decode-step graph per mode (different kernel sequences and output buffers)
@@ -479,6 +484,21 @@ class DecodeSession:
                 val = torch.tensor([v for _, v in opts.logit_bias], dtype=torch.float32)
                 self.bias.index_copy_(0, ids.to(dev), val.to(dev))
             self.decay.copy_(decay_table(opts.decay, self.t_max, n_steps).to(dev, non_blocking=True))
+        if opts.stop:                                            # rows no batch of the group fills: min 0 (or the call's one value), budget t_max
+            if self.stab is None:
+                self.stab = torch.zeros(ops.STOP_RULES_INTS, device=dev, dtype=I32)
+                self.min_tok, self.max_tok, self.finish_step, self.finish_reason, self.stop_index = (
+                    torch.zeros(self.B, device=dev, dtype=I32) for _ in range(5))
+                self.sban = torch.zeros_like(self.ban)
+                self.summary_stop = torch.zeros(2 + 6 * self.B, device=dev, dtype=I32)
+                host = torch.zeros(2 + 6 * self.B, dtype=I32)
+                self.summary_stop_host = host.pin_memory() if torch.device(dev).type == "cuda" else host
+            self.stab.copy_(stop_table(opts.stop_sequences).to(dev, non_blocking=True))
+            self.min_tok.fill_(opts.min_tokens or 0)
+            self.max_tok.fill_(self.t_max)
+            self.finish_step.fill_(-1)
+            self.finish_reason.zero_()
+            self.stop_index.fill_(-1)
         if opts.rules is not None:
             self.rules.copy_(ops.gen_rules_tensor(key=opts.rules).to(dev, non_blocking=True))
             self.hist_len.zero_()                                # rows no batch of the group fills: an empty prompt
@@ -503,6 +523,8 @@ class DecodeSession:
         if m.automaton:                                      # the columns the rows' automaton states allow; with rules the union of both bitmaps
             ban = ops.token_automaton(self.atab, self.gen_cfg, self.vrt_off, self.tokens, self.step, self.unfinished, self.astate, self.aban,
                                       cfg.vocab_size + self.np_max, cfg.vocab_size, rules_ban=ban)
+        if m.stop:                                           # min_tokens: the EOS ids of a row still below its minimum, on top of whatever is banned already
+            ban = ops.stop_ban(self.gen_cfg, cfg.eos_token_id, self.step, self.min_tok, self.sban, cfg.vocab_size + self.np_max, ban_in=ban)
         # forced tokens (generate(forced_tokens=)): the caller's table decides the token of a forced row.  Fused log-probs: the probe head leaves
         # the processed logit of the forced column next to the LSE partials; without log-probs the plain head runs and only the bookkeeping differs
         fc = self.forced if m.forced else None
@@ -570,6 +592,9 @@ class DecodeSession:
             ops.greedy_step(self.part_val, self.part_idx, nblk, hn, self.hidden_buf, self.unfinished, self.tokens,
                             self.cur_tok, self.step, self.slot, self.lens, self.pos3, cfg.eos_token_id, cfg.pad_token_id,
                             advance=advance, gen_cfg=self.gen_cfg, seen=self.seen, part_sum=psum, logprobs=lp_out)
+        if m.stop:                                           # the step counter is bumped: the rows hold *step tokens.  EOS, stop sequence, budget
+            ops.stop_match(self.stab, self.gen_cfg, cfg.eos_token_id, self.tokens, self.step, self.min_tok, self.max_tok, self.unfinished,
+                           self.finish_step, self.finish_reason, self.stop_index)
         if hk is not None:
             hk["t"] += 1
             if hk["criteria"]:
@@ -579,6 +604,12 @@ class DecodeSession:
                 stop = _call_hooks(hk["criteria"], hk["sequences"](), kept, chain=False)
                 if not isinstance(stop, torch.Tensor):       # criteria of the old API answer one bool for the whole batch
                     stop = torch.full((hk["B"],), bool(stop), device=hn.device)
+                if m.stop:                                   # a row the caller's criteria end: recorded here, reason "criteria" — padt_stop_match then leaves it alone
+                    nb = hk["B"]
+                    new = stop.to(device=hn.device, dtype=torch.bool) & (self.unfinished[:nb] != 0) & (self.finish_reason[:nb] == 0)
+                    self.finish_step[:nb].copy_(torch.where(new, torch.full_like(self.finish_step[:nb], hk["t"] - 1), self.finish_step[:nb]))
+                    self.finish_reason[:nb].copy_(torch.where(new, torch.full_like(self.finish_reason[:nb], ops.STOP_REASONS.index("criteria")),
+                                                              self.finish_reason[:nb]))
                 self.unfinished[: hk["B"]].mul_((~stop.to(device=hn.device, dtype=torch.bool)).to(self.unfinished.dtype))
 
     def run_steps(self, n: int, use_graph: bool = True):

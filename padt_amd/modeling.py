@@ -22,7 +22,7 @@ from . import _lib, ops
 from .config import PaDTConfig
 from .decoder import PaDTDecoder
 from .generation import (_GENERATE_CONFIG_NAMED, _GENERATE_CONFIG_OWN, check_decay_length_penalty, check_forced_tokens, check_generate_kwargs,  # noqa: F401
-                         check_logit_bias, check_patch_bias, check_token_automaton, check_top_logprobs, completion_logprobs, forced_tokens_active, generation_config_fields, resolve_options, with_warpers,
+                         check_logit_bias, check_max_tokens, check_min_tokens, check_patch_bias, check_stop_sequences, check_token_automaton, NO_BUDGET, check_top_logprobs, completion_logprobs, forced_tokens_active, generation_config_fields, resolve_options, with_warpers,
                          WARPER_NAMES)
 from .llm import MODE, LanguageModel, check_shared_destinations, plan_prompt, plan_prompt_shared
 from .vision import VisionEncoder
@@ -376,6 +376,25 @@ class PaDTForConditionalGeneration:
         the bias and the decay (HF's raw logits carry no processor).  A ``generation_config=`` that sets no decay leaves the checkpoint's
         ``exponential_decay_length_penalty`` in force, as for every other named field here (HF replaces the model's config wholesale);
         pass ``exponential_decay_length_penalty=(0, 1.0)`` to switch it off.
+        Keywords ``stop_sequences`` / ``min_tokens`` / ``max_tokens``: how a ROW ends, decided on the device inside the captured step
+        (generation.stop_ban_ids / stop_state are the specification; ``padt_stop_ban`` in front of the head, ``padt_stop_match`` behind the
+        bookkeeping kernel).  ``stop_sequences=[[id, ...], ...]``: up to 32 sequences of up to 32 TEXT ids (``NotImplementedError`` naming the
+        argument and the cap beyond, and for a VRT id; ``ValueError`` for an empty list or sequence); a row is finished by the step whose
+        token completes one of them within its GENERATED tokens — the prompt is never matched — and the sequence's tokens stay in the output,
+        as an EOS does.  ``min_tokens=n`` (an int, or one int per row): while a row has generated fewer than n tokens every id that would end
+        it (the config's EOS and the call's EOS list) scores ``-inf`` — exactly HF's ``MinNewTokensLengthLogitsProcessor(prompt_len, n,
+        eos_ids)``, seen by the arg-max, the sampler and its warpers, ``.scores``, the log-prob outputs and a caller's ``logits_processor``
+        — and a stop sequence that completes while the row holds fewer than n tokens is ignored, not matched retroactively later (vLLM's
+        rule); a forced EOS still wins, with log-prob ``-inf``; ``n < 0`` or n above the row's budget: ``ValueError``.  ``max_tokens`` (an int,
+        or one int per row, each in ``[1, max_new_tokens]``): row b is finished by its ``max_tokens[b]``-th token.  With one of the three the
+        output object also has ``finish_reason`` (a list of ``"eos"`` / ``"stop"`` / ``"length"``; ``"criteria"`` for a row the caller's
+        ``stopping_criteria`` ended on the hooked loop), ``stop_index`` (the matched sequence's place in the list, or -1) and ``finish_step``
+        (the index of the row's last token; -1, with reason ``"length"``, for a row still running when the call reached ``max_new_tokens``), and
+        ``sequences`` ends with the step in which the last row finished, whatever ``sync_every`` is.  Several conditions in one step: EOS, then
+        the stop sequence of the lowest index, then the budget.  Batches share a decode group only when ``stop_sequences`` and a one-value
+        ``min_tokens`` are equal and both or neither carry per-row lists (each batch writes its own rows of the session's minima and budgets);
+        one captured graph serves every value; without the three the call is what it was: same kernels, same step mode, same output
+        object.  They are NOT HF's ``min_new_tokens`` / ``min_length`` / ``stop_strings`` / ``max_time``, which stay refused by name.
         """
         if synced_gpus:
             raise NotImplementedError("generate(synced_gpus=True) is the ZeRO-3 / FSDP lock-step loop (padt.py:445,670): every rank holds a full "
@@ -386,6 +405,7 @@ class PaDTForConditionalGeneration:
         token_automaton = kwargs.pop("token_automaton", None)         # ... and the automaton that says which tokens may follow
         logit_bias, patch_bias = kwargs.pop("logit_bias", None), kwargs.pop("patch_bias", None)      # ... and the three additive score edits
         decay = kwargs.pop("exponential_decay_length_penalty", None)
+        stop_sequences, min_tokens, max_tokens = (kwargs.pop(k, None) for k in ("stop_sequences", "min_tokens", "max_tokens"))      # ... and how a row ends
         if generation_config is not None:
             named = dict(max_new_tokens=max_new_tokens, max_length=max_length, do_sample=do_sample, repetition_penalty=repetition_penalty,
                          eos_token_id=eos_token_id, pad_token_id=pad_token_id, temperature=temperature, top_k=top_k, top_p=top_p,
@@ -430,6 +450,8 @@ class PaDTForConditionalGeneration:
             hooks = dict(hooks or {}, automaton=token_automaton)
         if logit_bias is not None or patch_bias is not None or decay is not None:
             hooks = dict(hooks or {}, bias=dict(logit_bias=logit_bias, patch_bias=patch_bias, decay=decay))
+        if stop_sequences is not None or min_tokens is not None or max_tokens is not None:
+            hooks = dict(hooks or {}, stop=dict(stop_sequences=stop_sequences, min_tokens=min_tokens, max_tokens=max_tokens))
         if output_logits:
             pen = self.generation_config.repetition_penalty if repetition_penalty is None else repetition_penalty
             if float(pen) != 1.0 or schedule is not None or processors is not None:
@@ -477,6 +499,8 @@ class PaDTForConditionalGeneration:
         ``hooks=dict(bias=dict(logit_bias=..., patch_bias=..., decay=...))``: generate()'s ``logit_bias`` / ``patch_bias`` /
         ``exponential_decay_length_penalty`` (None entries: off, the decay then follows the generation config); the patch tensors are per-batch
         data, the other two part of the options.
+        ``hooks=dict(stop=dict(stop_sequences=..., min_tokens=..., max_tokens=...))``: generate()'s three arguments of that name (None
+        entries: off); the sequences and a one-value ``min_tokens`` are part of the options, per-row lists are per-batch data.
         """
         # a call's min_p / typical_p / epsilon_cutoff / eta_cutoff arrive as hooks["warpers"] (this method's parameter list is frozen) and are put
         # in front of the generation config's; what is left of `hooks` is the caller's processors / criteria, or nothing
@@ -501,6 +525,13 @@ class PaDTForConditionalGeneration:
             patch_bias = check_patch_bias(hb.get("patch_bias"), input_ids.shape[0])      # lengths once the batch's patch counts are known (_launch)
             decay = hb.get("decay") if hb.get("decay") is not None else decay
             hooks = {k: v for k, v in hooks.items() if k != "bias"} or None
+        stop_seqs = min_tok = max_tok = None
+        if hooks is not None and "stop" in hooks:
+            hs = hooks["stop"] or {}
+            stop_seqs = check_stop_sequences(hs.get("stop_sequences"), self.config.vocab_size)
+            max_tok = check_max_tokens(hs.get("max_tokens"), input_ids.shape[0], max_new_tokens)
+            min_tok = check_min_tokens(hs.get("min_tokens"), input_ids.shape[0], max_new_tokens, max_tok)
+            hooks = {k: v for k, v in hooks.items() if k != "stop"} or None
         decay = check_decay_length_penalty(decay, max_new_tokens)
         if decay is not None and decay[1] == 1.0:
             decay = None                                          # a[t] = 1 ** k - 1 = 0 at every step: the call without the argument
@@ -526,13 +557,19 @@ class PaDTForConditionalGeneration:
             if keep_logits and opts.sampling is None:
                 raise NotImplementedError("generate(output_logits=True) with a logits processor active (logit_bias, patch_bias or "
                                           "exponential_decay_length_penalty): only the processed rows are kept on this path — ask for output_scores=True")
+        stop = None
+        if stop_seqs is not None or min_tok is not None or max_tok is not None:
+            per_row = isinstance(min_tok, list)                   # one value for the call is part of the options; lists travel with the batch
+            opts = dataclasses.replace(opts, stop_sequences=stop_seqs, min_tokens=None if per_row else min_tok,
+                                       row_limits=per_row or max_tok is not None)
+            stop = dict(min_tokens=min_tok if per_row else None, max_tokens=max_tok)
         return owner._launch(opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, max_new_tokens=max_new_tokens,
                              schedule=schedule, hooks=hooks, sync_every=sync_every, use_graph=use_graph, lane=lane, decode_stream=decode_stream,
                              group=group, n_slots=n_slots, vit_stream=vit_stream, inputs_ready=inputs_ready, forced=forced, automaton=automaton,
-                             patch_bias=patch_bias)
+                             patch_bias=patch_bias, stop=stop)
 
     def _launch(self, opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, *, max_new_tokens, schedule, hooks, sync_every,
-                use_graph, lane, decode_stream, group, n_slots, vit_stream, inputs_ready, forced=None, automaton=None, patch_bias=None):
+                use_graph, lane, decode_stream, group, n_slots, vit_stream, inputs_ready, forced=None, automaton=None, patch_bias=None, stop=None):
         """generate_launch on the group's owner, with the call's options resolved (generation.GenOptions)."""
         self._batches_seen += 1
         if pixel_values is None or image_grid_thw is None:
@@ -669,6 +706,16 @@ class PaDTForConditionalGeneration:
             # this batch's rows of the session's table, in session numbering like the prompt history; the steps past n stay free (-1: begin())
             tab = torch.where(forced >= cfg.vocab_size, forced + proto_row0, forced) if proto_row0 else forced
             sess.forced[rows, : tab.shape[1]].copy_(tab.to(dev, non_blocking=True))
+        if opts.stop:
+            # this batch's rows of the session's minima and budgets (begin() set every row to the call's one minimum and to the budget of a
+            # row no batch fills): its own lists, or no budget at all — such a row ends on EOS, a stop sequence or the call's max_new_tokens
+            lim = stop or {}
+            if lim.get("min_tokens") is not None:
+                sess.min_tok[rows].copy_(torch.tensor(lim["min_tokens"], dtype=torch.int32).to(dev, non_blocking=True))
+            if lim.get("max_tokens") is not None:
+                sess.max_tok[rows].copy_(torch.tensor(lim["max_tokens"], dtype=torch.int32).to(dev, non_blocking=True))
+            else:
+                sess.max_tok[rows].fill_(NO_BUDGET)
         if patch_bias is not None:
             # this batch's segment of the session's bias vector: its own prototype rows (begin() zero-filled the vector; a row without an entry adds 0)
             seg = torch.zeros(n_proto, dtype=torch.float32)
@@ -688,7 +735,7 @@ class PaDTForConditionalGeneration:
             ops.gather_rows(hn_all, plan.last_idx, out=sess.hn_first[rows])
         group["subs"].append(dict(plan=plan, low=low, high=high, pe=pe, proto=proto, hn_all=hn_all, input_ids=input_ids,
                                   n_proto=n_proto, row0=row0, proto_row0=proto_row0, nf=nf, p_max=p_max, forced=forced, automaton=automaton,
-                                  patch_bias=patch_bias,
+                                  patch_bias=patch_bias, stop=stop,
                                   inputs=(attention_mask, pixel_values, image_grid_thw, image_index)))       # what a re-run on the bf16 twin needs
         group["proto_rows"] = proto_row0 + n_proto
         if len(group["subs"]) == group["n_slots"]:
@@ -745,6 +792,12 @@ class PaDTForConditionalGeneration:
         n_rows, n_sub = sess.B, len(group["subs"])
 
         def summary(done):
+            if opts.stop:                                         # the same launch and copy, with the rows' finish records behind the record
+                ops.collect_summary_stop(sess.err, sess.unfinished, sess.nf, sess.nf_batch, n_sub, sess.tokens, done, cfg.eos_token_id, sess.gen_cfg,
+                                         sess.finish_step, sess.finish_reason, sess.stop_index, sess.summary_stop)
+                sess.summary_stop_host.copy_(sess.summary_stop, non_blocking=True)
+                torch.cuda.current_stream().synchronize()
+                return sess.summary_stop_host.tolist()
             ops.collect_summary(sess.err, sess.unfinished, sess.nf, sess.nf_batch, n_sub, sess.tokens, done, cfg.eos_token_id, sess.gen_cfg, sess.summary)
             sess.summary_host.copy_(sess.summary, non_blocking=True)
             torch.cuda.current_stream().synchronize()
@@ -761,6 +814,9 @@ class PaDTForConditionalGeneration:
             raise AssertionError("input_ids.max() >= extended table rows (padt.py:203)")
         nf_rows, nf_batch = flags[2: 2 + n_rows], flags[2 + n_rows: 2 + n_rows + n_sub]
         first_eos = flags[2 + n_rows + n_sub: 2 + 2 * n_rows + n_sub]
+        if opts.stop:                                             # a row's end is what padt_stop_match (or the hooked loop) recorded, whatever ended it
+            o = 2 + 2 * n_rows + n_sub
+            fin_step, fin_reason, fin_index = flags[o: o + n_rows], flags[o + n_rows: o + 2 * n_rows], flags[o + 2 * n_rows: o + 3 * n_rows]
         outs = []
         for k_sub, sub in enumerate(group["subs"]):
             plan, row0, B = sub["plan"], sub["row0"], group["B"]
@@ -768,7 +824,7 @@ class PaDTForConditionalGeneration:
                 outs.append(self._non_finite_batch(group, sub, output_hidden_states, return_dict_in_generate, output_scores, output_logits))
                 continue
             # the reference stops right after the step in which the last sequence finished (padt.py:756-757); any id of the EOS list finishes a row
-            fe = first_eos[row0: row0 + B]
+            fe = fin_step[row0: row0 + B] if opts.stop else first_eos[row0: row0 + B]
             n_steps = max(fe) + 1 if all(f >= 0 for f in fe) else done_steps
             # [input_ids | tokens] with the group's session-global VRT ids shifted back to this batch's own (one launch, padt.py:751)
             sequences = ops.assemble_sequences(sub["input_ids"].to(dev), sess.tokens[row0: row0 + B], n_steps, cfg.vocab_size, sub["proto_row0"])
@@ -802,6 +858,11 @@ class PaDTForConditionalGeneration:
                 past_image_embeds=sub["proto"].clone(),
                 past_logit_mask=ops.logit_mask(sess.vrt_off[row0: row0 + B + 1], cfg.vocab_size, table_rows, sub["proto_row0"], B),
                 past_high_res_image_embeds=sub["high"], past_visual_pe=sub["pe"])
+            if opts.stop:                                         # a row still running at the call's end: -1, "length"
+                out["finish_step"] = [int(f) for f in fe]
+                out["finish_reason"] = [ops.STOP_REASONS[r] if f >= 0 and 0 < r < len(ops.STOP_REASONS) else "length"
+                                        for f, r in zip(fe, fin_reason[row0: row0 + B])]
+                out["stop_index"] = [int(i) if f >= 0 else -1 for f, i in zip(fe, fin_index[row0: row0 + B])]
             outs.append(out if return_dict_in_generate else sequences)
         return outs if all_batches else outs[0]
 
@@ -826,8 +887,10 @@ class PaDTForConditionalGeneration:
                           "instantiation" % (self.overflow_reruns, self._batches_seen), RuntimeWarning, stacklevel=3)
         am, pix, grid, image_index = sub["inputs"]
         # the group's options spelled as explicit arguments (an "off" is 0 / [], never the default), and what this collect was asked to return
-        kw = dict(group["opts"].generate_kwargs(), **group["opts"].warper_kwargs(), **group["opts"].bias_kwargs(), output_scores=output_scores,
-                  output_logits=output_logits)
+        kw = dict(group["opts"].generate_kwargs(), **group["opts"].warper_kwargs(), **group["opts"].bias_kwargs(), **group["opts"].stop_kwargs(),
+                  output_scores=output_scores, output_logits=output_logits)
+        if sub.get("stop") is not None:                           # the batch's own per-row lists: the options only say that there are some
+            kw.update({k: v for k, v in sub["stop"].items() if v is not None})
         if group.get("hooks") is not None:
             kw.update(logits_processor=group["hooks"]["processors"], stopping_criteria=group["hooks"]["criteria"])
         if sub.get("forced") is not None:
@@ -848,7 +911,9 @@ class PaDTForConditionalGeneration:
         sums.  completions: what ``forced_tokens`` takes.  Several candidates for one image: repeat the prompt rows and pass ``image_index``.
         ``token_automaton=A`` (default ``None``; one of ``**generate_kwargs``, handed to generate(token_automaton=)): every step's row is constrained to the columns A allows after the forced prefix,
         so ``token_logprobs`` is the log-softmax over the ALLOWED columns — the closed-set probability: over the labels of a trie the
-        probabilities of the first branching step sum to 1.  A completion that leaves the automaton scores ``-inf`` at that token."""
+        probabilities of the first branching step sum to 1.  A completion that leaves the automaton scores ``-inf`` at that token.
+        ``max_tokens=[len(c) for c in completions]`` (one of ``**generate_kwargs``, generate(max_tokens=)) ends every row with its own
+        completion instead of letting the short ones run free to the table's width; it is not passed by default."""
         for k in ("forced_tokens", "max_new_tokens", "output_token_logprobs", "return_dict_in_generate"):
             if k in generate_kwargs:
                 raise ValueError(f"score_completions sets generate({k}=...) itself")

@@ -1132,6 +1132,59 @@ def collect_summary(err, unfinished, nf_rows, nf_batch, n_batch, tokens, done, e
     return out
 
 
+STOP_RULES_MAGIC = 0x53523031
+STOP_RULES_MAX_SEQS = 32        # the packed stop sequences' caps: a session's copy has a fixed size, so it never moves (captured graphs read it)
+STOP_RULES_MAX_LEN = 32
+STOP_RULES_INTS = 2 + STOP_RULES_MAX_SEQS + STOP_RULES_MAX_SEQS * STOP_RULES_MAX_LEN
+STOP_REASONS = (None, "eos", "stop", "length", "criteria")      # finish_reason codes; "criteria" is written by the hooked loop alone
+
+
+def _chk_i32(*ts, n=0):
+    for t in ts:
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() >= n
+
+
+def stop_ban(gen_cfg, eos, step, min_tokens, ban_out, n_cols, ban_in=None):
+    """ban_out[b] = ban_in[b] (None: zeros) plus, while *step < min_tokens[b], the bits of `eos` and gen_cfg's EOS list (padt_stop_ban):
+    generate(min_tokens=) as the ban bitmap the head reads.  min_tokens int32 (B,), ban_out / ban_in int32 (>= B, words), two buffers.  → ban_out."""
+    B = min_tokens.numel()
+    _chk_i32(step, min_tokens, ban_out)
+    assert gen_cfg.is_cuda and gen_cfg.is_contiguous() and gen_cfg.numel() * gen_cfg.element_size() >= 20
+    assert ban_out.dim() == 2 and ban_out.shape[0] >= B and 0 < int(n_cols) <= 32 * ban_out.shape[1]
+    if ban_in is not None:
+        _chk_i32(ban_in)
+        assert ban_in.dim() == 2 and ban_in.shape[0] >= B and ban_in.shape[1] == ban_out.shape[1] and ban_in.data_ptr() != ban_out.data_ptr()
+    _lib.check(_lib.load().padt_stop_ban(_stream(), _p(gen_cfg), int(eos), _p(step), _p(min_tokens), _p(ban_in), _p(ban_out), ban_out.shape[1],
+                                         int(n_cols), B), "padt_stop_ban")
+    return ban_out
+
+
+def stop_match(table, gen_cfg, eos, tokens, step, min_tokens, max_tokens, unfinished, finish_step, finish_reason, stop_index):
+    """After greedy_step / forced_step: every row b of finish_reason without a recorded finish is tested for an EOS id, a completed stop
+    sequence (the lowest index; only once the row holds min_tokens[b] tokens) and its budget max_tokens[b], in this order; a finish clears
+    unfinished[b] and writes finish_step / finish_reason / stop_index (padt_stop_match).  table: the device copy of generation.stop_table."""
+    B = finish_reason.numel()
+    _chk_i32(step, n=1)
+    _chk_i32(min_tokens, max_tokens, unfinished, finish_step, finish_reason, stop_index, n=B)
+    _chk_i32(table, n=STOP_RULES_INTS)
+    assert gen_cfg.is_cuda and gen_cfg.is_contiguous() and gen_cfg.numel() * gen_cfg.element_size() >= 20
+    assert tokens.dtype == torch.int64 and tokens.is_cuda and tokens.dim() == 2 and tokens.stride(1) == 1 and tokens.shape[0] >= B
+    _lib.check(_lib.load().padt_stop_match(_stream(), _p(table), table.numel(), _p(gen_cfg), int(eos), _p(tokens), tokens.stride(0), _p(step),
+                                           _p(min_tokens), _p(max_tokens), _p(unfinished), _p(finish_step), _p(finish_reason), _p(stop_index), B),
+               "padt_stop_match")
+
+
+def collect_summary_stop(err, unfinished, nf_rows, nf_batch, n_batch, tokens, done, eos, gen_cfg, finish_step, finish_reason, stop_index, out):
+    """collect_summary's record, then finish_step, finish_reason and stop_index of every row (padt_collect_summary_stop): one launch."""
+    n_rows = unfinished.numel()
+    assert out.dtype == torch.int32 and out.numel() >= 2 + 5 * n_rows + n_batch and tokens.dtype == torch.int64 and tokens.is_contiguous()
+    _chk_i32(finish_step, finish_reason, stop_index, n=n_rows)
+    _lib.check(_lib.load().padt_collect_summary_stop(_stream(), _p(err), _p(unfinished), _p(nf_rows), _p(nf_batch), n_rows, int(n_batch),
+                                                     _p(tokens), tokens.shape[1], int(done), int(eos), _p(gen_cfg), _p(finish_step),
+                                                     _p(finish_reason), _p(stop_index), _p(out)), "padt_collect_summary_stop")
+    return out
+
+
 def assemble_sequences(input_ids, tokens, n_steps, vocab, proto_row0):
     """→ (B, L + n_steps) int64: [input_ids | tokens[:, :n_steps]] with session-global VRT ids shifted back by proto_row0 (padt.py:751)."""
     assert input_ids.dtype == torch.int64 and input_ids.stride(1) == 1 and tokens.dtype == torch.int64 and tokens.stride(1) == 1

@@ -21,7 +21,7 @@ def sample_grids(image_grid_thw, image_index):
 def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens=1024,
               schedule: Optional[Sequence] = None, need_thinking_mask=None, image_index=None, do_sample=False, min_p=None, typical_p=None,
               epsilon_cutoff=None, eta_cutoff=None, forced_tokens=None, token_automaton=None, logit_bias=None, patch_bias=None,
-              exponential_decay_length_penalty=None, **gen_kw):
+              exponential_decay_length_penalty=None, stop_sequences=None, min_tokens=None, max_tokens=None, **gen_kw):
     """→ (decoded dict of vl_decode, completions, labels, vrts).  ``input_ids`` carries LOCAL VRT ids (as a processor
     emits them) and is updated in place exactly like the reference's callers do.
     ``image_index``: sample b asks about image image_index[b] of the N <= B images given (generate(image_index=)); everything per sample
@@ -31,7 +31,9 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
     ``forced_tokens``: generate(forced_tokens=) — GLOBAL ids, numbered like the generated part of ``sequences``.
     ``token_automaton``: generate(token_automaton=) — a generation.TokenAutomaton constraining what may be generated.
     ``logit_bias`` / ``patch_bias`` / ``exponential_decay_length_penalty``: generate()'s additive score edits (text ids; one entry per
-    sample over its own patches; (start, factor))."""
+    sample over its own patches; (start, factor)).
+    ``stop_sequences`` / ``min_tokens`` / ``max_tokens``: generate()'s — how a row ends; the decoded dict then carries ``finish_reason`` /
+    ``stop_index`` / ``finish_step``."""
     B = input_ids.shape[0]
     grid_in = image_grid_thw
     if image_index is not None:
@@ -42,7 +44,8 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
                          image_grid_thw=grid_in, use_cache=True, max_new_tokens=max_new_tokens, do_sample=do_sample,
                          output_hidden_states=True, return_dict_in_generate=True, schedule=schedule, min_p=min_p, typical_p=typical_p,
                          epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, forced_tokens=forced_tokens, token_automaton=token_automaton,
-                         logit_bias=logit_bias, patch_bias=patch_bias, exponential_decay_length_penalty=exponential_decay_length_penalty, **gen_kw)
+                         logit_bias=logit_bias, patch_bias=patch_bias, exponential_decay_length_penalty=exponential_decay_length_penalty,
+                         stop_sequences=stop_sequences, min_tokens=min_tokens, max_tokens=max_tokens, **gen_kw)
     L = input_ids.shape[1]
     seq_local = processor.assign_to_local_vrt_id(out["sequences"].cpu(), image_grid_thw.cpu())
     completion_ids = seq_local[:, L:]
@@ -53,6 +56,9 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
         decoded["token_logprobs"] = out.token_logprobs
     for name in ("top_token_ids", "top_logprobs", "patch_logprobs"):      # generate(top_logprobs=k, output_patch_logprobs=True), likewise
         if out[name] is not None:
+            decoded[name] = out[name]
+    for name in ("finish_reason", "stop_index", "finish_step"):           # generate(stop_sequences=, min_tokens=, max_tokens=)
+        if name in out:
             decoded[name] = out[name]
     return decoded, completions, labels, vrts
 
@@ -111,7 +117,7 @@ class PipelinedRunner:
                need_thinking_mask=None, sync_every=None, repetition_penalty=None, eos_token_id=None, no_repeat_ngram_size=None,
                bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None, do_sample=False, min_p=None,
                typical_p=None, epsilon_cutoff=None, eta_cutoff=None, forced_tokens=None, token_automaton=None, logit_bias=None, patch_bias=None,
-               exponential_decay_length_penalty=None, **sampling):
+               exponential_decay_length_penalty=None, stop_sequences=None, min_tokens=None, max_tokens=None, **sampling):
         """image_index: see generate(); the batch's results are those of the expanded batch.
         do_sample (default: greedy) with min_p / typical_p / epsilon_cutoff / eta_cutoff and, through **sampling, temperature / top_k / top_p /
         seed: see generate(); batches whose resolved options differ in any of them (the seed included) do not share a decode group.
@@ -120,7 +126,10 @@ class PipelinedRunner:
         forced_tokens: generate(forced_tokens=), each batch its own table; a batch that forces and one that does not never share a group.
         token_automaton: generate(token_automaton=); batches share a decode group only when their automata are equal.
         logit_bias / patch_bias / exponential_decay_length_penalty: generate()'s additive score edits; batches share a decode group only
-        when logit_bias and the decay are equal and both or neither carry a patch_bias (each batch its own tensors)."""
+        when logit_bias and the decay are equal and both or neither carry a patch_bias (each batch its own tensors).
+        stop_sequences / min_tokens / max_tokens: generate()'s — how a row ends; the decoded dict then carries "finish_reason" / "stop_index" /
+        "finish_step".  Batches share a decode group only when stop_sequences and a one-value min_tokens are equal and both or neither carry
+        per-row lists (each batch its own min_tokens / max_tokens rows)."""
         done = []
         bid = self.n_batches
         self.n_batches += 1
@@ -137,6 +146,8 @@ class PipelinedRunner:
             hooks["automaton"] = token_automaton
         if logit_bias is not None or patch_bias is not None or exponential_decay_length_penalty is not None:
             hooks["bias"] = dict(logit_bias=logit_bias, patch_bias=patch_bias, decay=exponential_decay_length_penalty)
+        if stop_sequences is not None or min_tokens is not None or max_tokens is not None:
+            hooks["stop"] = dict(stop_sequences=stop_sequences, min_tokens=min_tokens, max_tokens=max_tokens)
         for attempt in range(2):
             if self.cur is None:
                 while len(self.pending) > self.depth - 1:         # the lane about to be reused must have been collected
@@ -202,6 +213,9 @@ class PipelinedRunner:
                     decoded["token_logprobs"] = out.token_logprobs
                 for name in ("top_token_ids", "top_logprobs", "patch_logprobs"):      # submit(top_logprobs=k, output_patch_logprobs=True)
                     if out[name] is not None:
+                        decoded[name] = out[name]
+                for name in ("finish_reason", "stop_index", "finish_step"):           # submit(stop_sequences=, min_tokens=, max_tokens=)
+                    if name in out:
                         decoded[name] = out[name]
                 res.append((decoded, completions, labels, vrts))
         self.decode_streams[lane].synchronize()
