@@ -385,6 +385,20 @@ int  padt_vrt_head_bias(void* stream, const void* hidden, long ldh, const void* 
                         const void* embed_table_packed, const void* gen_cfg, const void* seen, long seen_words,
                         const void* ban, long ban_words, void* part_sum, const int* forced, long t_forced, void* probe_val,
                         const void* bias, const void* decay, long t_decay);
+/* generate(frequency_penalty=, presence_penalty=, patch_suppression=): padt_vrt_head_bias (bias and decay stay nullable) with the edits that
+ * grow with what a row has generated, read from the tables padt_count_update keeps.  After the repetition penalty and before the logit mask /
+ * mode table / ban bitmap, for column c of sample b with count n (cnt_text[b][c] for a text column, cnt_patch[c - vocab] for a patch column):
+ *   s = s - f[b] * n;  s = s - p[b] * (n > 0)          vLLM's apply_penalties: two products, two differences, each rounded on its own
+ *   a patch column with near[c - vocab] > 0 and pen[b] > 0:  s = s - near * pen[b]          pen = +inf: -inf, a ban
+ * cnt_text: uint16 [batch][ld_cnt], ld_cnt >= vocab, ld_cnt % 4 == 0, 8-byte aligned; cnt_patch, near: uint16 [n_proto]; cpen: fp32 [3][batch] =
+ * f, p, pen (0: no suppression).  All four are required.  The head is chosen by the nullable outputs as in padt_vrt_head_bias. */
+int  padt_vrt_head_counts(void* stream, const void* hidden, long ldh, const void* embed_table, long vocab, const void* proto,
+                          long n_proto, const int* vrt_off, const int* mode_table, const int* step, void* logits_f32,
+                          long ld_logits, void* part_val, void* part_idx, long batch, long D, int eos,
+                          const void* embed_table_packed, const void* gen_cfg, const void* seen, long seen_words,
+                          const void* ban, long ban_words, void* part_sum, const int* forced, long t_forced, void* probe_val,
+                          const void* bias, const void* decay, long t_decay, const void* cnt_text, long ld_cnt, const void* cnt_patch,
+                          const void* near, const void* cpen);
 /* padt_greedy_step(_lp) with the forced table: after the arg-max (and the LSE fold) an unfinished row with a forced entry in [0, n_cols) takes
  * it as its token — appended, fed to the next step, entered in `seen`, an EOS id finishes the row — even where its score is -inf (the
  * no-candidate → pad branch applies to free rows only).  part_sum / logprobs / probe_val: all three (then logprobs[b][*step] =
@@ -519,6 +533,17 @@ int  padt_stop_match(void* stream, const int* table, long table_ints, const void
 int  padt_collect_summary_stop(void* stream, const int* err, const int* unfinished, const int* nf_rows, const int* nf_batch, long n_rows,
                                long n_batch, const long* tokens, long t_max, long done, int eos, const void* gen_cfg,
                                const int* finish_step, const int* finish_reason, const int* stop_index, int* out);
+/* generate(frequency_penalty=, presence_penalty=, patch_suppression=) (count_penalties.hip): the counts padt_vrt_head_counts reads, kept
+ * inside the decode step.  After padt_greedy_step / padt_forced_step and in front of padt_stop_match: with n = *step tokens in row b and
+ * tok = tokens[b][n - 1], for every row with unfinished[b] != 0 (a row finished in this step or earlier writes nothing):
+ *   tok a text id: cnt_text[b][tok] += 1;  tok - vocab in [vrt_off[b], vrt_off[b + 1]): cnt_patch[tok - vocab] += 1
+ *   tok not a VRT id, tokens[b][n - 2] a VRT id, 0 <= radius[b] <= 7: for every own-patch token (y, x) of the VRT run ending at n - 2, near[] += 1
+ *   on the window max(|dy|, |dx|) <= radius[b] of the row-major grid (hp, wp) = grid[b][0..1], clipped at its border (hp * wp must be the
+ *   row's patch count, else nothing is written to near).  radius[b] < 0: no suppression for the row.
+ * uint16 tables that saturate at 65535; nothing is written unless 1 <= n <= ld_tokens. */
+int  padt_count_update(void* stream, const long* tokens, long ld_tokens, const int* step, const int* unfinished, const int* vrt_off,
+                       const int* grid, const int* radius, void* cnt_text, long ld_cnt, long vocab, void* cnt_patch, void* near,
+                       long n_proto, long batch);
 
 /* ---- caller-side post-processing --------------------------------------------------------------- */
 /* out[o][y][x] = sigmoid(bilinear(masks[o][:src_h[o]][:src_w[o]] → dst_h[o] x dst_w[o], align_corners=False))[y][x] > 0.5,

@@ -542,6 +542,168 @@ def score_bias_row(logits, bias=None, penalty=1.0, seen=None, banned=None, eos_i
     return x
 
 
+# ------------------------------------------------------------------------------------------------ generate(frequency_penalty=, presence_penalty=, patch_suppression=)
+# The edits that GROW with what a row has already generated.  The specification (count_state / count_penalty_row below are its plain
+# statement; padt_count_update and the COUNTS head kernels, padt_vrt_head_counts, are compared against them bit for bit), for row b at step t:
+#   * count[c]: how often table column c — a text id or one of the row's own VRT columns — occurs among the row's GENERATED tokens 0 .. t - 1.
+#     The prompt is never counted (vLLM's rule for these two penalties, unlike the repetition penalty's `seen`), forced tokens are, the pad
+#     tokens behind a row's end are not.
+#   * near[j]: over the VRT tokens of the row's COMPLETED runs — maximal runs of consecutive VRT tokens followed by a non-VRT token; a run
+#     still open at step t suppresses nothing, so an object's own VRT tokens may sit next to each other — the number whose patch (y, x) on
+#     the row-major merged grid (h/2, w/2) lies within max(|y - y_j|, |x - x_j|) <= radius of patch j.
+#   * the edit, between the repetition penalty and the mask / schedule / ban filter (the order: bias, repetition penalty, token counts, patch
+#     neighbourhood, bans, EOS decay), all in fp32: s = s - f * count; s = s - p * (count > 0) — vLLM's apply_penalties, two products and two
+#     differences each rounded on its own — then, where near > 0: s = s - near * penalty (+inf: -inf, a ban; near == 0 is no operation, so
+#     there is no 0 * inf).
+# The device keeps the state of the tokens it selected FROM: the step whose token ends a row with an EOS id is not counted (nothing is selected
+# after it, so no output can tell) — count_state(tokens, n) with n the tokens before that one is what the tables then hold.
+COUNT_MAX_RADIUS = ops.COUNT_MAX_RADIUS
+
+
+def _row_floats(name, value, B, lo, hi):
+    """a float in [lo, hi], or one per row → list of B floats (rounded to fp32: what the device reads); None for None"""
+    if value is None:
+        return None
+    if isinstance(value, torch.Tensor):
+        if value.dtype == torch.bool or value.dtype.is_complex or value.dim() > 1:
+            raise ValueError(f"generate({name}=...): a number or one number per row is required, got a {value.dtype} tensor of shape {tuple(value.shape)}")
+        value = value.item() if value.dim() == 0 else value.tolist()
+    if isinstance(value, numbers.Real) and not isinstance(value, bool):
+        vals = [value] * int(B)
+    else:
+        if isinstance(value, (str, bytes)):
+            raise ValueError(f"generate({name}=...): a number or one number per row is required, got {value!r}")
+        try:
+            vals = list(value)
+        except TypeError:
+            raise ValueError(f"generate({name}=...): a number or one number per row is required, got {value!r}") from None
+        if len(vals) != int(B):
+            raise ValueError(f"generate({name}=...): {len(vals)} entries for a batch of {int(B)} samples")
+    out = []
+    for b, v in enumerate(vals):
+        if isinstance(v, torch.Tensor) and v.numel() == 1:
+            v = v.item()
+        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+            raise ValueError(f"generate({name}=...): row {b}: a real number is required, got {v!r}")
+        v = float(v)
+        if not math.isfinite(v) or not lo <= v <= hi:
+            raise ValueError(f"generate({name}=...): row {b}: {v!r} is not a finite number in [{lo:g}, {hi:g}] (vLLM's rule)")
+        out.append(float(torch.tensor(v, dtype=torch.float32)))
+    return out
+
+
+def check_count_penalties(frequency_penalty, presence_penalty, B):
+    """generate(frequency_penalty=, presence_penalty=) → (f, p): two lists of B fp32-rounded floats, or (None, None) when both are off (None, 0
+    or all zeros: the call without the arguments).  Each argument is a float or a sequence of B floats, finite and within [-2, 2]; anything
+    else raises ValueError naming the argument."""
+    f = _row_floats("frequency_penalty", frequency_penalty, B, -2.0, 2.0)
+    p = _row_floats("presence_penalty", presence_penalty, B, -2.0, 2.0)
+    if not any(f or ()) and not any(p or ()):
+        return None, None
+    return f or [0.0] * int(B), p or [0.0] * int(B)
+
+
+def check_patch_suppression(patch_suppression, B):
+    """generate(patch_suppression=) → a list of B entries, each None (the row is not suppressed) or (int radius, float penalty); None for None
+    or a list of Nones.  One (radius, penalty) pair applies to every row.  radius: an integer in [0, COUNT_MAX_RADIUS] — above the cap
+    NotImplementedError naming it, negative or not an integer ValueError; penalty: > 0, finite or +inf (a ban) — zero, negative or NaN
+    ValueError.  All name the argument."""
+    name = "generate(patch_suppression=...)"
+    if patch_suppression is None:
+        return None
+
+    def pair(e, where):
+        try:
+            radius, penalty = e
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: a (radius, penalty) pair is required, got {e!r}{where}") from None
+        if isinstance(radius, torch.Tensor) and radius.numel() == 1 and not (radius.dtype.is_floating_point or radius.dtype == torch.bool):
+            radius = int(radius)
+        if isinstance(radius, bool) or not isinstance(radius, numbers.Integral) or int(radius) < 0:
+            raise ValueError(f"{name}: radius must be an integer >= 0, got {radius!r}{where}")
+        if int(radius) > COUNT_MAX_RADIUS:
+            raise NotImplementedError(f"{name}: radius {int(radius)}{where}; at most {COUNT_MAX_RADIUS} on the MI355X path")
+        if isinstance(penalty, torch.Tensor) and penalty.numel() == 1:
+            penalty = penalty.item()
+        if isinstance(penalty, bool) or not isinstance(penalty, numbers.Real) or not float(penalty) > 0.0:
+            raise ValueError(f"{name}: penalty must be a number > 0 (+inf bans), got {penalty!r}{where}")
+        pen = float(torch.tensor(float(penalty), dtype=torch.float32))
+        if pen == math.inf and float(penalty) != math.inf or pen == 0.0:
+            raise ValueError(f"{name}: penalty {penalty!r} is not an fp32 value > 0{where}")
+        return int(radius), pen
+
+    # one pair for the call: two scalars, the first an integer (a tuple, or a list as a dict config spells it) — never a list of two rows
+    ps = patch_suppression
+    if (isinstance(ps, (tuple, list)) and len(ps) == 2 and isinstance(ps[0], numbers.Integral) and not isinstance(ps[0], bool)
+            and isinstance(ps[1], numbers.Real)):
+        return [pair(ps, "")] * int(B)
+    if isinstance(ps, (str, bytes, numbers.Number, torch.Tensor)):
+        raise ValueError(f"{name}: a (radius, penalty) pair or a list of per-row pairs / Nones is required, got {ps!r}")
+    try:
+        rows = list(ps)
+    except TypeError:
+        raise ValueError(f"{name}: a (radius, penalty) pair or a list of per-row pairs / Nones is required, got {ps!r}") from None
+    if len(rows) != int(B):
+        raise ValueError(f"{name}: {len(rows)} entries for a batch of {int(B)} samples")
+    out = [None if r is None else pair(r, f" (row {b})") for b, r in enumerate(rows)]
+    return out if any(r is not None for r in out) else None
+
+
+def count_state(tokens, n, vocab, lo, hi, grid=None, radius=None):
+    """The counts of a row after its first n generated tokens, by a plain walk → (count, near): count — a dict {table column: occurrences}
+    over text ids and the row's own VRT columns vocab + lo .. vocab + hi - 1 (a VRT id outside that range counts nowhere, but is a VRT token
+    of its run); near — a list of hi - lo ints over the row's patches, row-major on grid = (hp, wp): for every VRT token of a COMPLETED run
+    (followed by a non-VRT token within the n tokens) on one of the row's own patches (y, x), + 1 on the window max(|dy|, |dx|) <= radius
+    clipped at the grid's border.  radius None (or grid None): no suppression, near is all 0.  The caller chooses n: tokens behind a row's
+    end are not generated tokens and must not be passed as such."""
+    vocab, lo, hi = int(vocab), int(lo), int(hi)
+    row = [int(x) for x in tokens[: int(n)]]
+    count = {}
+    near = [0] * (hi - lo)
+    if radius is not None and grid is not None:
+        hp, wp = int(grid[0]), int(grid[1])
+        if hp * wp != hi - lo:
+            raise ValueError(f"count_state: a {hp} x {wp} grid for {hi - lo} patches")
+    run = []
+    for tok in row:
+        is_vrt = tok >= vocab
+        own = is_vrt and lo <= tok - vocab < hi
+        if (0 <= tok < vocab) or own:
+            count[tok] = count.get(tok, 0) + 1
+        if is_vrt:
+            if own:
+                run.append(tok - vocab - lo)
+            continue
+        if radius is not None and grid is not None:                   # a non-VRT token: the run before it, if any, is complete
+            for j in run:
+                y, x = divmod(j, wp)
+                for yy in range(max(0, y - int(radius)), min(hp, y + int(radius) + 1)):
+                    for xx in range(max(0, x - int(radius)), min(wp, x + int(radius) + 1)):
+                        near[yy * wp + xx] += 1
+        run = []
+    return count, near
+
+
+def count_penalty_row(logits, counts=None, frequency_penalty=0.0, presence_penalty=0.0, near=None, suppression_penalty=0.0, bias=None,
+                      penalty=1.0, seen=None, banned=None, eos_ids=(), a_t=0.0):
+    """score_bias_row with the count edits in their place — bias, repetition penalty, TOKEN COUNTS, PATCH NEIGHBOURHOOD, bans, EOS decay — on
+    fp32 rows (..., n): counts / near — integer or float (..., n) tensors over the row's columns (near is 0 on text columns), None = all 0
+    and no edit; frequency_penalty / presence_penalty / suppression_penalty — numbers, or (..., 1) tensors for per-row values.  Plain torch,
+    one rounding per operation: x -= f * counts; x -= p * (counts > 0); where near > 0 (and the penalty > 0): x -= near * penalty."""
+    x = score_bias_row(logits, bias=bias, penalty=penalty, seen=seen)
+    as_t = lambda v: v.to(device=x.device, dtype=torch.float32) if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=torch.float32, device=x.device)
+    if counts is not None:
+        c = counts.to(device=x.device, dtype=torch.float32)
+        x = x - as_t(frequency_penalty) * c
+        x = x - as_t(presence_penalty) * (c > 0).to(torch.float32)
+    if near is not None:
+        nr = near.to(device=x.device, dtype=torch.float32)
+        pen = as_t(suppression_penalty)
+        on = (nr > 0) & (pen > 0)
+        x = torch.where(on, x - torch.where(on, nr, torch.ones_like(nr)) * torch.where(pen > 0, pen, torch.ones_like(pen)), x)
+    return score_bias_row(x, banned=banned, eos_ids=eos_ids, a_t=a_t)
+
+
 # ------------------------------------------------------------------------------------------------ generate(stop_sequences=, min_tokens=, max_tokens=)
 # How a row ENDS.  The specification (stop_ban_ids / stop_state below are its plain statement; padt_stop_ban and padt_stop_match are compared
 # against them bit for bit), for a row that holds n generated tokens after a step:
@@ -775,6 +937,7 @@ class StepMode(NamedTuple):
     automaton: bool = False          # generate(token_automaton=): padt_token_automaton writes the bitmap the head reads (the union with the rules')
     bias: bool = False               # logit_bias / patch_bias / exponential_decay_length_penalty: padt_vrt_head_bias reads the session's bias vector and decay table
     stop: bool = False               # stop_sequences / min_tokens / max_tokens: padt_stop_ban in front of the head, padt_stop_match behind the bookkeeping kernel
+    counts: bool = False             # frequency_penalty / presence_penalty / patch_suppression: padt_vrt_head_counts reads the session's count tables, padt_count_update keeps them
 
 
 @dataclass(frozen=True)
@@ -810,8 +973,16 @@ class GenOptions:
     stop_sequences: InitVar[Optional[tuple]] = None
     min_tokens: InitVar[Optional[int]] = None
     row_limits: InitVar[bool] = False
+    # generate(frequency_penalty= / presence_penalty=) and generate(patch_suppression=): only WHETHER each mechanism is on — the per-row
+    # values travel with their batch like the forced table, so batches with different values share a decode group (each writes its own rows
+    # of the session's arrays) and a batch with the feature never shares one with a batch without.  Init-only attributes like those above.
+    count_penalties: InitVar[bool] = False
+    patch_suppression: InitVar[bool] = False
 
-    def __post_init__(self, forced, automaton, logit_bias, decay, patch_bias, stop_sequences, min_tokens, row_limits):
+    def __post_init__(self, forced, automaton, logit_bias, decay, patch_bias, stop_sequences, min_tokens, row_limits, count_penalties,
+                      patch_suppression):
+        object.__setattr__(self, "count_penalties", bool(count_penalties))
+        object.__setattr__(self, "patch_suppression", bool(patch_suppression))
         object.__setattr__(self, "stop_sequences", None if stop_sequences is None else tuple(tuple(int(i) for i in q) for q in stop_sequences))
         object.__setattr__(self, "min_tokens", None if min_tokens is None else int(min_tokens))
         object.__setattr__(self, "row_limits", bool(row_limits))
@@ -824,7 +995,8 @@ class GenOptions:
     def _key(self):
         # every field, whatever is added later, and the init-only attributes
         return tuple(getattr(self, f.name) for f in fields(self)) + (self.forced, self.automaton, self.logit_bias, self.decay, self.patch_bias,
-                                                                          self.stop_sequences, self.min_tokens, self.row_limits)
+                                                                          self.stop_sequences, self.min_tokens, self.row_limits,
+                                                                          self.count_penalties, self.patch_suppression)
 
     def __eq__(self, other):
         return self._key() == other._key() if isinstance(other, GenOptions) else NotImplemented
@@ -841,7 +1013,8 @@ class GenOptions:
                  f"decay={self.decay!r}", f"patch_bias={self.patch_bias!r}"]
         sq = self.stop_sequences
         args += [f"stop_sequences={sq!r}" if sq is None or sum(len(q) for q in sq) <= 16 else f"stop_sequences=<{len(sq)} sequences, #{hash(sq) & 0xffffffff:08x}>",
-                 f"min_tokens={self.min_tokens!r}", f"row_limits={self.row_limits!r}"]
+                 f"min_tokens={self.min_tokens!r}", f"row_limits={self.row_limits!r}", f"count_penalties={self.count_penalties!r}",
+                 f"patch_suppression={self.patch_suppression!r}"]
         return f"GenOptions({', '.join(args)})"
 
     @property
@@ -866,6 +1039,12 @@ class GenOptions:
         return self.stop_sequences is not None or self.min_tokens is not None or self.row_limits
 
     @property
+    def counts(self) -> bool:
+        """frequency_penalty / presence_penalty or patch_suppression is on: the head is padt_vrt_head_counts over the session's count
+        tables, which padt_count_update keeps behind the bookkeeping kernel."""
+        return self.count_penalties or self.patch_suppression
+
+    @property
     def reads_prompt(self) -> bool:
         """A ban or the repetition penalty is active: the built-in processors see the caller's full (B, L) input_ids."""
         return self.repetition_penalty != 1.0 or self.rules is not None
@@ -881,7 +1060,7 @@ class GenOptions:
         return StepMode(sampling=self.sampling is not None, keep_scores=self.keep_scores, keep_logits=self.keep_logits, rules=self.rules is not None,
                         token_logprobs=self.token_logprobs, top_k=self.top_logprobs, patches=self.patch_logprobs, processors=bool(processors),
                         reference=bool(reference), warpers=self.sampling is not None and self.sampling.warpers, forced=self.forced,
-                        automaton=self.automaton is not None, bias=self.score_bias, stop=self.stop)
+                        automaton=self.automaton is not None, bias=self.score_bias, stop=self.stop, counts=self.counts)
 
     def warper_kwargs(self) -> dict:
         """min_p / typical_p / epsilon_cutoff / eta_cutoff as explicit generate() keywords (with_warpers values), next to generate_kwargs():

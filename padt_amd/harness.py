@@ -9,8 +9,9 @@ Tokenisation / chat templating is the caller's (`prepare`): it needs the checkpo
 this repository.  `prepare(samples) -> dict(input_ids (local VRT ids), attention_mask, pixel_values, image_grid_thw,
 image_sizes [(w, h)], ids [image_id])`; optionally `image_index` (several samples on one image: generate(image_index=), with
 `pixel_values` / `image_grid_thw` holding each image once), `forced_tokens` (the batch's completion tokens to force:
-generate(forced_tokens=)), `patch_bias` (one entry per sample over its own patches: generate(patch_bias=)) and `min_tokens` / `max_tokens`
-(one int per sample: generate(min_tokens=, max_tokens=)).
+generate(forced_tokens=)), `patch_bias` (one entry per sample over its own patches: generate(patch_bias=)), `min_tokens` / `max_tokens`
+(one int per sample: generate(min_tokens=, max_tokens=)) and `frequency_penalty` / `presence_penalty` / `patch_suppression` (one entry per
+sample: generate()'s count edits).
 """
 import json
 import os
@@ -24,13 +25,15 @@ def infer_dataset(model, processor, dataset: Sequence, prepare: Callable, output
                   datasetname: str = "coco", suffix: str = "", rank: int = 0, world: int = 1, max_new_tokens: int = 1024,
                   depth: int = 2, merge: int = 4, schedule=None, repetition_penalty=None, eos_token_id=None,
                   token_automaton=None, logit_bias=None, exponential_decay_length_penalty=None, stop_sequences=None, min_tokens=None,
-                  max_tokens=None):
+                  max_tokens=None, frequency_penalty=None, presence_penalty=None, patch_suppression=None):
     """repetition_penalty / eos_token_id: None = the checkpoint's generation_config.json (model.generation_config), as HF's
     generate() inside the reference's loop applies it (utils.py:230-236 → padt.py:436).
     token_automaton: generate(token_automaton=) for every batch of the run (e.g. the dataset's category names followed by their VRTs).
     logit_bias / exponential_decay_length_penalty: generate()'s, for every batch of the run; a batch's own patch prior comes from `prepare`.
     stop_sequences / min_tokens / max_tokens: generate()'s, for every batch of the run (one value each; `prepare` may return per-row
-    `min_tokens` / `max_tokens` lists of its batch, which win)."""
+    `min_tokens` / `max_tokens` lists of its batch, which win).
+    frequency_penalty / presence_penalty / patch_suppression: generate()'s count edits, for every batch of the run (one value each; `prepare`
+    may return per-row lists of its batch under the same names, which win)."""
     os.makedirs(output_dir, exist_ok=True)
     f_res = os.path.join(output_dir, f"{datasetname}_{rank}_pred_results_{suffix}.json")
     f_comp = os.path.join(output_dir, f"{datasetname}_{rank}_pred_comp_{suffix}.json")
@@ -64,6 +67,9 @@ def infer_dataset(model, processor, dataset: Sequence, prepare: Callable, output
         extra["patch_bias"] = b.get("patch_bias")                 # None: no prior over the patches
         extra["min_tokens"] = b.get("min_tokens", min_tokens)     # the batch's own rows, else the run's value
         extra["max_tokens"] = b.get("max_tokens", max_tokens)
+        extra["frequency_penalty"] = b.get("frequency_penalty", frequency_penalty)
+        extra["presence_penalty"] = b.get("presence_penalty", presence_penalty)
+        extra["patch_suppression"] = b.get("patch_suppression", patch_suppression)
         drain(runner.submit(b["input_ids"], b["attention_mask"], b["pixel_values"], b["image_grid_thw"],
                             max_new_tokens=max_new_tokens, schedule=schedule, repetition_penalty=repetition_penalty,
                             eos_token_id=eos_token_id, token_automaton=token_automaton, logit_bias=logit_bias,

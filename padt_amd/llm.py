@@ -379,6 +379,10 @@ class DecodeSession:
         self.finish_step = self.finish_reason = self.stop_index = None      # ... what padt_stop_match records per row [B] (-1 / 0 / -1: no finish yet) ...
         self.sban = None                 # ... the bitmap padt_stop_ban writes for the head (the rules' / the automaton's plus the EOS ids below min_tokens) [B][words] ...
         self.summary_stop = self.summary_stop_host = None      # ... and generate_collect's read-back with the three finish arrays behind it
+        self.cnt_text = None             # mode.counts (generate(frequency_penalty=, presence_penalty=, patch_suppression=)): how often each row generated a text column, uint16 [B][V padded to 4] ...
+        self.cnt_patch = self.near = None        # ... how often a patch column was generated by its row, and the completed-run VRT tokens around each patch, uint16 [np_max] ...
+        self.cpen = None                 # ... each row's f, p and suppression penalty fp32 [3][B] (0: off) ...
+        self.cgrid = self.cradius = None         # ... and its merged patch grid (hp, wp) [B][2] and radius [B] (-1: no suppression), int32: what padt_count_update reads
         self.rope_cs = z(B, hd // 2, 2, dt=torch.float32)
         self.n_qkv = (cfg.num_attention_heads + 2 * Hkv) * hd
         self.graphs = {}                 # captured decode-step graph per mode (different kernel sequences and output buffers)
@@ -499,6 +503,22 @@ class DecodeSession:
             self.finish_step.fill_(-1)
             self.finish_reason.zero_()
             self.stop_index.fill_(-1)
+        if opts.counts:                                          # nothing generated yet; rows no batch of the group fills: no penalty, no suppression
+            if self.cnt_text is None:
+                V = self.cfg.vocab_size
+                self.cnt_text = torch.zeros((self.B, (V + 3) // 4 * 4), device=dev, dtype=ops.COUNT_DTYPE)
+                self.cnt_patch = torch.zeros(self.np_max, device=dev, dtype=ops.COUNT_DTYPE)
+                self.near = torch.zeros(self.np_max, device=dev, dtype=ops.COUNT_DTYPE)
+                self.cpen = torch.zeros((3, self.B), device=dev, dtype=torch.float32)
+                self.cgrid = torch.zeros((self.B, 2), device=dev, dtype=I32)
+                self.cradius = torch.zeros(self.B, device=dev, dtype=I32)
+            else:
+                self.cnt_text.zero_()
+                self.cnt_patch.zero_()
+                self.near.zero_()
+                self.cpen.zero_()
+                self.cgrid.zero_()
+            self.cradius.fill_(-1)
         if opts.rules is not None:
             self.rules.copy_(ops.gen_rules_tensor(key=opts.rules).to(dev, non_blocking=True))
             self.hist_len.zero_()                                # rows no batch of the group fills: an empty prompt
@@ -533,7 +553,11 @@ class DecodeSession:
         if hp is not None:                                   # packed table + packed hidden rows: 1 KiB contiguous wave loads
             ops.pack_rows(hn, self.hn_pk, self.B, to_packed=True)
             head_in, head_kw = self.hn_pk, dict(head_kw, table_packed=hp, rows=self.B)
-        if m.bias:                                           # the additive edits: the same heads, reading the session's bias vector and decay table
+        if m.counts:                                         # the count edits (and, with mode.bias, the additive ones): the same heads over the session's count tables
+            ops.vrt_head_counts(head_in, W["llm.head"], self.proto, self.vrt_off, self.part_val, self.part_idx, cfg.eos_token_id, self.cnt_text,
+                                self.cnt_patch, self.near, self.cpen, bias=self.bias if m.bias else None, decay=self.decay if m.bias else None,
+                                part_sum=psum, forced=fc if probe is not None else None, probe_val=probe, **head_kw)
+        elif m.bias:                                         # the additive edits: the same heads, reading the session's bias vector and decay table
             ops.vrt_head_bias(head_in, W["llm.head"], self.proto, self.vrt_off, self.part_val, self.part_idx, cfg.eos_token_id, bias=self.bias,
                               decay=self.decay, part_sum=psum, forced=fc if probe is not None else None, probe_val=probe, **head_kw)
         elif probe is not None:
@@ -592,6 +616,9 @@ class DecodeSession:
             ops.greedy_step(self.part_val, self.part_idx, nblk, hn, self.hidden_buf, self.unfinished, self.tokens,
                             self.cur_tok, self.step, self.slot, self.lens, self.pos3, cfg.eos_token_id, cfg.pad_token_id,
                             advance=advance, gen_cfg=self.gen_cfg, seen=self.seen, part_sum=psum, logprobs=lp_out)
+        if m.counts:                                         # the step counter is bumped: every row still unfinished counts the token it just generated
+            ops.count_update(self.tokens, self.step, self.unfinished, self.vrt_off, self.cgrid, self.cradius, self.cnt_text, self.cnt_patch,
+                             self.near, cfg.vocab_size, self.np_max)
         if m.stop:                                           # the step counter is bumped: the rows hold *step tokens.  EOS, stop sequence, budget
             ops.stop_match(self.stab, self.gen_cfg, cfg.eos_token_id, self.tokens, self.step, self.min_tok, self.max_tok, self.unfinished,
                            self.finish_step, self.finish_reason, self.stop_index)

@@ -22,7 +22,7 @@ from . import _lib, ops
 from .config import PaDTConfig
 from .decoder import PaDTDecoder
 from .generation import (_GENERATE_CONFIG_NAMED, _GENERATE_CONFIG_OWN, check_decay_length_penalty, check_forced_tokens, check_generate_kwargs,  # noqa: F401
-                         check_logit_bias, check_max_tokens, check_min_tokens, check_patch_bias, check_stop_sequences, check_token_automaton, NO_BUDGET, check_top_logprobs, completion_logprobs, forced_tokens_active, generation_config_fields, resolve_options, with_warpers,
+                         check_count_penalties, check_logit_bias, check_max_tokens, check_patch_suppression, check_min_tokens, check_patch_bias, check_stop_sequences, check_token_automaton, NO_BUDGET, check_top_logprobs, completion_logprobs, forced_tokens_active, generation_config_fields, resolve_options, with_warpers,
                          WARPER_NAMES)
 from .llm import MODE, LanguageModel, check_shared_destinations, plan_prompt, plan_prompt_shared
 from .vision import VisionEncoder
@@ -395,6 +395,24 @@ class PaDTForConditionalGeneration:
         ``min_tokens`` are equal and both or neither carry per-row lists (each batch writes its own rows of the session's minima and budgets);
         one captured graph serves every value; without the three the call is what it was: same kernels, same step mode, same output
         object.  They are NOT HF's ``min_new_tokens`` / ``min_length`` / ``stop_strings`` / ``max_time``, which stay refused by name.
+        Keywords ``frequency_penalty`` / ``presence_penalty`` / ``patch_suppression``: the edits that GROW with what a row has already
+        generated, applied by the logit head from per-row counts the captured step keeps on the device (generation.count_state /
+        count_penalty_row are the specification; ``padt_count_update`` behind the bookkeeping kernel, ``padt_vrt_head_counts``).
+        ``frequency_penalty=f`` / ``presence_penalty=p`` (each a float or one float per row, finite and within [-2, 2], else ``ValueError``;
+        0 / ``None``: off) are the OpenAI / vLLM pair: with n the number of times the row GENERATED the column — the prompt is never counted,
+        unlike the repetition penalty; forced tokens are; a row's own VRT columns count like text ids — ``s = s - f * n``, then
+        ``s = s - p * (n > 0)``, vLLM's ``apply_penalties`` arithmetic in fp32.  ``patch_suppression=(radius, penalty)`` (or a list of B such
+        pairs / ``None`` entries): non-maximum suppression in the pointing space — once a run of VRT tokens is COMPLETED (followed by a non-VRT
+        token), every patch within ``max(|dy|, |dx|) <= radius`` of one of its tokens, on the row-major merged grid ``(h/2, w/2)`` that
+        ``patch_bias`` maps use, loses ``penalty`` per such token; ``penalty=inf`` bans it.  A run still open suppresses nothing, so an object's
+        own VRT tokens may sit next to each other.  ``radius``: an integer in [0, 7] (above: ``NotImplementedError``; negative or not an
+        integer: ``ValueError``); ``penalty`` > 0, finite or ``+inf`` (else ``ValueError``).  Order in the head: bias, repetition penalty,
+        token counts, patch neighbourhood, mask / schedule / bans, EOS decay — so the arg-max, ``token_logprobs``, a forced column's value,
+        the sampler and its warpers, ``.scores``, ``top_logprobs`` / ``patch_logprobs`` and a caller's ``logits_processor`` all see the
+        edited row; a row whose every candidate ends at ``-inf`` continues with the pad token.  Also read from the dict form of
+        ``generation_config=``.  Works with ``precision="reference"`` (the same head).  The options carry only WHETHER each mechanism is
+        on: batches with different values share a decode group (each writes its own rows), a batch with the feature and one without do
+        not; one captured graph serves every value; without the three the call is what it was: same kernels, same step mode.
         """
         if synced_gpus:
             raise NotImplementedError("generate(synced_gpus=True) is the ZeRO-3 / FSDP lock-step loop (padt.py:445,670): every rank holds a full "
@@ -406,6 +424,7 @@ class PaDTForConditionalGeneration:
         logit_bias, patch_bias = kwargs.pop("logit_bias", None), kwargs.pop("patch_bias", None)      # ... and the three additive score edits
         decay = kwargs.pop("exponential_decay_length_penalty", None)
         stop_sequences, min_tokens, max_tokens = (kwargs.pop(k, None) for k in ("stop_sequences", "min_tokens", "max_tokens"))      # ... and how a row ends
+        frequency_penalty, presence_penalty, patch_suppression = (kwargs.pop(k, None) for k in ("frequency_penalty", "presence_penalty", "patch_suppression"))      # ... and the count edits
         if generation_config is not None:
             named = dict(max_new_tokens=max_new_tokens, max_length=max_length, do_sample=do_sample, repetition_penalty=repetition_penalty,
                          eos_token_id=eos_token_id, pad_token_id=pad_token_id, temperature=temperature, top_k=top_k, top_p=top_p,
@@ -424,6 +443,12 @@ class PaDTForConditionalGeneration:
                     top_logprobs = v if top_logprobs is None else top_logprobs
                 elif k == "output_patch_logprobs":
                     output_patch_logprobs = output_patch_logprobs or bool(v)
+                elif k == "frequency_penalty":
+                    frequency_penalty = v if frequency_penalty is None else frequency_penalty
+                elif k == "presence_penalty":
+                    presence_penalty = v if presence_penalty is None else presence_penalty
+                elif k == "patch_suppression":
+                    patch_suppression = v if patch_suppression is None else patch_suppression
                 elif k not in _GENERATE_CONFIG_OWN:
                     kwargs.setdefault(k, v)                           # the keyword policy below names what this path does not implement
             (max_new_tokens, max_length, do_sample, repetition_penalty, eos_token_id, pad_token_id, temperature, top_k, top_p, no_repeat_ngram_size,
@@ -452,6 +477,9 @@ class PaDTForConditionalGeneration:
             hooks = dict(hooks or {}, bias=dict(logit_bias=logit_bias, patch_bias=patch_bias, decay=decay))
         if stop_sequences is not None or min_tokens is not None or max_tokens is not None:
             hooks = dict(hooks or {}, stop=dict(stop_sequences=stop_sequences, min_tokens=min_tokens, max_tokens=max_tokens))
+        if frequency_penalty is not None or presence_penalty is not None or patch_suppression is not None:
+            hooks = dict(hooks or {}, counts=dict(frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
+                                                  patch_suppression=patch_suppression))
         if output_logits:
             pen = self.generation_config.repetition_penalty if repetition_penalty is None else repetition_penalty
             if float(pen) != 1.0 or schedule is not None or processors is not None:
@@ -501,6 +529,8 @@ class PaDTForConditionalGeneration:
         data, the other two part of the options.
         ``hooks=dict(stop=dict(stop_sequences=..., min_tokens=..., max_tokens=...))``: generate()'s three arguments of that name (None
         entries: off); the sequences and a one-value ``min_tokens`` are part of the options, per-row lists are per-batch data.
+        ``hooks=dict(counts=dict(frequency_penalty=..., presence_penalty=..., patch_suppression=...))``: generate()'s three arguments of that
+        name (None entries: off); the values are per-batch data, the options only say which of the two mechanisms is on.
         """
         # a call's min_p / typical_p / epsilon_cutoff / eta_cutoff arrive as hooks["warpers"] (this method's parameter list is frozen) and are put
         # in front of the generation config's; what is left of `hooks` is the caller's processors / criteria, or nothing
@@ -532,6 +562,14 @@ class PaDTForConditionalGeneration:
             max_tok = check_max_tokens(hs.get("max_tokens"), input_ids.shape[0], max_new_tokens)
             min_tok = check_min_tokens(hs.get("min_tokens"), input_ids.shape[0], max_new_tokens, max_tok)
             hooks = {k: v for k, v in hooks.items() if k != "stop"} or None
+        counts = None
+        if hooks is not None and "counts" in hooks:
+            hc = hooks["counts"] or {}
+            fpen, ppen = check_count_penalties(hc.get("frequency_penalty"), hc.get("presence_penalty"), input_ids.shape[0])
+            supp = check_patch_suppression(hc.get("patch_suppression"), input_ids.shape[0])
+            if fpen is not None or supp is not None:                  # all off: the call without the arguments
+                counts = dict(frequency_penalty=fpen, presence_penalty=ppen, patch_suppression=supp)
+            hooks = {k: v for k, v in hooks.items() if k != "counts"} or None
         decay = check_decay_length_penalty(decay, max_new_tokens)
         if decay is not None and decay[1] == 1.0:
             decay = None                                          # a[t] = 1 ** k - 1 = 0 at every step: the call without the argument
@@ -563,13 +601,20 @@ class PaDTForConditionalGeneration:
             opts = dataclasses.replace(opts, stop_sequences=stop_seqs, min_tokens=None if per_row else min_tok,
                                        row_limits=per_row or max_tok is not None)
             stop = dict(min_tokens=min_tok if per_row else None, max_tokens=max_tok)
+        if counts is not None:
+            opts = dataclasses.replace(opts, count_penalties=counts["frequency_penalty"] is not None,
+                                       patch_suppression=counts["patch_suppression"] is not None)
+            if keep_logits and opts.sampling is None:
+                raise NotImplementedError("generate(output_logits=True) with a logits processor active (frequency_penalty, presence_penalty or "
+                                          "patch_suppression): only the processed rows are kept on this path — ask for output_scores=True")
         return owner._launch(opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, max_new_tokens=max_new_tokens,
                              schedule=schedule, hooks=hooks, sync_every=sync_every, use_graph=use_graph, lane=lane, decode_stream=decode_stream,
                              group=group, n_slots=n_slots, vit_stream=vit_stream, inputs_ready=inputs_ready, forced=forced, automaton=automaton,
-                             patch_bias=patch_bias, stop=stop)
+                             patch_bias=patch_bias, stop=stop, counts=counts)
 
     def _launch(self, opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, *, max_new_tokens, schedule, hooks, sync_every,
-                use_graph, lane, decode_stream, group, n_slots, vit_stream, inputs_ready, forced=None, automaton=None, patch_bias=None, stop=None):
+                use_graph, lane, decode_stream, group, n_slots, vit_stream, inputs_ready, forced=None, automaton=None, patch_bias=None, stop=None,
+                counts=None):
         """generate_launch on the group's owner, with the call's options resolved (generation.GenOptions)."""
         self._batches_seen += 1
         if pixel_values is None or image_grid_thw is None:
@@ -597,6 +642,19 @@ class PaDTForConditionalGeneration:
             gi = grid if image_index is None else grid[torch.as_tensor([int(i) for i in image_index], dtype=torch.long)]
             patch_bias = check_patch_bias(patch_bias, B, [plan.vrt_off[i + 1] - plan.vrt_off[i] for i in range(B)],
                                           [(int(g[1]) // ms, int(g[2]) // ms) for g in gi])
+        count_grids = None
+        if opts.counts:                                           # each row's merged patch grid against its patch count, before any device state is touched:
+            cv = counts or {}                                     # padt_count_update indexes the row's patches with it
+            ms = cfg.vision_config.spatial_merge_size
+            gi = grid if image_index is None else grid[torch.as_tensor([int(i) for i in image_index], dtype=torch.long)]
+            count_grids = [(int(g[1]) // ms, int(g[2]) // ms) for g in gi]
+            supp = cv.get("patch_suppression") or [None] * B
+            for b, (hp_, wp_) in enumerate(count_grids):
+                if hp_ * wp_ != plan.vrt_off[b + 1] - plan.vrt_off[b]:
+                    if supp[b] is not None:
+                        raise ValueError(f"generate(patch_suppression=...): row {b}: a merged patch grid of {hp_} x {wp_} for "
+                                         f"{plan.vrt_off[b + 1] - plan.vrt_off[b]} patches")
+                    count_grids[b] = (0, 0)                       # never read: the row's radius is -1
         if opts.rules is not None:
             need_s = max(need_s, plan.L_pad)                      # the session's history rows hold the padded prompt row
         if hooks is not None and (group is not None or n_slots != 1):
@@ -716,6 +774,16 @@ class PaDTForConditionalGeneration:
                 sess.max_tok[rows].copy_(torch.tensor(lim["max_tokens"], dtype=torch.int32).to(dev, non_blocking=True))
             else:
                 sess.max_tok[rows].fill_(NO_BUDGET)
+        if opts.counts:
+            # this batch's rows of the session's penalties, grids and radii (begin() zeroed the tables and switched every row off): its own
+            # values and the grids checked above
+            cv = counts or {}
+            supp = cv.get("patch_suppression") or [None] * B
+            pen = torch.tensor([cv.get("frequency_penalty") or [0.0] * B, cv.get("presence_penalty") or [0.0] * B,
+                                [0.0 if e is None else e[1] for e in supp]], dtype=torch.float32)
+            sess.cpen[:, rows].copy_(pen.to(dev, non_blocking=True))
+            sess.cgrid[rows].copy_(torch.tensor(count_grids, dtype=torch.int32).to(dev, non_blocking=True))
+            sess.cradius[rows].copy_(torch.tensor([-1 if e is None else e[0] for e in supp], dtype=torch.int32).to(dev, non_blocking=True))
         if patch_bias is not None:
             # this batch's segment of the session's bias vector: its own prototype rows (begin() zero-filled the vector; a row without an entry adds 0)
             seg = torch.zeros(n_proto, dtype=torch.float32)
@@ -735,7 +803,7 @@ class PaDTForConditionalGeneration:
             ops.gather_rows(hn_all, plan.last_idx, out=sess.hn_first[rows])
         group["subs"].append(dict(plan=plan, low=low, high=high, pe=pe, proto=proto, hn_all=hn_all, input_ids=input_ids,
                                   n_proto=n_proto, row0=row0, proto_row0=proto_row0, nf=nf, p_max=p_max, forced=forced, automaton=automaton,
-                                  patch_bias=patch_bias, stop=stop,
+                                  patch_bias=patch_bias, stop=stop, counts=counts,
                                   inputs=(attention_mask, pixel_values, image_grid_thw, image_index)))       # what a re-run on the bf16 twin needs
         group["proto_rows"] = proto_row0 + n_proto
         if len(group["subs"]) == group["n_slots"]:
@@ -891,6 +959,8 @@ class PaDTForConditionalGeneration:
                   output_scores=output_scores, output_logits=output_logits)
         if sub.get("stop") is not None:                           # the batch's own per-row lists: the options only say that there are some
             kw.update({k: v for k, v in sub["stop"].items() if v is not None})
+        if sub.get("counts") is not None:                         # the batch's own per-row values: the options only say which mechanism is on
+            kw.update(sub["counts"])
         if group.get("hooks") is not None:
             kw.update(logits_processor=group["hooks"]["processors"], stopping_criteria=group["hooks"]["criteria"])
         if sub.get("forced") is not None:

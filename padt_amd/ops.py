@@ -1096,6 +1096,74 @@ def vrt_head_bias(hidden, table, proto, vrt_off, part_val, part_idx, eos, bias=N
                       _p(probe_val) if forced is not None else 0, _p(bias), _p(decay), decay.numel() if decay is not None else 0))
 
 
+COUNT_MAX_RADIUS = 7            # patch_suppression: (2 * 7 + 1) ** 2 = 225 window cells, one thread each of padt_count_update's 256
+COUNT_DTYPE = torch.int16       # the count tables' element as torch holds it: the kernels read the 16 bits UNSIGNED, saturating at 65535
+COUNT_SAT = 65535               # (profiles/count_penalties.md §1); count_values() gives the numbers
+
+
+def count_values(t):
+    """A count table (COUNT_DTYPE) → its unsigned values, int32."""
+    assert t.dtype == COUNT_DTYPE
+    return t.to(torch.int32) & 0xffff
+
+
+def _chk_counts(cnt_text, cnt_patch, near, B, vocab, n_proto):
+    for t in (cnt_text, cnt_patch, near):
+        assert t.dtype == COUNT_DTYPE and t.is_cuda
+    assert cnt_text.dim() == 2 and cnt_text.stride(1) == 1 and cnt_text.shape[0] >= B and cnt_text.shape[1] >= vocab
+    assert cnt_text.stride(0) >= vocab and cnt_text.stride(0) % 4 == 0 and cnt_text.data_ptr() % 8 == 0
+    assert cnt_patch.dim() == 1 and cnt_patch.stride(0) == 1 and cnt_patch.numel() >= n_proto
+    assert near.dim() == 1 and near.stride(0) == 1 and near.numel() >= n_proto
+
+
+def count_update(tokens, step, unfinished, vrt_off, grid, radius, cnt_text, cnt_patch, near, vocab, n_proto):
+    """After greedy_step / forced_step, in front of stop_match: every row the bookkeeping kernel left unfinished adds the token it just
+    generated to its counts — cnt_text[b][tok] for a text id, cnt_patch[tok - vocab] for one of its own patches — and, when that token closed a
+    run of VRT tokens, 1 per run token to near[] on the clipped radius[b] window of its grid[b] = (hp, wp) (padt_count_update;
+    generation.count_state is the specification).  uint16 tables, saturating; radius int32 (B,), < 0 = no suppression for the row; grid
+    int32 (B, 2).  Where the host can see it (CPU tensors are not read back), hp * wp == the row's patch count is the caller's to check."""
+    B = radius.numel()
+    _chk_i32(step, n=1)
+    _chk_i32(unfinished, radius, n=B)
+    _chk_i32(vrt_off, n=B + 1)
+    _chk_i32(grid, n=2 * B)
+    assert grid.dim() == 2 and grid.shape[1] == 2
+    _chk_counts(cnt_text, cnt_patch, near, B, int(vocab), int(n_proto))
+    assert tokens.dtype == torch.int64 and tokens.is_cuda and tokens.dim() == 2 and tokens.stride(1) == 1 and tokens.shape[0] >= B
+    _lib.check(_lib.load().padt_count_update(_stream(), _p(tokens), tokens.stride(0), _p(step), _p(unfinished), _p(vrt_off), _p(grid), _p(radius),
+                                             _p(cnt_text), cnt_text.stride(0), int(vocab), _p(cnt_patch), _p(near), int(n_proto), B),
+               "padt_count_update")
+
+
+def vrt_head_counts(hidden, table, proto, vrt_off, part_val, part_idx, eos, cnt_text, cnt_patch, near, cpen, bias=None, decay=None, step=None,
+                    mode_table=None, logits=None, table_packed=None, rows=None, gen_cfg=None, seen=None, ban=None, part_sum=None, forced=None,
+                    probe_val=None):
+    """vrt_head_bias (bias / decay optional) with the count edits of generate(frequency_penalty=, presence_penalty=, patch_suppression=)
+    (padt_vrt_head_counts; generation.count_penalty_row is the specification): count_update's three uint16 tables and cpen fp32 (3, rows) =
+    per row f, p and the suppression penalty (0: off, inf: a ban)."""
+    B = hidden.shape[0] if rows is None else rows
+    n_cols = table.shape[0] + proto.shape[0]
+    _chk_counts(cnt_text, cnt_patch, near, B, table.shape[0], proto.shape[0])
+    assert cpen.dtype == torch.float32 and cpen.is_cuda and cpen.is_contiguous() and cpen.shape == (3, B)
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.is_cuda and bias.dim() == 1 and bias.is_contiguous() and bias.numel() >= n_cols
+    if decay is not None:
+        assert decay.dtype == torch.float32 and decay.is_cuda and decay.dim() == 1 and decay.is_contiguous() and decay.numel() > 0
+        assert step is not None and step.dtype == torch.int32
+    if ban is not None:
+        assert ban.dtype == torch.int32 and ban.is_cuda and ban.dim() == 2 and ban.is_contiguous() and ban.shape[0] >= B
+    if part_sum is not None:
+        assert part_sum.dtype == torch.float32 and part_sum.is_cuda and part_sum.is_contiguous() and part_sum.numel() >= (n_cols + 15) // 16 * B
+    if forced is not None:
+        _chk_forced(forced, B)
+        assert part_sum is not None and step is not None and step.dtype == torch.int32
+        assert probe_val is not None and probe_val.dtype == torch.float32 and probe_val.is_cuda and probe_val.is_contiguous() and probe_val.numel() >= B
+    _head_call("padt_vrt_head_counts", hidden, table, proto, vrt_off, part_val, part_idx, eos, mode_table, step, logits, table_packed, B, gen_cfg,
+               seen, (_p(ban), ban.shape[1] if ban is not None else 0, _p(part_sum), _p(forced), forced.shape[1] if forced is not None else 0,
+                      _p(probe_val) if forced is not None else 0, _p(bias), _p(decay), decay.numel() if decay is not None else 0,
+                      _p(cnt_text), cnt_text.stride(0), _p(cnt_patch), _p(near), _p(cpen)))
+
+
 def forced_step(part_val, part_idx, nblk, hidden, hidden_buf, unfinished, tokens_out, cur_tok, step, slot, lens, pos3, eos, pad, forced, n_cols,
                 advance=True, gen_cfg=None, seen=None, part_sum=None, logprobs=None, probe_val=None):
     """greedy_step with the caller's tokens (padt_forced_step): an unfinished row b with 0 <= forced[b][*step] < n_cols takes that column as its

@@ -21,7 +21,8 @@ def sample_grids(image_grid_thw, image_index):
 def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens=1024,
               schedule: Optional[Sequence] = None, need_thinking_mask=None, image_index=None, do_sample=False, min_p=None, typical_p=None,
               epsilon_cutoff=None, eta_cutoff=None, forced_tokens=None, token_automaton=None, logit_bias=None, patch_bias=None,
-              exponential_decay_length_penalty=None, stop_sequences=None, min_tokens=None, max_tokens=None, **gen_kw):
+              exponential_decay_length_penalty=None, stop_sequences=None, min_tokens=None, max_tokens=None, frequency_penalty=None,
+              presence_penalty=None, patch_suppression=None, **gen_kw):
     """→ (decoded dict of vl_decode, completions, labels, vrts).  ``input_ids`` carries LOCAL VRT ids (as a processor
     emits them) and is updated in place exactly like the reference's callers do.
     ``image_index``: sample b asks about image image_index[b] of the N <= B images given (generate(image_index=)); everything per sample
@@ -33,7 +34,8 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
     ``logit_bias`` / ``patch_bias`` / ``exponential_decay_length_penalty``: generate()'s additive score edits (text ids; one entry per
     sample over its own patches; (start, factor)).
     ``stop_sequences`` / ``min_tokens`` / ``max_tokens``: generate()'s — how a row ends; the decoded dict then carries ``finish_reason`` /
-    ``stop_index`` / ``finish_step``."""
+    ``stop_index`` / ``finish_step``.
+    ``frequency_penalty`` / ``presence_penalty`` / ``patch_suppression``: generate()'s count edits (a value, or one per sample)."""
     B = input_ids.shape[0]
     grid_in = image_grid_thw
     if image_index is not None:
@@ -45,7 +47,8 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
                          output_hidden_states=True, return_dict_in_generate=True, schedule=schedule, min_p=min_p, typical_p=typical_p,
                          epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, forced_tokens=forced_tokens, token_automaton=token_automaton,
                          logit_bias=logit_bias, patch_bias=patch_bias, exponential_decay_length_penalty=exponential_decay_length_penalty,
-                         stop_sequences=stop_sequences, min_tokens=min_tokens, max_tokens=max_tokens, **gen_kw)
+                         stop_sequences=stop_sequences, min_tokens=min_tokens, max_tokens=max_tokens, frequency_penalty=frequency_penalty,
+                         presence_penalty=presence_penalty, patch_suppression=patch_suppression, **gen_kw)
     L = input_ids.shape[1]
     seq_local = processor.assign_to_local_vrt_id(out["sequences"].cpu(), image_grid_thw.cpu())
     completion_ids = seq_local[:, L:]
@@ -117,7 +120,8 @@ class PipelinedRunner:
                need_thinking_mask=None, sync_every=None, repetition_penalty=None, eos_token_id=None, no_repeat_ngram_size=None,
                bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None, do_sample=False, min_p=None,
                typical_p=None, epsilon_cutoff=None, eta_cutoff=None, forced_tokens=None, token_automaton=None, logit_bias=None, patch_bias=None,
-               exponential_decay_length_penalty=None, stop_sequences=None, min_tokens=None, max_tokens=None, **sampling):
+               exponential_decay_length_penalty=None, stop_sequences=None, min_tokens=None, max_tokens=None, frequency_penalty=None,
+               presence_penalty=None, patch_suppression=None, **sampling):
         """image_index: see generate(); the batch's results are those of the expanded batch.
         do_sample (default: greedy) with min_p / typical_p / epsilon_cutoff / eta_cutoff and, through **sampling, temperature / top_k / top_p /
         seed: see generate(); batches whose resolved options differ in any of them (the seed included) do not share a decode group.
@@ -129,7 +133,9 @@ class PipelinedRunner:
         when logit_bias and the decay are equal and both or neither carry a patch_bias (each batch its own tensors).
         stop_sequences / min_tokens / max_tokens: generate()'s — how a row ends; the decoded dict then carries "finish_reason" / "stop_index" /
         "finish_step".  Batches share a decode group only when stop_sequences and a one-value min_tokens are equal and both or neither carry
-        per-row lists (each batch its own min_tokens / max_tokens rows)."""
+        per-row lists (each batch its own min_tokens / max_tokens rows).
+        frequency_penalty / presence_penalty / patch_suppression: generate()'s count edits.  Batches share a decode group whatever their
+        values are (each batch writes its own rows), as long as the same of the two mechanisms — token counts, patch suppression — are on."""
         done = []
         bid = self.n_batches
         self.n_batches += 1
@@ -148,6 +154,8 @@ class PipelinedRunner:
             hooks["bias"] = dict(logit_bias=logit_bias, patch_bias=patch_bias, decay=exponential_decay_length_penalty)
         if stop_sequences is not None or min_tokens is not None or max_tokens is not None:
             hooks["stop"] = dict(stop_sequences=stop_sequences, min_tokens=min_tokens, max_tokens=max_tokens)
+        if frequency_penalty is not None or presence_penalty is not None or patch_suppression is not None:
+            hooks["counts"] = dict(frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, patch_suppression=patch_suppression)
         for attempt in range(2):
             if self.cur is None:
                 while len(self.pending) > self.depth - 1:         # the lane about to be reused must have been collected
