@@ -248,6 +248,20 @@ int padt_llm_qkv_post_shared(void* stream, const void* qkv, long ld_qkv, const i
                              void* k_join, long ld_kj, void* v_join, long ld_vj, long n_join, void* k_cache, void* vt_cache,
                              const int* dst_off, const int* dst_sample, const int* dst_slot, const int* dst_row, long T, int n_heads,
                              int n_kv_heads, int head_dim, int s_max, int batch, int sec0, int sec1, int cache_packed);
+/* Fan-out of CACHED prompt-prefix rows (generate(prefix=)): k_pre / v_pre [n_pre][ld_pre] hold one layer's roped K rows and V rows
+ * ([n_kv_heads * head_dim] each, as padt_llm_qkv_post_shared leaves them in join rows) of n_images prefixes, image u at rows
+ * [pre_off[u], pre_off[u+1]) (pre_off: n_images + 1 device ints; P_u = its length, max_p >= every P_u sizes the grid).  For every member m
+ * (mem_image[m], mem_row[m], mem_join[m]) the P rows of its image are written to slots [0, P) of the K / V^T cache images of session row
+ * mem_row[m] (cache_packed as above; skipped unless 0 <= row < batch and P <= s_max) and to rows [mem_join[m], mem_join[m] + P) of the
+ * join buffers (skipped unless they lie inside [0, n_join)); a member whose image is outside [0, n_images), or whose prefix rows are
+ * outside [0, n_pre), is skipped.  Nothing else is written, and what lands is bit for bit what padt_llm_qkv_post_shared writes for those
+ * tokens: pure data movement (32-slot tile x kv head x member; 16-byte stores in fragment order, V^T transposed through LDS, the fragment
+ * cut by P element-wise; a scalar branch for head_dim % 16, s_max % 8, a row stride % 8 or a base that is not 16-byte aligned).
+ * Returns -1 without launching on a null pointer or bad dimensions. */
+int padt_kv_prefix_fanout(void* stream, const void* k_pre, const void* v_pre, long ld_pre, long n_pre, const int* pre_off, int n_images,
+                          const int* mem_image, const int* mem_row, const int* mem_join, int n_members, int max_p, void* k_cache,
+                          void* vt_cache, void* k_join, long ld_kj, void* v_join, long ld_vj, long n_join, int n_kv_heads, int head_dim,
+                          int s_max, int batch, int cache_packed);
 /* PaDT mask head tail: per-patch 4x4 dot with the object's mask token, scattered to (n_obj, 4H, 4W) fp32.
  * padt_decoder.py:241-274. */
 int padt_mask_scatter(void* stream, const void* e2, long ld_e2, const void* mask_tok, long ld_tok, const int* cu_patch,

@@ -776,6 +776,152 @@ extern "C" int PADT_TWIN(padt_llm_qkv_post_shared)(void* stream, const void* qkv
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Fan-out of CACHED prompt-prefix rows (generate(prefix=), llm.plan_prompt_prefix): one layer's roped K rows / V rows of up to N images,
+// as a prompt pass with join-only destinations left them (modeling.PromptPrefix), go to every member (image, session row, join offset):
+// slots [0, P) of that row's K / V^T cache images and rows [off, off + P) of the join buffers — what llm_qkv_post_shared_kernel would have
+// written for those tokens, bit for bit (pure data movement).  Block = (32-slot tile, kv head, member).  16-byte path: the K / V tile is
+// copied row-wise (join rows, row-major K image), the V tile is staged in LDS for the transposition, and the packed images are written in
+// fragment order — lane l of a wave stores the 16 bytes of lane l of a fragment, so a wave writes whole 1 KiB fragments; a chunk of the
+// V^T image holding a slot >= P is written element by element.  Row stride of the LDS tile: 256 + 8 elements = 132 dwords, so the four
+// row groups a V^T fragment read touches (rows 4 apart) start 16 banks apart.
+constexpr int KVF_SLOTS = 32, KVF_LD = 256 + 8;
+
+struct KvPrefixFanoutArgs {
+    const x16_t* k_pre; const x16_t* v_pre; long ld_pre;     // [n_pre][>= Hkv*D]: image u's prefix at rows [pre_off[u], pre_off[u+1])
+    const int* pre_off;                                      // [N+1]
+    const int* mem_image; const int* mem_row; const int* mem_join;      // [M]
+    x16_t* kc; x16_t* vtc;                                   // caches
+    x16_t* k_join; long ld_kj; x16_t* v_join; long ld_vj;
+    int n_pre, N, Hkv, D, S_max, B, n_join, cache_packed, vec;
+};
+
+__global__ __launch_bounds__(256) void kv_prefix_fanout_kernel(KvPrefixFanoutArgs p) {
+    __shared__ __attribute__((aligned(16))) x16_t vs[KVF_SLOTS * KVF_LD];
+    const int m = blockIdx.z, g = blockIdx.y, s0 = blockIdx.x * KVF_SLOTS;
+    // every exit below is taken by the whole block, before its barrier
+    const int u = p.mem_image[m];
+    if ((unsigned)u >= (unsigned)p.N) return;
+    const int r0 = p.pre_off[u], P = p.pre_off[u + 1] - r0;
+    if (r0 < 0 || P <= 0 || (long)r0 + P > p.n_pre || s0 >= P) return;
+    const int b = p.mem_row[m], off = p.mem_join[m];
+    const bool cache = (unsigned)b < (unsigned)p.B && P <= p.S_max;             // a member out of range is skipped, each sink by itself
+    const bool join = off >= 0 && (long)off + P <= p.n_join;
+    if (!cache && !join) return;
+    const int D = p.D, S = p.S_max, packed = p.cache_packed;
+    const int ns = min(KVF_SLOTS, P - s0);                                      // slots of this tile inside the prefix
+    const x16_t* ks = p.k_pre + (long)(r0 + s0) * p.ld_pre + (long)g * D;
+    const x16_t* vsrc = p.v_pre + (long)(r0 + s0) * p.ld_pre + (long)g * D;
+    x16_t* kc = cache ? p.kc + ((long)b * p.Hkv + g) * S * D : nullptr;
+    x16_t* vtc = cache ? p.vtc + ((long)b * p.Hkv + g) * D * S : nullptr;
+    x16_t* kj = join ? p.k_join + (long)(off + s0) * p.ld_kj + (long)g * D : nullptr;
+    x16_t* vj = join ? p.v_join + (long)(off + s0) * p.ld_vj + (long)g * D : nullptr;
+    if (!p.vec) {                                                               // scalar path: head_dim % 16 != 0, odd strides or unaligned bases
+        for (int i = threadIdx.x; i < ns * D; i += blockDim.x) {
+            const int s = i / D, d = i % D;
+            const x16_t k = ks[(long)s * p.ld_pre + d], v = vsrc[(long)s * p.ld_pre + d];
+            if (join) {
+                kj[(long)s * p.ld_kj + d] = k;
+                vj[(long)s * p.ld_vj + d] = v;
+            }
+            if (cache) {
+                kc[kc_offset(s0 + s, d, D, packed)] = k;
+                vtc[vtc_offset(s0 + s, d, S, packed)] = v;
+            }
+        }
+        return;
+    }
+    // ---- row order: join rows, the row-major K image, V into LDS
+    const int cpr = D >> 3;                                                     // 16-byte chunks per row
+    for (int i = threadIdx.x; i < ns * cpr; i += blockDim.x) {
+        const int s = i / cpr, d = (i % cpr) * 8;
+        const u32x4 k = *reinterpret_cast<const u32x4*>(ks + (long)s * p.ld_pre + d);
+        const u32x4 v = *reinterpret_cast<const u32x4*>(vsrc + (long)s * p.ld_pre + d);
+        if (join) {
+            *reinterpret_cast<u32x4*>(kj + (long)s * p.ld_kj + d) = k;
+            *reinterpret_cast<u32x4*>(vj + (long)s * p.ld_vj + d) = v;
+        }
+        if (cache && !packed) *reinterpret_cast<u32x4*>(kc + (long)(s0 + s) * D + d) = k;
+        *reinterpret_cast<u32x4*>(vs + s * KVF_LD + d) = v;
+    }
+    if (!cache) return;
+    __syncthreads();
+    if (packed) {
+        // K [S/16][D/32][64][8]: fragment f = (16-slot block sb, 32-wide d block db) of this tile; lane l holds slot sb*16 + (l & 15),
+        // elements d = db*32 + (l >> 4)*8 .. +7 (kc_offset) — a chunk lies in ONE slot, so the cut by P is per chunk
+        const int dbs = D >> 5;
+        for (int i = threadIdx.x; i < 2 * dbs * 64; i += blockDim.x) {
+            const int l = i & 63, f = i >> 6, sb = f / dbs, db = f % dbs;
+            const int s = sb * 16 + (l & 15), d = db * 32 + (l >> 4) * 8;
+            if (s < ns)
+                *reinterpret_cast<u32x4*>(kc + ((((long)((s0 >> 4) + sb) * dbs + db) * 64) + l) * 8) =
+                    *reinterpret_cast<const u32x4*>(ks + (long)s * p.ld_pre + d);
+        }
+        // V^T [D/16][S/32][64][8]: fragment = (16-wide d block db, this 32-slot block); lane l holds d = db*16 + (l & 15) at the eight slots
+        // (j >> 2)*16 + (l >> 4)*4 + (j & 3), j = 0 .. 7 (vtc_offset)
+        for (int i = threadIdx.x; i < (D >> 4) * 64; i += blockDim.x) {
+            const int l = i & 63, db = i >> 6, d = db * 16 + (l & 15), sq = (l >> 4) * 4;
+            x16_t* dst = vtc + ((((long)db * (S >> 5) + (s0 >> 5)) * 64) + l) * 8;
+            if (16 + sq + 3 < ns) {
+                __attribute__((aligned(16))) x16_t e[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) e[j] = vs[((j >> 2) * 16 + sq + (j & 3)) * KVF_LD + d];
+                *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(e);
+            } else {
+                for (int j = 0; j < 8; ++j) {
+                    const int s = (j >> 2) * 16 + sq + (j & 3);
+                    if (s < ns) dst[j] = vs[s * KVF_LD + d];
+                }
+            }
+        }
+    } else {
+        // V^T [D][S]: item = (d, 8-slot chunk sc); the four lanes of a quad write the 64 contiguous bytes of one d
+        for (int i = threadIdx.x; i < D * 4; i += blockDim.x) {
+            const int sc = (i & 3) * 8, d = i >> 2;
+            x16_t* dst = vtc + (long)d * S + s0 + sc;
+            if (sc + 8 <= ns) {
+                __attribute__((aligned(16))) x16_t e[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) e[j] = vs[(sc + j) * KVF_LD + d];
+                *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(e);
+            } else {
+                for (int j = 0; j < 8 && sc + j < ns; ++j) dst[j] = vs[(sc + j) * KVF_LD + d];
+            }
+        }
+    }
+}
+
+extern "C" int PADT_TWIN(padt_kv_prefix_fanout)(void* stream, const void* k_pre, const void* v_pre, long ld_pre, long n_pre, const int* pre_off,
+                                     int n_images, const int* mem_image, const int* mem_row, const int* mem_join, int n_members, int max_p,
+                                     void* k_cache, void* vt_cache, void* k_join, long ld_kj, void* v_join, long ld_vj, long n_join,
+                                     int n_kv_heads, int head_dim, int s_max, int batch, int cache_packed) {
+    if (!k_pre || !v_pre || !pre_off || !mem_image || !mem_row || !mem_join || !k_cache || !vt_cache || !k_join || !v_join) {
+        padt_set_error("padt_kv_prefix_fanout: null pointer argument");
+        return -1;
+    }
+    if (n_pre <= 0 || n_pre > 0x7fffffffL || n_join <= 0 || n_join > 0x7fffffffL || n_images <= 0 || n_members < 0 || n_members > 65535 ||
+        max_p < 0 || n_kv_heads <= 0 || n_kv_heads > 65535 || s_max <= 0 || batch <= 0) {
+        padt_set_error("padt_kv_prefix_fanout: bad dimensions");
+        return -1;
+    }
+    if (head_dim <= 0 || head_dim > 256 || (head_dim & 1)) { padt_set_error("padt_kv_prefix_fanout: head_dim must be even and <= 256"); return -1; }
+    const long kv = (long)n_kv_heads * head_dim;
+    if (ld_pre < kv || ld_kj < kv || ld_vj < kv) { padt_set_error("padt_kv_prefix_fanout: a row stride is shorter than its row"); return -1; }
+    if (cache_packed && ((head_dim & 31) || (s_max & 31))) { padt_set_error("padt_kv_prefix_fanout: packed caches need head_dim % 32 == 0 and s_max % 32 == 0"); return -1; }
+    if (n_members == 0 || max_p == 0) return 0;
+    KvPrefixFanoutArgs a{(const x16_t*)k_pre, (const x16_t*)v_pre, ld_pre, pre_off, mem_image, mem_row, mem_join, (x16_t*)k_cache, (x16_t*)vt_cache,
+                         (x16_t*)k_join, ld_kj, (x16_t*)v_join, ld_vj, (int)n_pre, n_images, n_kv_heads, head_dim, s_max, batch, (int)n_join,
+                         cache_packed ? 1 : 0, 0};
+    // the 16-byte path: whole chunks per head and per 8 slots of a row-major V^T row, 16-byte aligned rows of every operand
+    a.vec = (head_dim & 15) == 0 && (s_max & 7) == 0 && (ld_pre & 7) == 0 && (ld_kj & 7) == 0 && (ld_vj & 7) == 0 && ((uintptr_t)k_pre & 15) == 0 &&
+            ((uintptr_t)v_pre & 15) == 0 && ((uintptr_t)k_join & 15) == 0 && ((uintptr_t)v_join & 15) == 0 && ((uintptr_t)k_cache & 15) == 0 &&
+            ((uintptr_t)vt_cache & 15) == 0;
+    hipLaunchKernelGGL(kv_prefix_fanout_kernel, dim3((unsigned)((max_p + KVF_SLOTS - 1) / KVF_SLOTS), (unsigned)n_kv_heads, (unsigned)n_members),
+                       dim3(256), 0, (hipStream_t)stream, a);
+    PADT_CHECK_LAUNCH();
+    return 0;
+}
+
 #if !PADT_OP16_F16   // type-independent (or bf16-decoder-only): compiled once
 // ---------------------------------------------------------------------------------------------------------------------
 // PaDT mask head tail (padt_decoder.py:241-274) on bf16 operands: mask_scatter_kernel<x16_t>, common.h

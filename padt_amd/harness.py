@@ -8,7 +8,8 @@ post-processing (utils.py:252-266) and the two JSONL files with the reference's 
 Tokenisation / chat templating is the caller's (`prepare`): it needs the checkpoint's tokenizer files, which are not part of
 this repository.  `prepare(samples) -> dict(input_ids (local VRT ids), attention_mask, pixel_values, image_grid_thw,
 image_sizes [(w, h)], ids [image_id])`; optionally `image_index` (several samples on one image: generate(image_index=), with
-`pixel_values` / `image_grid_thw` holding each image once), `forced_tokens` (the batch's completion tokens to force:
+`pixel_values` / `image_grid_thw` holding each image once), `prefix` (a handle of model.encode_prefix the batch's rows continue:
+generate(prefix=), with `pixel_values` / `image_grid_thw` left out or `None`), `forced_tokens` (the batch's completion tokens to force:
 generate(forced_tokens=)), `patch_bias` (one entry per sample over its own patches: generate(patch_bias=)), `min_tokens` / `max_tokens`
 (one int per sample: generate(min_tokens=, max_tokens=)) and `frequency_penalty` / `presence_penalty` / `patch_suppression` (one entry per
 sample: generate()'s count edits).
@@ -63,6 +64,8 @@ def infer_dataset(model, processor, dataset: Sequence, prepare: Callable, output
         b = prepare(dataset[idx: idx + batch_size])
         meta.append({"ids": list(b["ids"]), "image_sizes": list(b["image_sizes"])})
         extra = {"image_index": b["image_index"]} if b.get("image_index") is not None else {}
+        if b.get("prefix") is not None:
+            extra["prefix"] = b["prefix"]
         extra["forced_tokens"] = b.get("forced_tokens")           # None: nothing forced
         extra["patch_bias"] = b.get("patch_bias")                 # None: no prior over the patches
         extra["min_tokens"] = b.get("min_tokens", min_tokens)     # the batch's own rows, else the run's value
@@ -70,7 +73,7 @@ def infer_dataset(model, processor, dataset: Sequence, prepare: Callable, output
         extra["frequency_penalty"] = b.get("frequency_penalty", frequency_penalty)
         extra["presence_penalty"] = b.get("presence_penalty", presence_penalty)
         extra["patch_suppression"] = b.get("patch_suppression", patch_suppression)
-        drain(runner.submit(b["input_ids"], b["attention_mask"], b["pixel_values"], b["image_grid_thw"],
+        drain(runner.submit(b["input_ids"], b["attention_mask"], b.get("pixel_values"), b.get("image_grid_thw"),
                             max_new_tokens=max_new_tokens, schedule=schedule, repetition_penalty=repetition_penalty,
                             eos_token_id=eos_token_id, token_automaton=token_automaton, logit_bias=logit_bias,
                             exponential_decay_length_penalty=exponential_decay_length_penalty, stop_sequences=stop_sequences, **extra))

@@ -141,6 +141,177 @@ class SharedPrompt:
     patch_rows: torch.Tensor         # (sum patches per sample,) int32: the same for the patch-level rows (high_res, visual_pe)
     grid_x: torch.Tensor             # (B, 3) image_grid_thw[image_index]
     dst_host: tuple = ()             # host copies of (dst_sample, dst_slot, dst_row) for check_shared_destinations
+    # generate(prefix=) (plan_prompt_prefix): no prefix segment is computed — the token set is the own tokens, and the handle's cached rows
+    # are put where the shared pass would have fanned them out (ops.kv_prefix_fanout), its hidden rows behind the token set's
+    prefix: Optional["PromptPrefix"] = None
+    prefix_len: tuple = ()           # per sample: the length P of its image's cached prefix
+    members: tuple = ()              # device int32 (mem_image, mem_row, mem_join): per sample its image, session row, first row of its key segment
+    max_p: int = 0
+
+
+@dataclass
+class PromptPrefix:
+    """What model.encode_prefix keeps of N images and the prompt rows in front of each query on them, for generate(prefix=) in later
+    calls: the ViT outputs every consumer downstream reads and, per LLM layer, the roped K rows and V rows of the prefix tokens — what the
+    join buffers of the shared prompt pass hold.  Image u's prefix has P = len(ids[u]) tokens, rows [off[u], off[u+1]) of ``hidden`` /
+    ``k[layer]`` / ``v[layer]``.  The handle owns its tensors and belongs to no session; nothing in a generate call writes to it."""
+    ids: List[List[int]]             # per image: the unpadded prefix ids, VRT ids in image-LOCAL numbering
+    grid: torch.Tensor               # (N, 3) int64, host
+    pos3: Optional[List[torch.Tensor]] = None      # per image (3, P) int32, host: mRoPE positions of the prefix
+    next_pos: Optional[List[int]] = None           # ... and the position after it
+    dtype: Optional[torch.dtype] = None            # the 16-bit operand type it was built with
+    low: Optional[torch.Tensor] = None             # (sum merged, D) merged rows
+    high: Optional[torch.Tensor] = None            # (sum patches, vh) fp32 patch-level rows
+    pe: Optional[tuple] = None                     # (cos, sin) (sum patches, hd): visual PE
+    proto: Optional[torch.Tensor] = None           # (sum merged, D) prototype rows
+    hidden: Optional[torch.Tensor] = None          # (sum P, D) last-layer post-norm rows of the prefix tokens
+    k: Optional[torch.Tensor] = None               # (layers, sum P, Hkv * hd) roped K rows
+    v: Optional[torch.Tensor] = None               # (layers, sum P, Hkv * hd) V rows
+    pre_off: Optional[torch.Tensor] = None         # (N + 1,) int32 on the device: ``off``
+    ready: object = None                           # event after which the tensors may be read
+    inputs: tuple = ()                             # (input_ids, attention_mask, pixel_values, image_grid_thw) it was built from
+    twin: Optional["PromptPrefix"] = None          # the bf16 build of an fp16 handle, made once when a call needs it (operands="auto")
+
+    @property
+    def n_images(self) -> int:
+        return len(self.ids)
+
+    @property
+    def lens(self) -> List[int]:
+        return [len(r) for r in self.ids]
+
+    @property
+    def off(self) -> List[int]:
+        o = [0]
+        for r in self.ids:
+            o.append(o[-1] + len(r))
+        return o
+
+    @property
+    def nbytes(self) -> int:
+        ts = [self.low, self.high, self.proto, self.hidden, self.k, self.v] + list(self.pe or ())
+        return sum(t.numel() * t.element_size() for t in ts if t is not None)
+
+    def image_k(self, u: int) -> torch.Tensor:
+        """[layer][P][Hkv * hd] roped K rows of image u's prefix (a view)."""
+        return self.k[:, self.off[u]: self.off[u + 1]]
+
+    def image_v(self, u: int) -> torch.Tensor:
+        return self.v[:, self.off[u]: self.off[u + 1]]
+
+
+def unpadded_rows(input_ids, attention_mask):
+    ids_cpu = input_ids.detach().cpu()
+    am = attention_mask.detach().cpu() if attention_mask is not None else torch.ones_like(ids_cpu)
+    return [ids_cpu[b][am[b] == 1].tolist() for b in range(ids_cpu.shape[0])]
+
+
+def plan_prefix_build(cfg: PaDTConfig, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], grid_thw: torch.Tensor,
+                      device) -> PromptPlan:
+    """The prompt pass model.encode_prefix runs: plan_prompt of the N prefix rows (row u = image u's prefix) with a token set whose every
+    destination is a join row only (dst_sample = -1) — ops.llm_qkv_post_shared then leaves the roped K rows and V rows in the handle's
+    layer slices, in packed row order, and touches no cache image."""
+    rows = unpadded_rows(input_ids, attention_mask)
+    grids = [[int(x) for x in r] for r in torch.as_tensor(grid_thw).tolist()]
+    if len(grids) != len(rows):
+        raise ValueError(f"encode_prefix takes one row per image: {len(rows)} rows, {len(grids)} images")
+    for u, (r, g) in enumerate(zip(rows, grids)):
+        n_tok, n_feat = r.count(cfg.image_token_id), g[0] * g[1] * g[2] // cfg.merge_unit
+        if n_tok != n_feat:
+            raise ValueError(f"encode_prefix: row {u} must contain the image tokens of image {u} completely: {n_tok} image tokens, "
+                             f"{n_feat} features")
+    plan = plan_prompt(cfg, input_ids, attention_mask, torch.tensor(grids, dtype=torch.long), device)
+    T = sum(plan.lens)
+    ar = torch.arange(T, dtype=I32)
+    none = torch.full((T,), -1, dtype=I32)
+    plan.shared = SharedPrompt(
+        n_images=len(grids), groups=[], prefix_of=[-1] * len(rows), ids=plan.ids, img_index=plan.img_index, pos3=plan.pos3,
+        dst_off=torch.arange(T + 1, dtype=I32).to(device), dst_sample=none.to(device), dst_slot=plan.slot, dst_row=ar.to(device), n_join=T,
+        cu_q=plan.cu, cu_k=plan.cu, max_q=max(plan.lens), unshare=ar.to(device), low_rows=None, patch_rows=None,
+        grid_x=torch.tensor(grids, dtype=torch.long), dst_host=(none, plan.slot.cpu(), ar))
+    return plan
+
+
+def check_prefix_rows(cfg: PaDTConfig, prefix: PromptPrefix, image_index, rows: List[List[int]]) -> List[int]:
+    """generate(prefix=): → the index as a list, after the host-side validation of the rows against the handle (ValueError)."""
+    B, N = len(rows), prefix.n_images
+    if image_index is None:
+        if B != N:
+            raise ValueError(f"generate(prefix=...) without image_index needs one row per image of the prefix: {B} rows, {N} images")
+        idx = list(range(B))
+    else:
+        idx = [int(i) for i in (image_index.detach().cpu().reshape(-1).tolist() if isinstance(image_index, torch.Tensor) else list(image_index))]
+    if len(idx) != B:
+        raise ValueError(f"image_index has {len(idx)} entries for a batch of {B} samples")
+    for b, u in enumerate(idx):
+        if not 0 <= u < N:
+            raise ValueError(f"image_index[{b}] = {u} is outside [0, {N}): the prefix holds {N} images")
+    merged = [int(g[0] * g[1] * g[2]) // cfg.merge_unit for g in prefix.grid.tolist()]
+    off = 0
+    for b, u in enumerate(idx):                                   # compared in image-local VRT numbering: the row's ids count the batch's patches
+        pre, V = prefix.ids[u], cfg.vocab_size
+        r = [t - off if t >= V else t for t in rows[b]]
+        n = 0
+        while n < min(len(r), len(pre)) and r[n] == pre[n]:
+            n += 1
+        if n < min(len(r), len(pre)):
+            raise ValueError(f"generate(prefix=...): row {b} does not start with the prefix of image {u}: first difference at position {n} "
+                             f"(id {r[n]}, the prefix has {pre[n]})")
+        if len(r) <= len(pre):
+            raise ValueError(f"generate(prefix=...): row {b} has no token of its own: it ends at position {len(r)}, the prefix of image {u} "
+                             f"has {len(pre)} tokens")
+        off += merged[u]
+    return idx
+
+
+def plan_prompt_prefix(cfg: PaDTConfig, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], prefix: PromptPrefix,
+                       image_index, device, row0: int = 0, proto_row0: int = 0) -> PromptPlan:
+    """plan_prompt_shared for rows whose prefixes are CACHED (generate(prefix=)): → the PromptPlan of the expanded inputs with ``shared``
+    describing the token set the pass computes — every sample's own tokens (those behind its image's prefix) and nothing else.  Sample b's
+    key segment is [prefix of its image | own tokens]; the prefix part of it, and slots [0, P) of its cache images, are filled from the
+    handle (``members``, ops.kv_prefix_fanout), so no destination of the token set names them.  ``unshare`` reads the prefix rows of the
+    unshared packed order behind the token set's rows: row Ts + off[u] + j is row j of image u's cached hidden rows."""
+    rows = unpadded_rows(input_ids, attention_mask)
+    B = len(rows)
+    idx = check_prefix_rows(cfg, prefix, image_index, rows)
+    grids = [[int(x) for x in r] for r in prefix.grid.tolist()]
+    base = plan_prompt(cfg, input_ids, attention_mask, torch.tensor([grids[u] for u in idx], dtype=torch.long), "cpu", row0=row0,
+                       proto_row0=proto_row0)
+    lens, cu = base.lens, base.cu.tolist()
+    P, p_off = [prefix.lens[u] for u in idx], prefix.off
+    merged = [g[0] * g[1] * g[2] // cfg.merge_unit for g in grids]
+    low_off, patch_off = [0], [0]
+    for g, n in zip(grids, merged):
+        low_off.append(low_off[-1] + n)
+        patch_off.append(patch_off[-1] + g[0] * g[1] * g[2])
+    low_rows = torch.cat([torch.arange(low_off[u], low_off[u + 1], dtype=I32) for u in idx])
+    patch_rows = torch.cat([torch.arange(patch_off[u], patch_off[u + 1], dtype=I32) for u in idx])
+    own = [lens[b] - P[b] for b in range(B)]
+    cu_q, cu_k = [0], [0]
+    for b in range(B):
+        cu_q.append(cu_q[-1] + own[b])
+        cu_k.append(cu_k[-1] + lens[b])
+    Ts = cu_q[-1]
+    src = torch.cat([torch.arange(cu[b] + P[b], cu[b] + lens[b], dtype=torch.int64) for b in range(B)])
+    dst_off, d_sample, d_slot, d_row = [0], [], [], []
+    unshare = torch.empty((cu[-1],), dtype=I32)
+    for b in range(B):
+        for j in range(own[b]):
+            d_sample.append(row0 + b), d_slot.append(P[b] + j), d_row.append(cu_k[b] + P[b] + j)
+            dst_off.append(len(d_sample))
+        unshare[cu[b]: cu[b] + P[b]] = torch.arange(Ts + p_off[idx[b]], Ts + p_off[idx[b]] + P[b], dtype=I32)
+        unshare[cu[b] + P[b]: cu[b] + lens[b]] = torch.arange(cu_q[b], cu_q[b + 1], dtype=I32)
+    t32 = lambda v: torch.tensor(v, dtype=I32).to(device)
+    base.shared = SharedPrompt(
+        n_images=len(grids), groups=[], prefix_of=[-1] * B, ids=base.ids[src].to(device), img_index=base.img_index[src].to(device),
+        pos3=base.pos3[:, src].contiguous().to(device), dst_off=t32(dst_off), dst_sample=t32(d_sample), dst_slot=t32(d_slot), dst_row=t32(d_row),
+        n_join=cu_k[-1], cu_q=t32(cu_q), cu_k=t32(cu_k), max_q=max(own), unshare=unshare.to(device), low_rows=low_rows.to(device),
+        patch_rows=patch_rows.to(device), grid_x=torch.tensor([grids[u] for u in idx], dtype=torch.long),
+        dst_host=tuple(torch.tensor(v, dtype=I32) for v in (d_sample, d_slot, d_row)), prefix=prefix, prefix_len=tuple(P),
+        members=(t32(idx), t32([row0 + b for b in range(B)]), t32(cu_k[:-1])), max_p=max(P))
+    for f in ("ids", "img_index", "pos3", "sample", "slot", "cu", "last_idx"):
+        setattr(base, f, getattr(base, f).to(device))
+    return base
 
 
 def check_image_index(cfg: PaDTConfig, image_index, B: int, rows: List[List[int]], grids: List[List[int]]) -> List[int]:
@@ -709,9 +880,11 @@ class LanguageModel:
             self._sessions[key] = s
         return s
 
-    def prefill(self, plan: PromptPlan, image_embeds: torch.Tensor, sess: DecodeSession, nf=None):
+    def prefill(self, plan: PromptPlan, image_embeds: torch.Tensor, sess: DecodeSession, nf=None, kv_out=None):
         """Packed prefill; fills the session's KV caches; returns the post-norm hidden states of all prompt tokens (T,D).
-        nf: int32 device flag set when a post-norm row is not finite (the residual stream absorbs every upstream inf / NaN)."""
+        nf: int32 device flag set when a post-norm row is not finite (the residual stream absorbs every upstream inf / NaN).
+        kv_out = (K, V), each (layers, n_join, Hkv * hd), with a shared plan: the join buffers of layer i ARE K[i] / V[i] (encode_prefix:
+        the prompt pass writes the handle's rows itself)."""
         cfg, W = self.cfg, self.W
         Hq, Hkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
         sh = plan.shared                                         # generate(image_index=): the smaller token set (plan_prompt_shared);
@@ -730,9 +903,10 @@ class LanguageModel:
         q = torch.empty((T, Hq * hd), device=dev, dtype=bf)
         if sh is None:
             kp = torch.empty((T, Hkv * hd), device=dev, dtype=bf)
-        else:                                                    # roped K / V rows of every key segment: [prefix] / [group prefix | own tokens]
+        elif kv_out is None:                                     # roped K / V rows of every key segment: [prefix] / [group prefix | own tokens]
             kj = torch.empty((sh.n_join, Hkv * hd), device=dev, dtype=bf)
             vj = torch.empty((sh.n_join, Hkv * hd), device=dev, dtype=bf)
+        pre = sh.prefix if sh is not None else None              # generate(prefix=): cached prefix rows instead of prefix segments
         att = torch.empty((T, Hq * hd), device=dev, dtype=bf)
         h = torch.empty((T, W.llm_ipad), device=dev, dtype=bf)
         mx = max(plan.lens)
@@ -759,6 +933,11 @@ class LanguageModel:
             else:
                 # a token is rotated once and fanned out to every member's cache images and key segment; a suffix's queries then see
                 # [group prefix | own tokens] under the bottom-right aligned causal mask (Lk > Lq), exactly the keys of its full row
+                if kv_out is not None:
+                    kj, vj = kv_out[0][i], kv_out[1][i]
+                if pre is not None:                              # the cached rows go where the shared pass would have fanned them out
+                    ops.kv_prefix_fanout(pre.k[i], pre.v[i], pre.pre_off, *sh.members, sh.max_p, sess.kc[i], sess.vtc[i], kj, vj, Hkv, hd,
+                                         sess.s_max, cache_packed=sess.cache_packed)
                 ops.llm_qkv_post_shared(qkv, sh.pos3, sess.inv_freq, q, sess.kc[i], sess.vtc[i], kj, vj, sh.dst_off, sh.dst_sample,
                                         sh.dst_slot, sh.dst_row, Hq, Hkv, hd, sess.s_max, cfg.mrope_section,
                                         cache_packed=sess.cache_packed)
@@ -783,5 +962,7 @@ class LanguageModel:
         if nf is not None:
             ops.check_finite(n, nf)
         if sh is not None:                                       # back to the unshared packed per-sample order every consumer reads
+            if pre is not None:                                  # the prefix rows of that order are the handle's
+                n = torch.cat([n, pre.hidden])
             n = ops.gather_rows(n, sh.unshare)
         return n

@@ -24,7 +24,8 @@ from .decoder import PaDTDecoder
 from .generation import (_GENERATE_CONFIG_NAMED, _GENERATE_CONFIG_OWN, check_decay_length_penalty, check_forced_tokens, check_generate_kwargs,  # noqa: F401
                          check_count_penalties, check_logit_bias, check_max_tokens, check_patch_suppression, check_min_tokens, check_patch_bias, check_stop_sequences, check_token_automaton, NO_BUDGET, check_top_logprobs, completion_logprobs, forced_tokens_active, generation_config_fields, resolve_options, with_warpers,
                          WARPER_NAMES)
-from .llm import MODE, LanguageModel, check_shared_destinations, plan_prompt, plan_prompt_shared
+from .llm import (MODE, LanguageModel, PromptPrefix, check_shared_destinations, plan_prefix_build, plan_prompt, plan_prompt_prefix,
+                  plan_prompt_shared, unpadded_rows)
 from .vision import VisionEncoder
 from .weights import Fp16RangeError, load_checkpoint_state_dict, prepare_weights, synthetic_state_dict
 
@@ -252,6 +253,14 @@ class PaDTForConditionalGeneration:
         image tokens, a repeated instruction) ONCE, fanning their K / V rows out to every member's cache.  Nothing is kept between calls.  Pass
         ``image_grid_thw[image_index]`` to ``vl_decode``.  Not available with ``precision="reference"``.
 
+        ``prefix`` (a keyword; the handle of ``encode_prefix``) keeps that sharing ACROSS calls: ``input_ids`` / ``attention_mask`` are the full
+        rows as for an ``image_index`` call, ``pixel_values`` / ``image_grid_thw`` must be ``None`` (``ValueError``), ``image_index[b]`` names the
+        handle's image for row b (default ``range(B)`` when B equals the handle's image count).  Every row must start with its image's prefix
+        (VRT ids compared in image-local numbering) and keep a token of its own — ``ValueError`` naming the row and the first differing
+        position.  The ViT does not run, the prompt pass computes the own tokens only (llm.plan_prompt_prefix; the cached K / V rows reach
+        the rows' cache images through ``padt_kv_prefix_fanout``), and the call returns what the ``image_index`` call returns; the handle is
+        not modified.  ``precision="reference"`` rejects it by name; HF's ``past_key_values`` stays rejected by name.
+
         ``no_repeat_ngram_size`` / ``bad_words_ids`` / ``suppress_tokens`` / ``begin_suppress_tokens`` (padt.py:570-580 → HF's NoRepeatNGram /
         NoBadWords / SuppressTokens / SuppressTokensAtBegin processors): pure bans, served ON THE DEVICE in every mode — one kernel per step
         builds each row's ban bitmap from its history (the padded prompt row and the tokens so far, VRT ids included) inside the captured step,
@@ -425,6 +434,7 @@ class PaDTForConditionalGeneration:
         decay = kwargs.pop("exponential_decay_length_penalty", None)
         stop_sequences, min_tokens, max_tokens = (kwargs.pop(k, None) for k in ("stop_sequences", "min_tokens", "max_tokens"))      # ... and how a row ends
         frequency_penalty, presence_penalty, patch_suppression = (kwargs.pop(k, None) for k in ("frequency_penalty", "presence_penalty", "patch_suppression"))      # ... and the count edits
+        prefix = kwargs.pop("prefix", None)                           # ... and the handle of encode_prefix
         if generation_config is not None:
             named = dict(max_new_tokens=max_new_tokens, max_length=max_length, do_sample=do_sample, repetition_penalty=repetition_penalty,
                          eos_token_id=eos_token_id, pad_token_id=pad_token_id, temperature=temperature, top_k=top_k, top_p=top_p,
@@ -480,6 +490,8 @@ class PaDTForConditionalGeneration:
         if frequency_penalty is not None or presence_penalty is not None or patch_suppression is not None:
             hooks = dict(hooks or {}, counts=dict(frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
                                                   patch_suppression=patch_suppression))
+        if prefix is not None:
+            hooks = dict(hooks or {}, prefix=prefix)
         if output_logits:
             pen = self.generation_config.repetition_penalty if repetition_penalty is None else repetition_penalty
             if float(pen) != 1.0 or schedule is not None or processors is not None:
@@ -538,6 +550,18 @@ class PaDTForConditionalGeneration:
         if hooks is not None and "warpers" in hooks:
             gen_cfg = with_warpers(gen_cfg, hooks["warpers"])
             hooks = {k: v for k, v in hooks.items() if k != "warpers"} or None
+        prefix = None
+        if hooks is not None and "prefix" in hooks:
+            prefix = hooks["prefix"]
+            hooks = {k: v for k, v in hooks.items() if k != "prefix"} or None
+            if prefix is not None:
+                if not isinstance(prefix, PromptPrefix):
+                    raise TypeError("generate(prefix=...) takes the handle encode_prefix returns (HF's past_key_values is not accepted)")
+                if pixel_values is not None or image_grid_thw is not None:
+                    raise ValueError("generate(prefix=...): the handle holds the images — pixel_values and image_grid_thw must be None")
+                if getattr(self, "precision", "default") == "reference":
+                    raise NotImplementedError("generate(prefix=...) is not implemented with precision='reference' (its prompt pass is its own: "
+                                              "reference.ReferencePath.prefill): pass the images or use precision='default'")
         forced = None
         if hooks is not None and "forced" in hooks:
             if hooks["forced"] is not None:                       # shape / dtype now; the id bound once the batch's patch count is known (_launch)
@@ -578,7 +602,10 @@ class PaDTForConditionalGeneration:
                                       "reference.ReferencePath.prefill): expand the inputs or use precision='default'")
         # operands="auto" whose checkpoint keeps overflowing fp16: new decode groups start on the bf16 twin (a group stays with its owner).  The
         # options resolve the same on either: the twin shares this model's generation_config and config
-        owner = group["owner"] if group is not None else (self.fallback_model() if self.prefers_bf16 else self)
+        # ... and so do those of a call whose prefix was built there (a flagged encode_prefix): its rows are bf16 rows
+        on_twin = self.prefers_bf16 or (prefix is not None and prefix.dtype == torch.bfloat16 and self.dtype == torch.float16
+                                        and self.operands == "auto")
+        owner = group["owner"] if group is not None else (self.fallback_model() if on_twin else self)
         opts = resolve_options(gen_cfg, self.config.eos_token_id, self.config.vocab_size, do_sample=do_sample,
                                repetition_penalty=repetition_penalty, eos_token_id=eos_token_id, temperature=temperature, top_k=top_k, top_p=top_p,
                                seed=seed, keep_scores=keep_scores, keep_logits=keep_logits, no_repeat_ngram_size=no_repeat_ngram_size,
@@ -610,24 +637,27 @@ class PaDTForConditionalGeneration:
         return owner._launch(opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, max_new_tokens=max_new_tokens,
                              schedule=schedule, hooks=hooks, sync_every=sync_every, use_graph=use_graph, lane=lane, decode_stream=decode_stream,
                              group=group, n_slots=n_slots, vit_stream=vit_stream, inputs_ready=inputs_ready, forced=forced, automaton=automaton,
-                             patch_bias=patch_bias, stop=stop, counts=counts)
+                             patch_bias=patch_bias, stop=stop, counts=counts, prefix=prefix)
 
     def _launch(self, opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, *, max_new_tokens, schedule, hooks, sync_every,
                 use_graph, lane, decode_stream, group, n_slots, vit_stream, inputs_ready, forced=None, automaton=None, patch_bias=None, stop=None,
-                counts=None):
+                counts=None, prefix=None):
         """generate_launch on the group's owner, with the call's options resolved (generation.GenOptions)."""
         self._batches_seen += 1
-        if pixel_values is None or image_grid_thw is None:
+        if prefix is None and (pixel_values is None or image_grid_thw is None):
             raise ValueError("pixel_values and image_grid_thw are required (text-only input crashes in the reference too, "
                              "padt.py:292 with image_prototypes unbound)")
         cfg, dev = self.config, self.device
-        grid = image_grid_thw.detach().cpu().long()
+        handle = None if prefix is None else self._prefix_for(prefix)       # the build in this model's operand type
+        grid = image_grid_thw.detach().cpu().long() if prefix is None else handle.grid
         B = input_ids.shape[0]
         T_max = int(max_new_tokens)
         k = 0 if group is None else len(group["subs"])
         row0 = k * B
         proto_row0 = 0 if group is None else group["proto_rows"]
-        if image_index is None:
+        if prefix is not None:
+            plan = plan_prompt_prefix(cfg, input_ids, attention_mask, handle, image_index, dev, row0=row0, proto_row0=proto_row0)
+        elif image_index is None:
             plan = plan_prompt(cfg, input_ids, attention_mask, grid, dev, row0=row0, proto_row0=proto_row0)
         else:
             plan = plan_prompt_shared(cfg, input_ids, attention_mask, grid, image_index, dev, row0=row0, proto_row0=proto_row0)
@@ -710,11 +740,18 @@ class PaDTForConditionalGeneration:
         # cur.wait_stream(vit_stream) below
         # The flag is slot k of the session's per-batch vector (read back with every other flag by ONE ops.collect_summary launch).
         nf = sess.nf_batch[k: k + 1]
-        if vit_stream is None or self.ref is not None:
+        if vit_stream is None or self.ref is not None or prefix is not None:
             nf.zero_()
 
         # ---- ViT → prototypes → session table
-        if self.ref is not None:
+        if prefix is not None:
+            # no ViT: every per-sample output is a device row copy of the handle's rows, on the current stream (they were checked when built)
+            if handle.ready is not None:
+                torch.cuda.current_stream().wait_event(handle.ready)
+            low, high = ops.gather_rows(handle.low, sh.low_rows), ops.gather_rows(handle.high, sh.patch_rows)
+            pe = (ops.gather_rows(handle.pe[0], sh.patch_rows), ops.gather_rows(handle.pe[1], sh.patch_rows))
+            proto = ops.gather_rows(handle.proto, sh.low_rows, out=sess.proto[proto_row0: proto_row0 + n_proto])
+        elif self.ref is not None:
             low, high, pe = self.ref.visual(pixel_values.to(dev), grid, nf=nf)
             proto = self.ref.prototypes(low, sess, proto_row0, nf=nf)     # fp32 rows (→ past_image_embeds); sess.proto gets their fp16 image
         elif vit_stream is None:
@@ -803,12 +840,90 @@ class PaDTForConditionalGeneration:
             ops.gather_rows(hn_all, plan.last_idx, out=sess.hn_first[rows])
         group["subs"].append(dict(plan=plan, low=low, high=high, pe=pe, proto=proto, hn_all=hn_all, input_ids=input_ids,
                                   n_proto=n_proto, row0=row0, proto_row0=proto_row0, nf=nf, p_max=p_max, forced=forced, automaton=automaton,
-                                  patch_bias=patch_bias, stop=stop, counts=counts,
+                                  patch_bias=patch_bias, stop=stop, counts=counts, prefix=prefix,
                                   inputs=(attention_mask, pixel_values, image_grid_thw, image_index)))       # what a re-run on the bf16 twin needs
         group["proto_rows"] = proto_row0 + n_proto
         if len(group["subs"]) == group["n_slots"]:
             self.launch_decode(group)
         return group
+
+    # ------------------------------------------------------------------ prompt prefixes kept across calls
+    @torch.no_grad()
+    def encode_prefix(self, input_ids, attention_mask, pixel_values, image_grid_thw) -> PromptPrefix:
+        """ViT pass and prompt pass of N images and the prompt rows in front of every query on them, kept for later calls:
+        ``generate(prefix=handle, image_index=[...])`` then computes each row's own tokens only.  Row u is the prompt up to wherever sharing
+        is to end; it must contain image u's image tokens completely (``ValueError``).  The handle (llm.PromptPrefix) owns what it holds —
+        merged / patch-level / PE / prototype rows, the prefix's last-layer hidden rows and, per LLM layer, its roped K rows and V rows in
+        this model's 16-bit operand type: 2 * layers * Hkv * head_dim * 2 bytes per prefix token (``handle.nbytes``) — and keeps the inputs
+        it was built from.  operands="auto": a build whose range guard fires is answered by the bf16 twin's (counted in
+        ``overflow_reruns``); calls with such a handle run on the twin.  Synchronises once (the guard's flag)."""
+        if getattr(self, "precision", "default") == "reference":
+            raise NotImplementedError("encode_prefix / generate(prefix=...) is not implemented with precision='reference' (its prompt pass is "
+                                      "its own: reference.ReferencePath.prefill)")
+        owner = self.fallback_model() if self.prefers_bf16 else self
+        h = owner._build_prefix(input_ids, attention_mask, pixel_values, image_grid_thw)
+        if h is None:
+            what = ("a non-finite value reached the ViT output / prototypes / post-norm hidden rows of a prompt prefix (%s MFMA operands)"
+                    % ("fp16" if owner.dtype == torch.float16 else "bf16"))
+            if owner is not self or self.operands != "auto" or self.dtype != torch.float16:
+                raise _lib.PaDTHipError(what)
+            import warnings
+            self.overflow_reruns += 1
+            warnings.warn("padt_amd: " + what + " — fp16 range exceeded; the prefix is built on the bf16-operand instantiation "
+                          "(%d so far)" % self.overflow_reruns, RuntimeWarning, stacklevel=2)
+            h = self.fallback_model()._build_prefix(input_ids, attention_mask, pixel_values, image_grid_thw)
+            if h is None:
+                raise _lib.PaDTHipError(what.replace("fp16", "bf16"))
+        return h
+
+    def _build_prefix(self, input_ids, attention_mask, pixel_values, image_grid_thw) -> Optional[PromptPrefix]:
+        """encode_prefix in THIS model's operand type: → the handle, or None when the range guard fired.  The kernels are generate()'s at the
+        same row counts — ViT, prototype projection, the prompt pass over the N rows — with one difference: the post-pass's only
+        destinations are the handle's own layer slices (llm.plan_prefix_build), so no session is involved."""
+        cfg, dev = self.config, self.device
+        grid = image_grid_thw.detach().cpu().long()
+        plan = plan_prefix_build(cfg, input_ids, attention_mask, grid, dev)
+        rows = unpadded_rows(input_ids, attention_mask)
+        V, cu = cfg.vocab_size, plan.cu.tolist()
+        ids = [[t - plan.vrt_off[u] if t >= V else t for t in r] for u, r in enumerate(rows)]
+        nf = torch.zeros(1, device=dev, dtype=torch.int32)
+        low, high, pe = self.visual(pixel_values.to(dev), grid, nf=nf)
+        proto = self.lm.prototypes(low, nf=nf)
+        nl, kv, hd = cfg.num_hidden_layers, cfg.num_key_value_heads * cfg.head_dim, cfg.head_dim
+        T = cu[-1]
+        K, Vr = (torch.empty((nl, T, kv), device=dev, dtype=self.dtype) for _ in range(2))
+        # what the prompt pass reads of a session: the prototype table, the id-range flag, the rope frequencies; the cache images are
+        # never written (every destination is a join row), one small block stands in for all of them
+        dummy = torch.zeros((1, cfg.num_key_value_heads, 64, hd), device=dev, dtype=self.dtype)
+        stub = SimpleNamespace(proto=proto, err=torch.zeros(1, device=dev, dtype=torch.int32), s_max=64, cache_packed=False,
+                               inv_freq=(1.0 / (cfg.rope_theta ** (torch.arange(0, hd, 2, dtype=torch.float) / hd))).to(dev),
+                               kc=[dummy] * nl, vtc=[dummy.view(1, cfg.num_key_value_heads, hd, 64)] * nl)
+        hidden = self.lm.prefill(plan, low, stub, nf=nf, kv_out=(K, Vr))
+        flags = torch.cat([stub.err, nf]).cpu().tolist()
+        if flags[0] != 0:
+            raise AssertionError("input_ids.max() >= extended table rows (padt.py:203)")
+        if flags[1] != 0:
+            return None
+        pos3 = plan.pos3.cpu()
+        keep = lambda t: t.detach().clone() if isinstance(t, torch.Tensor) else t
+        return PromptPrefix(ids=ids, grid=grid, pos3=[pos3[:, cu[u]: cu[u + 1]].clone() for u in range(len(rows))], next_pos=list(plan.next_pos),
+                            dtype=self.dtype, low=low, high=high, pe=pe, proto=proto, hidden=hidden, k=K, v=Vr,
+                            pre_off=torch.tensor(cu, dtype=torch.int32, device=dev), ready=torch.cuda.current_stream().record_event(),
+                            inputs=tuple(keep(t) for t in (input_ids, attention_mask, pixel_values, image_grid_thw)))
+
+    def _prefix_for(self, prefix: PromptPrefix) -> PromptPrefix:
+        """The build of the caller's handle in this model's operand type: the handle itself, or — the bf16 twin answering for an fp16
+        handle — its bf16 build, made once from the inputs the handle kept."""
+        if prefix.dtype == self.dtype:
+            return prefix
+        if prefix.dtype == torch.float16 and self.dtype == torch.bfloat16:
+            if prefix.twin is None:
+                prefix.twin = self._build_prefix(*prefix.inputs)
+                if prefix.twin is None:
+                    raise _lib.PaDTHipError("a non-finite value reached the rows of a prompt prefix (bf16 MFMA operands): NaN / inf weights or inputs?")
+            return prefix.twin
+        raise ValueError(f"generate(prefix=...): the prefix was built with {prefix.dtype} operands, this model multiplies {self.dtype} — "
+                         "build it with this model's encode_prefix")
 
     def _vit_and_prototypes(self, pixel_values, grid, proto_out, nf, sh):
         """ViT → prototypes into the session's table rows ``proto_out``, on the current stream: → (low, high, pe, proto).  With a shared plan
@@ -969,6 +1084,8 @@ class PaDTForConditionalGeneration:
             kw.update(token_automaton=sub["automaton"])           # the batch's automaton object: the options carry its key only
         if sub.get("patch_bias") is not None:
             kw.update(patch_bias=sub["patch_bias"])               # the batch's tensors: the options only say that there are some
+        if sub.get("prefix") is not None:
+            kw.update(prefix=sub["prefix"])                       # the caller's handle: the twin reads its bf16 build (made once, _prefix_for)
         return fb.generate(input_ids=sub["input_ids"], attention_mask=am, pixel_values=pix, image_grid_thw=grid, max_new_tokens=group["T_max"],
                            schedule=group["schedule"], sync_every=group["sync_every"], use_graph=group["use_graph"], lane=("fb", group["lane"]),
                            output_hidden_states=output_hidden_states, return_dict_in_generate=return_dict_in_generate, image_index=image_index, **kw)

@@ -719,6 +719,30 @@ def llm_qkv_post_shared(qkv, pos3, inv_freq, q_out, k_cache, vt_cache, k_join, v
                "padt_llm_qkv_post_shared")
 
 
+def kv_prefix_fanout(k_pre, v_pre, pre_off, mem_image, mem_row, mem_join, max_p, k_cache, vt_cache, k_join, v_join, n_kv_heads, head_dim,
+                     s_max, cache_packed=False):
+    """Cached prompt-prefix rows → cache images and join rows (padt_kv_prefix_fanout): k_pre / v_pre (n_pre, Hkv * D) are one layer's roped
+    K rows / V rows of the prefixes, image u at rows [pre_off[u], pre_off[u+1]); member m = (mem_image[m], mem_row[m], mem_join[m]) gets
+    them at slots [0, P) of session row mem_row[m] and join rows [mem_join[m], mem_join[m] + P).  max_p: the longest prefix (host int)."""
+    dt = _x16(k_pre, v_pre, k_cache, vt_cache, k_join, v_join)
+    kv = n_kv_heads * head_dim
+    assert k_pre.shape == v_pre.shape and k_pre.dim() == 2 and k_pre.shape[1] == kv and k_pre.stride(1) == v_pre.stride(1) == 1
+    assert k_pre.stride(0) == v_pre.stride(0)
+    assert k_join.shape == v_join.shape and k_join.shape[1] == kv and k_join.stride(1) == v_join.stride(1) == 1
+    assert k_cache.is_contiguous() and vt_cache.is_contiguous() and k_cache.numel() == vt_cache.numel()
+    assert k_cache.numel() % (kv * s_max) == 0
+    batch = k_cache.numel() // (kv * s_max)
+    for t in (pre_off, mem_image, mem_row, mem_join):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+    assert pre_off.numel() >= 2 and mem_image.numel() == mem_row.numel() == mem_join.numel()
+    # no alignment assertion: on a base that is not 16-byte aligned the entry point takes the kernel's scalar branch (same bits)
+    _lib.check(_fn("padt_kv_prefix_fanout", dt)(_stream(), _p(k_pre), _p(v_pre), k_pre.stride(0), k_pre.shape[0], _p(pre_off), pre_off.numel() - 1,
+                                                _p(mem_image), _p(mem_row), _p(mem_join), mem_image.numel(), int(max_p), _p(k_cache), _p(vt_cache),
+                                                _p(k_join), k_join.stride(0), _p(v_join), v_join.stride(0), k_join.shape[0], n_kv_heads, head_dim,
+                                                s_max, batch, 1 if cache_packed else 0),
+               "padt_kv_prefix_fanout")
+
+
 def mask_scatter(e2, mask_tok, cu_patch, obj_w, masks, n_obj, total_patches, dm):
     lib = _lib.load()
     _chk_bf16(e2, mask_tok)

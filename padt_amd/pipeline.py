@@ -22,11 +22,13 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
               schedule: Optional[Sequence] = None, need_thinking_mask=None, image_index=None, do_sample=False, min_p=None, typical_p=None,
               epsilon_cutoff=None, eta_cutoff=None, forced_tokens=None, token_automaton=None, logit_bias=None, patch_bias=None,
               exponential_decay_length_penalty=None, stop_sequences=None, min_tokens=None, max_tokens=None, frequency_penalty=None,
-              presence_penalty=None, patch_suppression=None, **gen_kw):
+              presence_penalty=None, patch_suppression=None, prefix=None, **gen_kw):
     """→ (decoded dict of vl_decode, completions, labels, vrts).  ``input_ids`` carries LOCAL VRT ids (as a processor
     emits them) and is updated in place exactly like the reference's callers do.
     ``image_index``: sample b asks about image image_index[b] of the N <= B images given (generate(image_index=)); everything per sample
     (VRT id ranges, vl_decode) then follows ``image_grid_thw[image_index]``.
+    ``prefix``: generate(prefix=) — a handle of model.encode_prefix; ``pixel_values`` / ``image_grid_thw`` are then ``None`` and the grids
+    are the handle's.
     ``do_sample`` (default: greedy, whatever the checkpoint's generation_config says) with ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` /
     ``eta_cutoff`` and, through ``**gen_kw``, ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: see generate().
     ``forced_tokens``: generate(forced_tokens=) — GLOBAL ids, numbered like the generated part of ``sequences``.
@@ -38,6 +40,9 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
     ``frequency_penalty`` / ``presence_penalty`` / ``patch_suppression``: generate()'s count edits (a value, or one per sample)."""
     B = input_ids.shape[0]
     grid_in = image_grid_thw
+    if prefix is not None:                                        # the handle's grids stand in for the caller's (generate() refuses both)
+        gen_kw = dict(gen_kw, prefix=prefix)
+        image_grid_thw = prefix.grid
     if image_index is not None:
         gen_kw = dict(gen_kw, image_index=image_index)
         image_grid_thw = sample_grids(image_grid_thw, image_index)
@@ -121,8 +126,9 @@ class PipelinedRunner:
                bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None, do_sample=False, min_p=None,
                typical_p=None, epsilon_cutoff=None, eta_cutoff=None, forced_tokens=None, token_automaton=None, logit_bias=None, patch_bias=None,
                exponential_decay_length_penalty=None, stop_sequences=None, min_tokens=None, max_tokens=None, frequency_penalty=None,
-               presence_penalty=None, patch_suppression=None, **sampling):
+               presence_penalty=None, patch_suppression=None, prefix=None, **sampling):
         """image_index: see generate(); the batch's results are those of the expanded batch.
+        prefix: generate(prefix=) — pixel_values / image_grid_thw are then None and the grids are the handle's; the batch's ViT stream is idle.
         do_sample (default: greedy) with min_p / typical_p / epsilon_cutoff / eta_cutoff and, through **sampling, temperature / top_k / top_p /
         seed: see generate(); batches whose resolved options differ in any of them (the seed included) do not share a decode group.
         output_token_logprobs / top_logprobs / output_patch_logprobs (through **sampling, see generate()): the decoded dict of the batch carries
@@ -140,12 +146,16 @@ class PipelinedRunner:
         bid = self.n_batches
         self.n_batches += 1
         grid_in = image_grid_thw                                  # the N images' grids (what the ViT sees)
+        if prefix is not None:
+            image_grid_thw = prefix.grid
         if image_index is not None:                               # ... and one grid per sample for everything downstream of the prompt pass
             image_grid_thw = sample_grids(image_grid_thw, image_index)
         ids = self.processor.assign_to_global_vrt_id(input_ids, image_grid_thw)
         sched = tuple(schedule) if schedule is not None else None
         warpers = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
         hooks = dict(warpers=warpers) if any(v is not None for v in warpers.values()) else {}
+        if prefix is not None:
+            hooks["prefix"] = prefix
         if forced_tokens is not None:
             hooks["forced"] = forced_tokens
         if token_automaton is not None:
