@@ -19,7 +19,7 @@ import torch
 
 from . import ops
 from .config import PaDTConfig
-from .generation import GenOptions, StepMode, decay_table, stop_table
+from .generation import NO_BUDGET, GenOptions, StepMode, decay_table, stop_table
 
 I32 = torch.int32
 
@@ -523,7 +523,7 @@ class DecodeSession:
         self.err = z(1, dt=I32)
         self.nf = z(B, dt=I32)           # per row: a decode step produced a non-finite hidden row (fp16 operand overflow; ops.check_finite)
         self.nf_batch = z(B, dt=I32)     # per batch of the decode group (slot k): ViT rows / prototypes / prompt-pass rows not finite
-        # generate_collect's ONE read-back per chunk (ops.collect_summary): [err, any unfinished, nf rows, nf batches, first EOS step per row]
+        # read_summary's ONE read-back per chunk (ops.collect_summary): [err, any unfinished, nf rows, nf batches, first EOS step per row]
         self.summary = z(2 + 3 * B, dt=I32)
         self.summary_host = torch.zeros(2 + 3 * B, dtype=I32).pin_memory() if torch.device(device).type == "cuda" else torch.zeros(2 + 3 * B, dtype=I32)
         # what this generate's step launches and keeps (generation.StepMode, set by begin()); the buffers below are allocated on first use
@@ -549,7 +549,7 @@ class DecodeSession:
         self.min_tok = self.max_tok = None       # ... each row's minimum and budget [B] ...
         self.finish_step = self.finish_reason = self.stop_index = None      # ... what padt_stop_match records per row [B] (-1 / 0 / -1: no finish yet) ...
         self.sban = None                 # ... the bitmap padt_stop_ban writes for the head (the rules' / the automaton's plus the EOS ids below min_tokens) [B][words] ...
-        self.summary_stop = self.summary_stop_host = None      # ... and generate_collect's read-back with the three finish arrays behind it
+        self.summary_stop = self.summary_stop_host = None      # ... and read_summary's read-back with the three finish arrays behind it
         self.cnt_text = None             # mode.counts (generate(frequency_penalty=, presence_penalty=, patch_suppression=)): how often each row generated a text column, uint16 [B][V padded to 4] ...
         self.cnt_patch = self.near = None        # ... how often a patch column was generated by its row, and the completed-run VRT tokens around each patch, uint16 [np_max] ...
         self.cpen = None                 # ... each row's f, p and suppression penalty fp32 [3][B] (0: off) ...
@@ -599,100 +599,195 @@ class DecodeSession:
         ops.check_finite(self.hn, self.nf, rows_per_flag=1, rows=B)      # sticky per-row flag, read once per generate (modeling.generate_collect)
         self.head_and_select(self.hn, advance=True)
 
-    def begin(self, opts: GenOptions, p_max: int = 0, processors: bool = False, step_fn=None, automaton=None, n_steps=None):
-        """Start of a generate with these options (p_max: the largest patch count of one sample; n_steps: the call's max_new_tokens, None = the session's t_max — the decay table is filled up to there; processors: the caller's logits_processor runs in
-        the hooked loop; step_fn: precision="reference"'s step): the gen_cfg slots and the rule table the captured step reads, the step mode,
-        and the log-prob buffers, allocated on first use and set to their finished-row values (0 / -1 / -inf) for every generate that asks.
+    def _own(self, name: str, shape, dtype, fill=0, reset: bool = True):
+        """The buffer `name` of an option that is on: allocated on first use (nothing is held for an option that is off) holding `fill`, and
+        at that address ever after — the captured graphs hold it.  Every later generate that asks starts from `fill` again; reset=False:
+        what a kernel or begin() writes in full before anything reads it keeps what it holds."""
+        t = getattr(self, name)
+        if t is None:
+            dev, shape = self.part_val.device, (shape,) if isinstance(shape, int) else tuple(shape)
+            t = torch.zeros(shape, device=dev, dtype=dtype) if fill == 0 else torch.full(shape, fill, device=dev, dtype=dtype)
+            setattr(self, name, t)
+        elif reset:
+            t.zero_() if fill == 0 else t.fill_(fill)
+        return t
+
+    def begin(self, opts: GenOptions, p_max: int = 0, processors: bool = False, step_fn=None, automaton=None, n_steps=None, schedule=None):
+        """Start of a generate — of a new decode group — with these options (p_max: the largest patch count of one sample; n_steps: the call's
+        max_new_tokens, None = the session's t_max — the mode table and the decay table are filled up to there; processors: the caller's
+        logits_processor runs in the hooked loop; step_fn: precision="reference"'s step; schedule: the forced token class per step, None =
+        every step free).  Sets the gen_cfg slots and the rule table the captured step reads and the step mode, puts every row into the
+        neutral state — finished, empty, no VRT range — that the group's batches overwrite for their own rows (add_batch), and sets the
+        buffers of the options that are on (_own) to their finished-row values (0 / -1 / -inf).
         top_logprobs uses the leading B * t_max * k elements of ONE flat (ids, values) pair sized for k = 32 as [B][t_max][k], so a captured
         step keeps its addresses and memory does not grow with the k values asked; the patch buffer grows, and the graphs captured over the
         smaller one go with it."""
         dev = self.part_val.device
+        B, t_max, F32 = self.B, self.t_max, torch.float32
+        T = t_max if n_steps is None else int(n_steps)
         self.gen_cfg.copy_(opts.gen_cfg().to(dev, non_blocking=True))
         self.mode, self.step_fn, self.hooks = opts.step_mode(processors, step_fn is not None), step_fn, None
         self.eos_ids = tuple(dict.fromkeys((int(self.cfg.eos_token_id),) + tuple(opts.eos_ids)))      # every id that finishes a row on the device
+        if opts.repetition_penalty != 1.0:
+            self.seen.zero_()
+        # neutral state for every row; the batches overwrite their own rows (unused rows stay finished / empty)
+        st = torch.zeros(T + 1, dtype=I32)
+        if schedule is not None:
+            for i, mm in enumerate(schedule[:T]):
+                st[i] = MODE[mm]
+        self.mode_table[: T + 1].copy_(st.to(dev, non_blocking=True))
+        for t in (self.step, self.err, self.unfinished, self.slot, self.pos3, self.vrt_off):
+            t.zero_()
+        self.lens.fill_(1)                                       # slot + 1, as for a filled row (add_batch): the keys visible to the next token of an empty prompt
+        self.cur_tok.fill_(self.cfg.pad_token_id)
+        if opts.sampling is not None:
+            self.batch_row0.zero_()                              # read by the sampling kernels alone
+        if step_fn is not None and (self.hid32 is None or self.hid32.shape[0] < T):      # reference precision keeps fp32 hidden rows per step
+            self.hid32 = torch.zeros((t_max, B, self.cfg.hidden_size), device=dev, dtype=F32)
         if opts.token_logprobs:
-            if self.logprobs is None:
-                self.part_sum = torch.zeros(self.nblk * self.B, device=dev, dtype=torch.float32)
-                self.logprobs = torch.zeros((self.B, self.t_max), device=dev, dtype=torch.float32)
-            else:
-                self.part_sum.zero_()
-                self.logprobs.zero_()
+            self._own("part_sum", self.nblk * B, F32)
+            self._own("logprobs", (B, t_max), F32)
         self.top_idx = self.top_val = None
         if opts.want_rows and self.topk_ws is None:
-            nbytes = ops.topk_rows_workspace(self.cfg.vocab_size + self.np_max, ops.TOPK_ROWS_MAX_K, self.B)
+            nbytes = ops.topk_rows_workspace(self.cfg.vocab_size + self.np_max, ops.TOPK_ROWS_MAX_K, B)
             self.topk_ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         if opts.top_logprobs:
             if self.top_flat is None:
-                n = self.B * self.t_max * ops.TOPK_ROWS_MAX_K
-                self.top_flat = (torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=torch.float32))
-            n = self.B * self.t_max * opts.top_logprobs
-            self.top_idx, self.top_val = (f[:n].view(self.B, self.t_max, opts.top_logprobs) for f in self.top_flat)
+                n = B * t_max * ops.TOPK_ROWS_MAX_K
+                self.top_flat = (torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=F32))
+            n = B * t_max * opts.top_logprobs
+            self.top_idx, self.top_val = (f[:n].view(B, t_max, opts.top_logprobs) for f in self.top_flat)
             self.top_idx.fill_(-1)
             self.top_val.fill_(float("-inf"))
         if opts.patch_logprobs:
             if self.patch_lp is None or self.p_cap < p_max:
                 self.graphs = {m: g for m, g in self.graphs.items() if not m.patches}      # their launches hold the old buffer's address
-                self.p_cap = max(int(p_max), 1)
-                self.patch_lp = torch.empty((self.B, self.t_max, self.p_cap), device=dev, dtype=torch.float32)
-            self.patch_lp.fill_(float("-inf"))
-        if opts.forced:                                          # every row free; each batch of the group fills its own rows (modeling._launch)
-            if self.forced is None:
-                self.forced = torch.empty((self.B, self.t_max), device=dev, dtype=I32)
-                self.probe_val = torch.zeros(self.B, device=dev, dtype=torch.float32)
-            self.forced.fill_(-1)
+                self.p_cap, self.patch_lp = max(int(p_max), 1), None
+            self._own("patch_lp", (B, t_max, self.p_cap), F32, float("-inf"))
+        if opts.forced:                                          # every row free; each batch of the group fills its own rows (add_batch)
+            self._own("forced", (B, t_max), I32, -1)
+            self._own("probe_val", B, F32, reset=False)
         if opts.automaton is not None:                           # `automaton`: the generation.TokenAutomaton whose key the options carry
             tab = ops.token_automaton_tensor(automaton, key=None if automaton is not None else opts.automaton)
-            if self.atab is None:
-                self.atab = torch.zeros(ops.TOKEN_AUTOMATON_INTS, device=dev, dtype=I32)
-                self.astate = torch.empty((self.B, 2), device=dev, dtype=I32)
-                self.aban = torch.zeros_like(self.ban)
-            self.atab[: tab.numel()].copy_(tab.to(dev, non_blocking=True))
-            self.astate.fill_(-1)                                # no row's state is valid: the first launch starts every row at the start state
-        if opts.score_bias:                                      # text columns and the decay now; each batch of the group adds its patch segment (modeling._launch)
-            if self.bias is None:
-                self.bias = torch.zeros(self.cfg.vocab_size + self.np_max, device=dev, dtype=torch.float32)
-                self.decay = torch.zeros(self.t_max, device=dev, dtype=torch.float32)
-            else:
-                self.bias.zero_()
+            self._own("atab", ops.TOKEN_AUTOMATON_INTS, I32, reset=False)[: tab.numel()].copy_(tab.to(dev, non_blocking=True))
+            self._own("astate", (B, 2), I32, -1)                 # no row's state is valid: the first launch starts every row at the start state
+            self._own("aban", self.ban.shape, I32, reset=False)
+        if opts.score_bias:                                      # text columns and the decay now; each batch of the group adds its patch segment (add_batch)
+            self._own("bias", self.cfg.vocab_size + self.np_max, F32)
+            self._own("decay", t_max, F32, reset=False)
             if opts.logit_bias is not None:
                 ids = torch.tensor([k for k, _ in opts.logit_bias], dtype=torch.long)
                 val = torch.tensor([v for _, v in opts.logit_bias], dtype=torch.float32)
                 self.bias.index_copy_(0, ids.to(dev), val.to(dev))
             self.decay.copy_(decay_table(opts.decay, self.t_max, n_steps).to(dev, non_blocking=True))
         if opts.stop:                                            # rows no batch of the group fills: min 0 (or the call's one value), budget t_max
-            if self.stab is None:
-                self.stab = torch.zeros(ops.STOP_RULES_INTS, device=dev, dtype=I32)
-                self.min_tok, self.max_tok, self.finish_step, self.finish_reason, self.stop_index = (
-                    torch.zeros(self.B, device=dev, dtype=I32) for _ in range(5))
-                self.sban = torch.zeros_like(self.ban)
-                self.summary_stop = torch.zeros(2 + 6 * self.B, device=dev, dtype=I32)
-                host = torch.zeros(2 + 6 * self.B, dtype=I32)
+            if self.summary_stop_host is None:
+                host = torch.zeros(2 + 6 * B, dtype=I32)
                 self.summary_stop_host = host.pin_memory() if torch.device(dev).type == "cuda" else host
-            self.stab.copy_(stop_table(opts.stop_sequences).to(dev, non_blocking=True))
-            self.min_tok.fill_(opts.min_tokens or 0)
-            self.max_tok.fill_(self.t_max)
-            self.finish_step.fill_(-1)
-            self.finish_reason.zero_()
-            self.stop_index.fill_(-1)
+            self._own("summary_stop", 2 + 6 * B, I32, reset=False)
+            self._own("stab", ops.STOP_RULES_INTS, I32, reset=False).copy_(stop_table(opts.stop_sequences).to(dev, non_blocking=True))
+            self._own("sban", self.ban.shape, I32, reset=False)
+            self._own("min_tok", B, I32, opts.min_tokens or 0)
+            self._own("max_tok", B, I32, t_max)
+            self._own("finish_step", B, I32, -1)
+            self._own("finish_reason", B, I32)
+            self._own("stop_index", B, I32, -1)
         if opts.counts:                                          # nothing generated yet; rows no batch of the group fills: no penalty, no suppression
-            if self.cnt_text is None:
-                V = self.cfg.vocab_size
-                self.cnt_text = torch.zeros((self.B, (V + 3) // 4 * 4), device=dev, dtype=ops.COUNT_DTYPE)
-                self.cnt_patch = torch.zeros(self.np_max, device=dev, dtype=ops.COUNT_DTYPE)
-                self.near = torch.zeros(self.np_max, device=dev, dtype=ops.COUNT_DTYPE)
-                self.cpen = torch.zeros((3, self.B), device=dev, dtype=torch.float32)
-                self.cgrid = torch.zeros((self.B, 2), device=dev, dtype=I32)
-                self.cradius = torch.zeros(self.B, device=dev, dtype=I32)
-            else:
-                self.cnt_text.zero_()
-                self.cnt_patch.zero_()
-                self.near.zero_()
-                self.cpen.zero_()
-                self.cgrid.zero_()
-            self.cradius.fill_(-1)
+            self._own("cnt_text", (B, (self.cfg.vocab_size + 3) // 4 * 4), ops.COUNT_DTYPE)
+            self._own("cnt_patch", self.np_max, ops.COUNT_DTYPE)
+            self._own("near", self.np_max, ops.COUNT_DTYPE)
+            self._own("cpen", (3, B), F32)
+            self._own("cgrid", (B, 2), I32)
+            self._own("cradius", B, I32, -1)
         if opts.rules is not None:
             self.rules.copy_(ops.gen_rules_tensor(key=opts.rules).to(dev, non_blocking=True))
             self.hist_len.zero_()                                # rows no batch of the group fills: an empty prompt
+
+    def add_batch(self, opts: GenOptions, row0: int, proto_row0: int, vrt_off, lens, next_pos, prompt_ids=None, forced=None, stop=None,
+                  counts=None, count_grids=None, patch_bias=None):
+        """The per-generate device state of one batch's rows, after begin(): rows [row0, row0 + B) for B = len(lens), whose prototype rows
+        start at proto_row0 of the session's table.  All values are the batch's own and already validated (modeling._launch): vrt_off —
+        its B + 1 patch offsets from 0; lens / next_pos — each row's prompt length and next rope position; prompt_ids (opts.reads_prompt) —
+        the caller's padded (B, L) ids on the session's device; forced — its int table (B, n <= t_max), -1 = free; stop — dict(min_tokens=,
+        max_tokens=) of per-row lists or None; counts — dict(frequency_penalty=, presence_penalty=, patch_suppression=) of per-row lists or
+        None, with count_grids, each row's merged patch grid (hp, wp); patch_bias — per row a tensor over its patches or None.  VRT ids of
+        the batch's own numbering (>= vocab) become session columns: + proto_row0."""
+        cfg, dev = self.cfg, self.part_val.device
+        B, V, n_proto = len(lens), cfg.vocab_size, vrt_off[-1]
+        rows = slice(row0, row0 + B)
+        up = lambda v, dt=I32: torch.tensor(v, dtype=dt).to(dev, non_blocking=True)
+        shift = lambda ids: torch.where(ids >= V, ids + proto_row0, ids) if proto_row0 else ids
+        self.vrt_off[row0: row0 + B + 1].copy_(up([proto_row0 + o for o in vrt_off]))
+        if row0 + B + 1 < self.vrt_off.numel():
+            self.vrt_off[row0 + B + 1:].fill_(proto_row0 + n_proto)     # rows not (yet) in use: empty VRT range
+        if opts.sampling is not None:
+            self.batch_row0[rows].fill_(row0)
+        self.unfinished[rows].fill_(1)
+        lens_t = torch.tensor(lens, dtype=I32)
+        self.slot[rows].copy_(lens_t.to(dev, non_blocking=True))        # next append index
+        self.lens[rows].copy_((lens_t + 1).to(dev, non_blocking=True))  # keys visible to the next token
+        self.pos3[:, rows].copy_(up([next_pos] * 3))
+        if opts.reads_prompt:
+            ids_full = shift(prompt_ids)                          # HF's logits processors see the caller's full (B, L) input_ids, padding included
+        if opts.repetition_penalty != 1.0:
+            rws = (torch.arange(B, device=dev, dtype=I32) + row0)[:, None].expand(B, ids_full.shape[1]).contiguous()
+            ops.seen_init(ids_full.reshape(-1).contiguous(), rws.reshape(-1), self.seen)
+        if opts.rules is not None:
+            self.hist[rows, : ids_full.shape[1]].copy_(ids_full)  # int64 → int32 (ids are table rows)
+            self.hist_len[rows].fill_(ids_full.shape[1])
+        if forced is not None:
+            # this batch's rows of the session's table, in session numbering like the prompt history; the steps past n stay free (-1: begin())
+            self.forced[rows, : forced.shape[1]].copy_(shift(forced).to(dev, non_blocking=True))
+        if opts.stop:
+            # this batch's rows of the session's minima and budgets (begin() set every row to the call's one minimum and to the budget of a
+            # row no batch fills): its own lists, or no budget at all — such a row ends on EOS, a stop sequence or the call's max_new_tokens
+            lim = stop or {}
+            if lim.get("min_tokens") is not None:
+                self.min_tok[rows].copy_(up(lim["min_tokens"]))
+            if lim.get("max_tokens") is not None:
+                self.max_tok[rows].copy_(up(lim["max_tokens"]))
+            else:
+                self.max_tok[rows].fill_(NO_BUDGET)
+        if opts.counts:
+            # this batch's rows of the session's penalties, grids and radii (begin() zeroed the tables and switched every row off)
+            cv = counts or {}
+            supp = cv.get("patch_suppression") or [None] * B
+            self.cpen[:, rows].copy_(up([cv.get("frequency_penalty") or [0.0] * B, cv.get("presence_penalty") or [0.0] * B,
+                                         [0.0 if e is None else e[1] for e in supp]], torch.float32))
+            self.cgrid[rows].copy_(up(count_grids))
+            self.cradius[rows].copy_(up([-1 if e is None else e[0] for e in supp]))
+        if patch_bias is not None:
+            # this batch's segment of the session's bias vector: its own prototype rows (begin() zero-filled the vector; a row without an entry adds 0)
+            seg = torch.zeros(n_proto, dtype=torch.float32)
+            for b, pb in enumerate(patch_bias):
+                if pb is not None:
+                    seg[vrt_off[b]: vrt_off[b + 1]] = pb.reshape(-1)
+            c0 = V + proto_row0
+            self.bias[c0: c0 + n_proto].copy_(seg.to(dev, non_blocking=True))
+
+    def read_summary(self, done: int, n_batches: int) -> dict:
+        """Everything the host needs from the device after `done` steps of a group of n_batches — ONE launch (ops.collect_summary, with stop
+        rules ops.collect_summary_stop: the same record with the rows' finish arrays behind it), ONE pinned device-to-host copy, ONE
+        synchronise — by name: err (the table-range flag), unfinished (any row), nf_rows [B] / nf_batch [n_batches] (the range guard's
+        flags), first_eos [B] (each row's first EOS step, -1: none) and, with stop rules, finish_step / finish_reason / stop_index [B]."""
+        B, eos = self.B, self.cfg.eos_token_id
+        if self.mode.stop:
+            ops.collect_summary_stop(self.err, self.unfinished, self.nf, self.nf_batch, n_batches, self.tokens, done, eos, self.gen_cfg,
+                                     self.finish_step, self.finish_reason, self.stop_index, self.summary_stop)
+            dst, host = self.summary_stop, self.summary_stop_host
+        else:
+            ops.collect_summary(self.err, self.unfinished, self.nf, self.nf_batch, n_batches, self.tokens, done, eos, self.gen_cfg, self.summary)
+            dst, host = self.summary, self.summary_host
+        host.copy_(dst, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        rec = host.tolist()
+        # the record's words: [err, any unfinished, nf rows [B], nf batches [n_batches], first EOS [B]] (+ the three finish arrays [B] each)
+        o = 2 + B + n_batches
+        out = dict(err=rec[0], unfinished=rec[1], nf_rows=rec[2: 2 + B], nf_batch=rec[2 + B: o], first_eos=rec[o: o + B])
+        if self.mode.stop:
+            names = ("finish_step", "finish_reason", "stop_index")
+            out.update({nm: rec[o + (i + 1) * B: o + (i + 2) * B] for i, nm in enumerate(names)})
+        return out
 
     def head_and_select(self, hn, advance: bool):
         cfg, W = self.cfg, self.W

@@ -22,9 +22,9 @@ from . import _lib, ops
 from .config import PaDTConfig
 from .decoder import PaDTDecoder
 from .generation import (_GENERATE_CONFIG_NAMED, _GENERATE_CONFIG_OWN, check_decay_length_penalty, check_forced_tokens, check_generate_kwargs,  # noqa: F401
-                         check_count_penalties, check_logit_bias, check_max_tokens, check_patch_suppression, check_min_tokens, check_patch_bias, check_stop_sequences, check_token_automaton, NO_BUDGET, check_top_logprobs, completion_logprobs, forced_tokens_active, generation_config_fields, resolve_options, with_warpers,
+                         check_count_penalties, check_logit_bias, check_max_tokens, check_patch_suppression, check_min_tokens, check_patch_bias, check_stop_sequences, check_token_automaton, check_top_logprobs, completion_logprobs, forced_tokens_active, generation_config_fields, resolve_options, with_warpers,
                          WARPER_NAMES)
-from .llm import (MODE, LanguageModel, PromptPrefix, check_shared_destinations, plan_prefix_build, plan_prompt, plan_prompt_prefix,
+from .llm import (LanguageModel, PromptPrefix, check_shared_destinations, plan_prefix_build, plan_prompt, plan_prompt_prefix,
                   plan_prompt_shared, unpadded_rows)
 from .vision import VisionEncoder
 from .weights import Fp16RangeError, load_checkpoint_state_dict, prepare_weights, synthetic_state_dict
@@ -694,9 +694,10 @@ class PaDTForConditionalGeneration:
             group = dict(sess=sess, subs=[], proto_rows=0, B=B, n_slots=n_slots, T_max=T_max, sync_every=sync_every,
                          use_graph=use_graph, decode_stream=decode_stream, done=0, launched=False, schedule=schedule,
                          opts=opts, lane=lane, owner=self)
-            # reference precision: eager split-precision steps (+ fp32 hidden rows, below)
+            # every row neutral and the options' buffers reset; the batches write their own rows (add_batch below).  Reference precision:
+            # eager split-precision steps and fp32 hidden rows
             sess.begin(opts, p_max, processors=bool(hooks and hooks["processors"]), step_fn=self.ref.step if self.ref is not None else None,
-                       automaton=automaton, n_steps=T_max)
+                       automaton=automaton, n_steps=T_max, schedule=schedule)
             if hooks is not None:
                 ids_dev = input_ids.detach().to(dev).long().contiguous()
                 hk = dict(hooks, B=B, table_rows=cfg.vocab_size + n_proto, t=0)
@@ -704,26 +705,6 @@ class PaDTForConditionalGeneration:
                 hk["sequences"] = lambda hk=hk, s=sess: ops.assemble_sequences(ids_dev, s.tokens[:B], hk["t"], cfg.vocab_size, 0)
                 sess.hooks = hk
                 group["hooks"] = hooks
-            if opts.repetition_penalty != 1.0:
-                sess.seen.zero_()
-            # neutral state for every row; the batches overwrite their own rows (unused rows stay finished / empty)
-            st = torch.zeros(T_max + 1, dtype=torch.int32)
-            if schedule is not None:
-                for i, mm in enumerate(schedule[: T_max]):
-                    st[i] = MODE[mm]
-            sess.mode_table[: T_max + 1].copy_(st.to(dev, non_blocking=True))
-            sess.step.zero_()
-            sess.err.zero_()
-            sess.unfinished.zero_()
-            sess.slot.zero_()
-            sess.lens.fill_(1)
-            sess.pos3.zero_()
-            sess.cur_tok.fill_(cfg.pad_token_id)
-            sess.vrt_off.zero_()
-            if opts.sampling is not None:
-                sess.batch_row0.zero_()                           # read by the sampling kernels alone
-            if self.ref is not None and (sess.hid32 is None or sess.hid32.shape[0] < T_max):
-                sess.hid32 = torch.zeros((sess.t_max, sess.B, cfg.hidden_size), device=dev, dtype=torch.float32)
         else:
             sess = group["sess"]
             if (group["launched"] or k >= group["n_slots"] or B != group["B"] or T_max != group["T_max"]
@@ -773,62 +754,11 @@ class PaDTForConditionalGeneration:
                 t_.record_stream(cur)
                 if decode_stream is not None:
                     t_.record_stream(decode_stream)
-        # ---- per-generate device state of this batch's rows
-        off = torch.tensor([proto_row0 + o for o in plan.vrt_off], dtype=torch.int32)
-        sess.vrt_off[row0: row0 + B + 1].copy_(off.to(dev, non_blocking=True))
-        if row0 + B + 1 < sess.vrt_off.numel():
-            sess.vrt_off[row0 + B + 1:].fill_(proto_row0 + n_proto)     # rows not (yet) in use: empty VRT range
-        if opts.sampling is not None:
-            sess.batch_row0[rows].fill_(row0)
-        sess.unfinished[rows].fill_(1)
-        lens_t = torch.tensor(plan.lens, dtype=torch.int32)
-        sess.slot[rows].copy_(lens_t.to(dev, non_blocking=True))        # next append index
-        sess.lens[rows].copy_((lens_t + 1).to(dev, non_blocking=True))  # keys visible to the next token
-        sess.pos3[:, rows].copy_(torch.tensor([plan.next_pos] * 3, dtype=torch.int32).to(dev, non_blocking=True))
+        # ---- per-generate device state of this batch's rows (the session writes its own buffers: DecodeSession.add_batch)
+        sess.add_batch(opts, row0, proto_row0, plan.vrt_off, plan.lens, plan.next_pos,
+                       prompt_ids=input_ids.detach().to(dev).long() if opts.reads_prompt else None, forced=forced, stop=stop, counts=counts,
+                       count_grids=count_grids, patch_bias=patch_bias)
         self.rope_deltas = plan.rope_deltas
-        if opts.reads_prompt:
-            # HF's logits processors see the caller's full (B, L) input_ids, padding included
-            ids_full = input_ids.detach().to(dev).long()
-            if proto_row0:
-                ids_full = torch.where(ids_full >= cfg.vocab_size, ids_full + proto_row0, ids_full)
-        if opts.repetition_penalty != 1.0:
-            rws = (torch.arange(B, device=dev, dtype=torch.int32) + row0)[:, None].expand(B, ids_full.shape[1]).contiguous()
-            ops.seen_init(ids_full.reshape(-1).contiguous(), rws.reshape(-1), sess.seen)
-        if opts.rules is not None:
-            sess.hist[rows, : plan.L_pad].copy_(ids_full)         # int64 → int32 (ids are table rows)
-            sess.hist_len[rows].fill_(plan.L_pad)
-        if forced is not None:
-            # this batch's rows of the session's table, in session numbering like the prompt history; the steps past n stay free (-1: begin())
-            tab = torch.where(forced >= cfg.vocab_size, forced + proto_row0, forced) if proto_row0 else forced
-            sess.forced[rows, : tab.shape[1]].copy_(tab.to(dev, non_blocking=True))
-        if opts.stop:
-            # this batch's rows of the session's minima and budgets (begin() set every row to the call's one minimum and to the budget of a
-            # row no batch fills): its own lists, or no budget at all — such a row ends on EOS, a stop sequence or the call's max_new_tokens
-            lim = stop or {}
-            if lim.get("min_tokens") is not None:
-                sess.min_tok[rows].copy_(torch.tensor(lim["min_tokens"], dtype=torch.int32).to(dev, non_blocking=True))
-            if lim.get("max_tokens") is not None:
-                sess.max_tok[rows].copy_(torch.tensor(lim["max_tokens"], dtype=torch.int32).to(dev, non_blocking=True))
-            else:
-                sess.max_tok[rows].fill_(NO_BUDGET)
-        if opts.counts:
-            # this batch's rows of the session's penalties, grids and radii (begin() zeroed the tables and switched every row off): its own
-            # values and the grids checked above
-            cv = counts or {}
-            supp = cv.get("patch_suppression") or [None] * B
-            pen = torch.tensor([cv.get("frequency_penalty") or [0.0] * B, cv.get("presence_penalty") or [0.0] * B,
-                                [0.0 if e is None else e[1] for e in supp]], dtype=torch.float32)
-            sess.cpen[:, rows].copy_(pen.to(dev, non_blocking=True))
-            sess.cgrid[rows].copy_(torch.tensor(count_grids, dtype=torch.int32).to(dev, non_blocking=True))
-            sess.cradius[rows].copy_(torch.tensor([-1 if e is None else e[0] for e in supp], dtype=torch.int32).to(dev, non_blocking=True))
-        if patch_bias is not None:
-            # this batch's segment of the session's bias vector: its own prototype rows (begin() zero-filled the vector; a row without an entry adds 0)
-            seg = torch.zeros(n_proto, dtype=torch.float32)
-            for b, pb in enumerate(patch_bias):
-                if pb is not None:
-                    seg[plan.vrt_off[b]: plan.vrt_off[b + 1]] = pb.reshape(-1)
-            c0 = cfg.vocab_size + proto_row0
-            sess.bias[c0: c0 + n_proto].copy_(seg.to(dev, non_blocking=True))
 
         # ---- prefill; the first token is selected together with the other batches of the group (launch_decode)
         if self.ref is not None:
@@ -966,40 +896,26 @@ class PaDTForConditionalGeneration:
         """Synchronising half of generate(): remaining decode chunks, trimming to the reference's stop rule, output object — of the group's only
         batch, or a list over its batches.  Everything the host needs from the device per chunk — the table-range assert (padt.py:203), `any
         row unfinished`, the range guard's per-row / per-batch flags, each row's first EOS step — comes from ONE kernel + ONE pinned D2H copy
-        (ops.collect_summary; round 6: no ATen reductions, no `.item()` round trips)."""
+        (DecodeSession.read_summary over ops.collect_summary; round 6: no ATen reductions, no `.item()` round trips)."""
         if group["owner"] is not self:
             return group["owner"].generate_collect(group, output_hidden_states, return_dict_in_generate, all_batches, output_scores, output_logits)
         cfg, dev = self.config, self.device
         self.launch_decode(group)
         sess, T_max, opts = group["sess"], group["T_max"], group["opts"]
-        n_rows, n_sub = sess.B, len(group["subs"])
-
-        def summary(done):
-            if opts.stop:                                         # the same launch and copy, with the rows' finish records behind the record
-                ops.collect_summary_stop(sess.err, sess.unfinished, sess.nf, sess.nf_batch, n_sub, sess.tokens, done, cfg.eos_token_id, sess.gen_cfg,
-                                         sess.finish_step, sess.finish_reason, sess.stop_index, sess.summary_stop)
-                sess.summary_stop_host.copy_(sess.summary_stop, non_blocking=True)
-                torch.cuda.current_stream().synchronize()
-                return sess.summary_stop_host.tolist()
-            ops.collect_summary(sess.err, sess.unfinished, sess.nf, sess.nf_batch, n_sub, sess.tokens, done, cfg.eos_token_id, sess.gen_cfg, sess.summary)
-            sess.summary_host.copy_(sess.summary, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            return sess.summary_host.tolist()
+        n_sub = len(group["subs"])
         done_steps = group["done"]
-        flags = summary(done_steps)
-        while done_steps < T_max and flags[1]:
+        rec = sess.read_summary(done_steps, n_sub)
+        while done_steps < T_max and rec["unfinished"]:
             n = min(group["sync_every"], T_max - done_steps)
             sess.run_steps(n, use_graph=group["use_graph"])
             done_steps += n
-            flags = summary(done_steps)
+            rec = sess.read_summary(done_steps, n_sub)
         group["done"] = done_steps
-        if flags[0] != 0:
+        if rec["err"] != 0:
             raise AssertionError("input_ids.max() >= extended table rows (padt.py:203)")
-        nf_rows, nf_batch = flags[2: 2 + n_rows], flags[2 + n_rows: 2 + n_rows + n_sub]
-        first_eos = flags[2 + n_rows + n_sub: 2 + 2 * n_rows + n_sub]
+        nf_rows, nf_batch, first_eos = rec["nf_rows"], rec["nf_batch"], rec["first_eos"]
         if opts.stop:                                             # a row's end is what padt_stop_match (or the hooked loop) recorded, whatever ended it
-            o = 2 + 2 * n_rows + n_sub
-            fin_step, fin_reason, fin_index = flags[o: o + n_rows], flags[o + n_rows: o + 2 * n_rows], flags[o + 2 * n_rows: o + 3 * n_rows]
+            fin_step, fin_reason, fin_index = rec["finish_step"], rec["finish_reason"], rec["stop_index"]
         outs = []
         for k_sub, sub in enumerate(group["subs"]):
             plan, row0, B = sub["plan"], sub["row0"], group["B"]

@@ -24,34 +24,20 @@ mode in turn (the modes alternate, so drift of the machine hits them alike).  Pe
 window's value.  Prints one JSON line per (rows, mode).
 
 usage: python tools/bench_forced_tokens.py [--rows 8,64] [--modes plain,logprobs,forced,forced_lp,forced_scores,forced_rows] [--operands fp16|bf16]"""
-import argparse
-import dataclasses
-import json
 import os
-import statistics
 import sys
-
-import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from padt_amd import config  # noqa: E402
+import dataclasses  # noqa: E402
+import statistics  # noqa: E402
+
+import torch  # noqa: E402
+
 from padt_amd.generation import GenOptions, Sampling  # noqa: E402
-from padt_amd.llm import DecodeSession  # noqa: E402
-from padt_amd.weights import _pad_to  # noqa: E402
-from bench_decode_weights import build_weights  # noqa: E402
+from step_bench import StepBench, main, parser  # noqa: E402
 
 MODES = ("plain", "logprobs", "forced", "forced_lp", "forced_scores", "forced_rows", "row_kernels")
-
-
-def set_mode(sess, mode, table):
-    opts = GenOptions(keep_scores=mode == "forced_scores", token_logprobs=mode in ("logprobs", "forced_lp", "forced_scores", "forced_rows"),
-                      sampling=Sampling(1.0, 50, 1.0, 7) if mode == "forced_rows" else None)
-    if mode.startswith("forced"):
-        opts = dataclasses.replace(opts, forced=True)
-    sess.begin(opts)
-    if mode.startswith("forced"):
-        sess.forced.copy_(table)
 
 
 def time_row_kernels(sess, cfg, rows, table, args):
@@ -79,54 +65,28 @@ def time_row_kernels(sess, cfg, rows, table, args):
 
 def time_rows(cfg, rows, op16, modes, args, device):
     row_kernels, modes = "row_kernels" in modes, [m for m in modes if m != "row_kernels"]
-    W, wbytes = build_weights(cfg, "bf16", op16, device)
-    window = max(args.steps, args.warmup)
-    sess = DecodeSession(cfg, W, rows, _pad_to(args.context + window + 1, 64), 16, window + 1, device)
-    gen = torch.Generator(device=device).manual_seed(1)
-    first = torch.randint(0, cfg.vocab_size, (rows,), generator=gen, device=device)
-    table = torch.randint(0, min(cfg.vocab_size, cfg.image_token_id), (rows, sess.t_max), generator=gen, device=device).to(torch.int32)
+    bench = StepBench(cfg, rows, op16, args, device)
+    sess = bench.sess
+    table = torch.randint(0, min(cfg.vocab_size, cfg.image_token_id), (rows, sess.t_max), generator=bench.gen, device=device).to(torch.int32)
 
-    def reset():
-        """`context` cached tokens per row, step counter at zero: every window replays the same steps (never past s_max / t_max)"""
-        sess.step.zero_()
-        sess.unfinished.fill_(1)
-        sess.cur_tok.copy_(first)
-        sess.slot.fill_(args.context)
-        sess.lens.fill_(args.context)
-        sess.pos3.fill_(args.context)
+    def set_mode(mode):
+        opts = GenOptions(keep_scores=mode == "forced_scores", token_logprobs=mode in ("logprobs", "forced_lp", "forced_scores", "forced_rows"),
+                          sampling=Sampling(1.0, 50, 1.0, 7) if mode == "forced_rows" else None)
+        if mode.startswith("forced"):
+            opts = dataclasses.replace(opts, forced=True)
+        sess.begin(opts)
+        if mode.startswith("forced"):                             # one batch whose table forces every step of every row
+            bench.fake_batch(opts, forced=table)
 
-    n_chk = max(args.warmup, 2)
-    tokens = {}
-    for mode in modes:                                            # one eager step, the capture, then replays — per mode
-        set_mode(sess, mode, table)
-        reset()
-        sess.run_steps(n_chk)
-        torch.cuda.synchronize()
-        tokens[mode] = sess.tokens[:, :n_chk].clone()
+    tokens = bench.capture(modes, set_mode)
     free = [m for m in modes if not m.startswith("forced")]
     for mode in free[1:]:                                         # the free modes select the same tokens ...
         assert torch.equal(tokens[mode], tokens[free[0]]), f"mode {mode} selected other tokens than {free[0]}"
     for mode in modes:                                            # ... and a forced mode emits its table
         if mode.startswith("forced"):
-            assert torch.equal(tokens[mode], table[:, :n_chk].long()), f"mode {mode} did not emit the forced tokens"
-    us = {m: [] for m in modes}
-    for _ in range(args.repeats):
-        for mode in modes:
-            set_mode(sess, mode, table)
-            reset()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            sess.run_steps(args.steps)
-            e1.record()
-            torch.cuda.synchronize()
-            us[mode].append(e0.elapsed_time(e1) * 1e3 / args.steps)
-    out = []
-    for mode in modes:
-        med = statistics.median(us[mode])
-        out.append({"model": "PaDT_Pro_3B", "mode": mode, "rows": rows, "layers": cfg.num_hidden_layers, "operands": str(op16).split(".")[-1],
-                    "context": args.context, "us_per_step": round(med, 1), "us_min": round(min(us[mode]), 1), "us_max": round(max(us[mode]), 1),
-                    "windows": [round(u, 1) for u in us[mode]], "steps_per_window": args.steps, "weight_bytes": int(wbytes)})
+            assert torch.equal(tokens[mode], table[:, : bench.n_chk].long()), f"mode {mode} did not emit the forced tokens"
+    us = bench.time(modes, set_mode)
+    out = [bench.record(mode, us[mode]) for mode in modes]
     if row_kernels:
         u = time_row_kernels(sess, cfg, rows, table, args)
         out.append({"model": "PaDT_Pro_3B", "mode": "row_kernels", "rows": rows, "us_per_step": round(statistics.median(u), 1),
@@ -134,31 +94,5 @@ def time_rows(cfg, rows, op16, modes, args, device):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--rows", default="8,64")
-    ap.add_argument("--modes", default=",".join(MODES))
-    ap.add_argument("--operands", default="fp16", choices=["fp16", "bf16"])
-    ap.add_argument("--context", type=int, default=512, help="cached tokens per row when a window starts")
-    ap.add_argument("--steps", type=int, default=64, help="graph replays per timed window")
-    ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--repeats", type=int, default=9)
-    ap.add_argument("--tag", default="", help="copied into every JSON line (which tree / which run)")
-    args = ap.parse_args()
-    modes = args.modes.split(",")
-    for m in modes:
-        if m not in MODES:
-            raise SystemExit(f"unknown mode '{m}'")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_forced_tokens.py times kernels on an MI355X: no GPU found")
-    device = torch.device("cuda:0")
-    op16 = torch.float16 if args.operands == "fp16" else torch.bfloat16
-    cfg = config.padt_pro_3b()
-    for rows in (int(r) for r in args.rows.split(",")):
-        for res in time_rows(cfg, rows, op16, modes, args, device):
-            print(json.dumps(dict(res, tag=args.tag) if args.tag else res), flush=True)
-        torch.cuda.empty_cache()
-
-
 if __name__ == "__main__":
-    main()
+    main(parser(__doc__, MODES, tag=True), MODES, time_rows)

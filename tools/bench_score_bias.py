@@ -7,7 +7,7 @@ One DecodeSession (padt_amd/llm.py) per row count at the PaDT_Pro_3B LLM shape, 
                feature added, so the script also runs in a tree without it (--modes plain): THAT run is the yardstick of the off path — the
                new build's `plain` is compared with the parent commit's `plain` of the same session, never with itself
   logit_bias   padt_vrt_head_bias: a bias over 64 text ids (the plain run's first tokens banned with -inf, so the run must change)
-  patch_bias   ... a prior over the session's patch columns
+  patch_bias   ... generate(patch_bias=) on for a batch in which no row owns a patch: the patch columns of the vector stay zero
   decay        ... exponential_decay_length_penalty=(8, 1.05)
   all          ... the three together
   all_lp       ... with output_token_logprobs=True: the LSE instantiation of the same head + padt_greedy_step_lp
@@ -20,119 +20,53 @@ mode in turn (the modes alternate, so drift of the machine hits them alike).  Pe
 window's value.  Prints one JSON line per (rows, mode).
 
 usage: python tools/bench_score_bias.py [--rows 8,64] [--modes plain,logit_bias,patch_bias,decay,all,all_lp] [--operands fp16|bf16] [--tag T]"""
-import argparse
-import dataclasses
-import json
 import os
-import statistics
 import sys
-
-import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from padt_amd import config  # noqa: E402
+import dataclasses  # noqa: E402
+
+import torch  # noqa: E402
+
 from padt_amd.generation import GenOptions  # noqa: E402
-from padt_amd.llm import DecodeSession  # noqa: E402
-from padt_amd.weights import _pad_to  # noqa: E402
-from bench_decode_weights import build_weights  # noqa: E402
+from step_bench import StepBench, main, parser  # noqa: E402
 
 MODES = ("plain", "logit_bias", "patch_bias", "decay", "all", "all_lp")
 DECAY = (8, 1.05)
 
 
-def set_mode(sess, cfg, mode, banned):
-    opts = GenOptions(token_logprobs=mode == "all_lp")
-    if mode != "plain":
-        lb = None
-        if mode in ("logit_bias", "all", "all_lp"):
-            lb = {int(t): float("-inf") for t in banned}
-            lb.update({i: 0.25 * (i % 7) - 0.5 for i in range(100, 164) if i not in lb and i % 7 != 2})
-            lb = tuple(sorted(lb.items()))
-        opts = dataclasses.replace(opts, logit_bias=lb, decay=DECAY if mode in ("decay", "all", "all_lp") else None,
-                                   patch_bias=mode in ("patch_bias", "all", "all_lp"))
-    sess.begin(opts)
-    if mode != "plain" and opts.patch_bias:
-        sess.bias[cfg.vocab_size:].copy_(torch.linspace(-2.0, 2.0, sess.np_max))
-
-
 def time_rows(cfg, rows, op16, modes, args, device):
-    W, wbytes = build_weights(cfg, "bf16", op16, device)
-    window = max(args.steps, args.warmup)
-    sess = DecodeSession(cfg, W, rows, _pad_to(args.context + window + 1, 64), 16, window + 1, device)
-    gen = torch.Generator(device=device).manual_seed(1)
-    first = torch.randint(0, cfg.vocab_size, (rows,), generator=gen, device=device)
+    bench = StepBench(cfg, rows, op16, args, device)
+    sess, banned = bench.sess, []
 
-    def reset():
-        """`context` cached tokens per row, step counter at zero: every window replays the same steps (never past s_max / t_max)"""
-        sess.step.zero_()
-        sess.unfinished.fill_(1)
-        sess.cur_tok.copy_(first)
-        sess.slot.fill_(args.context)
-        sess.lens.fill_(args.context)
-        sess.pos3.fill_(args.context)
+    def set_mode(mode):
+        opts = GenOptions(token_logprobs=mode == "all_lp")
+        if mode != "plain":
+            lb = None
+            if mode in ("logit_bias", "all", "all_lp"):
+                lb = {int(t): float("-inf") for t in banned}
+                lb.update({i: 0.25 * (i % 7) - 0.5 for i in range(100, 164) if i not in lb and i % 7 != 2})
+                lb = tuple(sorted(lb.items()))
+            opts = dataclasses.replace(opts, logit_bias=lb, decay=DECAY if mode in ("decay", "all", "all_lp") else None,
+                                       patch_bias=mode in ("patch_bias", "all", "all_lp"))
+        sess.begin(opts)
+        if opts.patch_bias:                                       # one batch in which no row owns a patch: its segment of the vector is empty
+            bench.fake_batch(opts, patch_bias=[None] * rows)
 
-    n_chk = max(args.warmup, 2)
-    tokens, banned = {}, []
-    for mode in ["plain"] + [m for m in modes if m != "plain"]:     # one eager step, the capture, then replays — per mode; plain first: its tokens get banned
-        set_mode(sess, cfg, mode, banned)
-        reset()
-        sess.run_steps(n_chk)
-        torch.cuda.synchronize()
-        tokens[mode] = sess.tokens[:, :n_chk].clone()
-        if mode == "plain":
-            banned = sorted(set(tokens["plain"][:, 0].tolist()))
+    def check(mode, tok):
+        if mode == "plain":                                       # plain runs first: its first tokens get banned
+            banned[:] = sorted(set(tok[:, 0].tolist()))
+
+    tokens = bench.capture(["plain"] + [m for m in modes if m != "plain"], set_mode, check)
     for mode in modes:
         if mode in ("logit_bias", "all", "all_lp"):                  # the banned columns are gone from step 0
             assert not set(tokens[mode][:, 0].tolist()) & set(banned), f"mode {mode} emitted a banned token"
         if mode in ("patch_bias", "decay"):                           # no row owns a patch here and no row is near EOS: the run is the plain one
             assert torch.equal(tokens[mode][:, 0], tokens["plain"][:, 0]), f"mode {mode} changed the first token"
-    us = {m: [] for m in modes}
-    for _ in range(args.repeats):
-        for mode in modes:
-            set_mode(sess, cfg, mode, banned)
-            reset()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            sess.run_steps(args.steps)
-            e1.record()
-            torch.cuda.synchronize()
-            us[mode].append(e0.elapsed_time(e1) * 1e3 / args.steps)
-    out = []
-    for mode in modes:
-        med = statistics.median(us[mode])
-        out.append({"model": "PaDT_Pro_3B", "mode": mode, "rows": rows, "layers": cfg.num_hidden_layers, "operands": str(op16).split(".")[-1],
-                    "context": args.context, "us_per_step": round(med, 1), "us_min": round(min(us[mode]), 1), "us_max": round(max(us[mode]), 1),
-                    "windows": [round(u, 1) for u in us[mode]], "steps_per_window": args.steps, "weight_bytes": int(wbytes)})
-    return out
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--rows", default="8,64")
-    ap.add_argument("--modes", default=",".join(MODES))
-    ap.add_argument("--operands", default="fp16", choices=["fp16", "bf16"])
-    ap.add_argument("--context", type=int, default=512, help="cached tokens per row when a window starts")
-    ap.add_argument("--steps", type=int, default=64, help="graph replays per timed window")
-    ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--repeats", type=int, default=9)
-    ap.add_argument("--tag", default="", help="copied into every JSON line (which tree / which run)")
-    args = ap.parse_args()
-    modes = args.modes.split(",")
-    for m in modes:
-        if m not in MODES:
-            raise SystemExit(f"unknown mode '{m}'")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_score_bias.py times kernels on an MI355X: no GPU found")
-    device = torch.device("cuda:0")
-    op16 = torch.float16 if args.operands == "fp16" else torch.bfloat16
-    cfg = config.padt_pro_3b()
-    for rows in (int(r) for r in args.rows.split(",")):
-        for res in time_rows(cfg, rows, op16, modes, args, device):
-            print(json.dumps(dict(res, tag=args.tag) if args.tag else res), flush=True)
-        torch.cuda.empty_cache()
+    us = bench.time(modes, set_mode)
+    return [bench.record(mode, us[mode]) for mode in modes]
 
 
 if __name__ == "__main__":
-    main()
+    main(parser(__doc__, MODES, tag=True), MODES, time_rows)

@@ -19,116 +19,49 @@ mode in turn (the modes alternate, so drift of the machine hits them alike).  Pe
 window's value.  Prints one JSON line per (rows, mode).
 
 usage: python tools/bench_stop_rules.py [--rows 8,64] [--modes plain,stop_sequences,min_tokens,max_tokens] [--operands fp16|bf16] [--tag T]"""
-import argparse
-import dataclasses
-import json
 import os
-import statistics
 import sys
-
-import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from padt_amd import config  # noqa: E402
+import dataclasses  # noqa: E402
+
+import torch  # noqa: E402
+
 from padt_amd.generation import GenOptions  # noqa: E402
-from padt_amd.llm import DecodeSession  # noqa: E402
-from padt_amd.weights import _pad_to  # noqa: E402
-from bench_decode_weights import build_weights  # noqa: E402
+from step_bench import StepBench, main, parser  # noqa: E402
 
 MODES = ("plain", "stop_sequences", "min_tokens", "max_tokens")
 
 
-def set_mode(sess, cfg, mode, window):
-    opts = GenOptions()
-    if mode != "plain":
-        from padt_amd.generation import NO_BUDGET
-        seqs = tuple(tuple(1000 + 32 * i + k for k in range(32)) for i in range(32)) if mode == "stop_sequences" else None
-        opts = dataclasses.replace(opts, stop_sequences=seqs, min_tokens=window + 1 if mode == "min_tokens" else None,
-                                   row_limits=mode == "max_tokens")
-    sess.begin(opts)
-    if mode != "plain":
-        sess.max_tok.fill_(NO_BUDGET)                                 # no row ends inside a window: every step does a live row's work
-
-
 def time_rows(cfg, rows, op16, modes, args, device):
-    W, wbytes = build_weights(cfg, "bf16", op16, device)
-    window = max(args.steps, args.warmup)
-    sess = DecodeSession(cfg, W, rows, _pad_to(args.context + window + 1, 64), 16, window + 1, device)
-    gen = torch.Generator(device=device).manual_seed(1)
-    first = torch.randint(0, cfg.vocab_size, (rows,), generator=gen, device=device)
+    bench = StepBench(cfg, rows, op16, args, device)
+    sess, window = bench.sess, max(args.steps, args.warmup)
 
-    def reset():
-        """`context` cached tokens per row, step counter at zero: every window replays the same steps (never past s_max / t_max)"""
-        sess.step.zero_()
-        sess.unfinished.fill_(1)
-        sess.cur_tok.copy_(first)
-        sess.slot.fill_(args.context)
-        sess.lens.fill_(args.context)
-        sess.pos3.fill_(args.context)
+    def set_mode(mode):
+        opts = GenOptions()
+        if mode != "plain":
+            seqs = tuple(tuple(1000 + 32 * i + k for k in range(32)) for i in range(32)) if mode == "stop_sequences" else None
+            opts = dataclasses.replace(opts, stop_sequences=seqs, min_tokens=window + 1 if mode == "min_tokens" else None,
+                                       row_limits=mode == "max_tokens")
+        sess.begin(opts)
+        if mode != "plain":                                       # a batch without budgets: no row ends inside a window, every step does a live row's work
+            bench.fake_batch(opts, stop=dict(min_tokens=None, max_tokens=None))
 
-    n_chk = max(args.warmup, 2)
-    tokens = {}
-    for mode in ["plain"] + [m for m in modes if m != "plain"]:     # one eager step, the capture, then replays — per mode
-        set_mode(sess, cfg, mode, window)
-        reset()
-        sess.run_steps(n_chk)
-        torch.cuda.synchronize()
-        tokens[mode] = sess.tokens[:, :n_chk].clone()
+    def check(mode, _):
         if mode != "plain":
             assert bool(sess.unfinished.all()) and not bool(sess.finish_reason.any()), f"mode {mode}: a row ended inside the window"
+
+    tokens = bench.capture(["plain"] + [m for m in modes if m != "plain"], set_mode, check)
     eos = int(cfg.eos_token_id)
     for mode in modes:
         if mode in ("stop_sequences", "max_tokens"):                  # nothing is banned and nothing matches: the run is the plain one
             assert torch.equal(tokens[mode], tokens["plain"]), f"mode {mode} changed the run"
         if mode == "min_tokens":
             assert not bool((tokens[mode] == eos).any()), "an EOS below min_tokens"
-    us = {m: [] for m in modes}
-    for _ in range(args.repeats):
-        for mode in modes:
-            set_mode(sess, cfg, mode, window)
-            reset()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            sess.run_steps(args.steps)
-            e1.record()
-            torch.cuda.synchronize()
-            us[mode].append(e0.elapsed_time(e1) * 1e3 / args.steps)
-    out = []
-    for mode in modes:
-        med = statistics.median(us[mode])
-        out.append({"model": "PaDT_Pro_3B", "mode": mode, "rows": rows, "layers": cfg.num_hidden_layers, "operands": str(op16).split(".")[-1],
-                    "context": args.context, "us_per_step": round(med, 1), "us_min": round(min(us[mode]), 1), "us_max": round(max(us[mode]), 1),
-                    "windows": [round(u, 1) for u in us[mode]], "steps_per_window": args.steps, "weight_bytes": int(wbytes)})
-    return out
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--rows", default="8,64")
-    ap.add_argument("--modes", default=",".join(MODES))
-    ap.add_argument("--operands", default="fp16", choices=["fp16", "bf16"])
-    ap.add_argument("--context", type=int, default=512, help="cached tokens per row when a window starts")
-    ap.add_argument("--steps", type=int, default=64, help="graph replays per timed window")
-    ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--repeats", type=int, default=9)
-    ap.add_argument("--tag", default="", help="copied into every JSON line (which tree / which run)")
-    args = ap.parse_args()
-    modes = args.modes.split(",")
-    for m in modes:
-        if m not in MODES:
-            raise SystemExit(f"unknown mode '{m}'")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_stop_rules.py times kernels on an MI355X: no GPU found")
-    device = torch.device("cuda:0")
-    op16 = torch.float16 if args.operands == "fp16" else torch.bfloat16
-    cfg = config.padt_pro_3b()
-    for rows in (int(r) for r in args.rows.split(",")):
-        for res in time_rows(cfg, rows, op16, modes, args, device):
-            print(json.dumps(dict(res, tag=args.tag) if args.tag else res), flush=True)
-        torch.cuda.empty_cache()
+    us = bench.time(modes, set_mode)
+    return [bench.record(mode, us[mode]) for mode in modes]
 
 
 if __name__ == "__main__":
-    main()
+    main(parser(__doc__, MODES, tag=True), MODES, time_rows)

@@ -20,23 +20,19 @@ mode in turn (the modes alternate, so drift of the machine hits them alike).  Pe
 window's value.  Prints one JSON line per (rows, mode).
 
 usage: python tools/bench_token_automaton.py [--rows 8,64] [--modes plain,ngram3,bans,automaton,automaton_bans] [--operands fp16|bf16]"""
-import argparse
-import dataclasses
-import json
 import os
-import random
-import statistics
 import sys
-
-import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from padt_amd import config, ops  # noqa: E402
+import dataclasses  # noqa: E402
+import random  # noqa: E402
+
+import torch  # noqa: E402
+
+from padt_amd import ops  # noqa: E402
 from padt_amd.generation import GenOptions  # noqa: E402
-from padt_amd.llm import DecodeSession  # noqa: E402
-from padt_amd.weights import _pad_to  # noqa: E402
-from bench_decode_weights import build_weights  # noqa: E402
+from step_bench import StepBench, main, parser  # noqa: E402
 
 MODES = ("plain", "ngram3", "bans", "automaton", "automaton_bans")
 
@@ -55,15 +51,12 @@ def coco_sized_trie(cfg, n_labels=80, n_vrt=5, seed=80):
 
 
 def time_rows(cfg, rows, op16, modes, args, device):
-    W, wbytes = build_weights(cfg, "bf16", op16, device)
-    window = max(args.steps, args.warmup)
-    sess = DecodeSession(cfg, W, rows, _pad_to(args.context + window + 1, 64), rows * args.patches, window + 1, device)
-    gen = torch.Generator(device=device).manual_seed(1)
-    first = torch.randint(0, cfg.vocab_size, (rows,), generator=gen, device=device)
+    bench = StepBench(cfg, rows, op16, args, device, np_max=rows * args.patches)
+    sess, gen = bench.sess, bench.gen
     ids = torch.randint(0, cfg.vocab_size, (40,), generator=gen, device=device).tolist()
     prompt = torch.randint(0, cfg.vocab_size, (rows, args.context), generator=gen, device=device).to(torch.int32)
-    sess.proto.copy_((torch.randn(sess.proto.shape, generator=gen, device=device) * 0.02).to(op16))
-    vrt_off = (torch.arange(rows + 1, device=device) * args.patches).to(torch.int32)
+    bench.random_prototypes(gen)
+    vrt_off = [b * args.patches for b in range(rows + 1)]        # every row owns `patches` prototype rows, in every mode
     rules = {"ngram3": ops.gen_rules_key(3, vocab_size=cfg.vocab_size),
              "bans": ops.gen_rules_key(3, [ids[2 * i: 2 * i + 2] for i in range(8)], ids[16: 32], vocab_size=cfg.vocab_size)}
     rules["automaton_bans"] = rules["bans"]
@@ -72,83 +65,28 @@ def time_rows(cfg, rows, op16, modes, args, device):
     def set_mode(mode):
         opts = GenOptions(rules=rules.get(mode))
         if mode.startswith("automaton"):
-            sess.begin(dataclasses.replace(opts, automaton=trie.key), automaton=trie)
+            opts = dataclasses.replace(opts, automaton=trie.key)
+            sess.begin(opts, automaton=trie)
         else:
             sess.begin(opts)
-        if opts.rules is not None:
-            sess.hist[:, : args.context] = prompt
-            sess.hist_len.fill_(args.context)
+        bench.fake_batch(opts, vrt_off=vrt_off, prompt_ids=prompt if opts.rules is not None else None)
 
-    def reset():
-        """`context` cached tokens per row, step counter at zero: every window replays the same steps (never past s_max / t_max)"""
-        sess.step.zero_()
-        sess.unfinished.fill_(1)
-        sess.cur_tok.copy_(first)
-        sess.slot.fill_(args.context)
-        sess.lens.fill_(args.context)
-        sess.pos3.fill_(args.context)
-        sess.vrt_off.copy_(vrt_off)
-
-    n_chk = max(args.warmup, 2)
-    for mode in modes:                                            # one eager step, the capture, then replays — per mode
-        set_mode(mode)
-        reset()
-        sess.run_steps(n_chk)
-        torch.cuda.synchronize()
+    def check(mode, tok):
         if mode.startswith("automaton"):                          # what was emitted is on the automaton, row by row
-            tok = sess.tokens[:, :n_chk].tolist()
-            for b, row in enumerate(tok):
+            for b, row in enumerate(tok.tolist()):
                 assert trie.accepts(row, cfg.vocab_size, (b * args.patches, (b + 1) * args.patches), ()), f"mode {mode}: row {b} left the automaton: {row}"
-    us = {m: [] for m in modes}
-    for _ in range(args.repeats):
-        for mode in modes:
-            set_mode(mode)
-            reset()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            sess.run_steps(args.steps)
-            e1.record()
-            torch.cuda.synchronize()
-            us[mode].append(e0.elapsed_time(e1) * 1e3 / args.steps)
+
+    bench.capture(modes, set_mode, check)
+    us = bench.time(modes, set_mode)
     out = []
     for mode in modes:
-        med = statistics.median(us[mode])
-        out.append({"model": "PaDT_Pro_3B", "mode": mode, "rows": rows, "layers": cfg.num_hidden_layers, "operands": str(op16).split(".")[-1],
-                    "context": args.context, "patches_per_row": args.patches, "us_per_step": round(med, 1), "us_min": round(min(us[mode]), 1),
-                    "us_max": round(max(us[mode]), 1), "windows": [round(u, 1) for u in us[mode]], "steps_per_window": args.steps,
-                    "weight_bytes": int(wbytes)})
+        out.append(bench.record(mode, us[mode], patches_per_row=args.patches))
         if trie is not None and mode.startswith("automaton"):
             out[-1].update(states=len(trie.edges), edges=sum(len(e) for e in trie.edges))
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--rows", default="8,64")
-    ap.add_argument("--modes", default=",".join(MODES))
-    ap.add_argument("--operands", default="fp16", choices=["fp16", "bf16"])
-    ap.add_argument("--context", type=int, default=512, help="cached tokens per row when a window starts (and the n-gram ban's prompt length)")
-    ap.add_argument("--patches", type=int, default=8, help="prototype rows (VRT columns) per session row")
-    ap.add_argument("--steps", type=int, default=64, help="graph replays per timed window")
-    ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--repeats", type=int, default=9)
-    ap.add_argument("--tag", default="", help="copied into every JSON line (which tree / which run)")
-    args = ap.parse_args()
-    modes = args.modes.split(",")
-    for m in modes:
-        if m not in MODES:
-            raise SystemExit(f"unknown mode '{m}'")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_token_automaton.py times kernels on an MI355X: no GPU found")
-    device = torch.device("cuda:0")
-    op16 = torch.float16 if args.operands == "fp16" else torch.bfloat16
-    cfg = config.padt_pro_3b()
-    for rows in (int(r) for r in args.rows.split(",")):
-        for res in time_rows(cfg, rows, op16, modes, args, device):
-            print(json.dumps(dict(res, tag=args.tag) if args.tag else res), flush=True)
-        torch.cuda.empty_cache()
-
-
 if __name__ == "__main__":
-    main()
+    ap = parser(__doc__, MODES, tag=True)
+    ap.add_argument("--patches", type=int, default=8, help="prototype rows (VRT columns) per session row")
+    main(ap, MODES, time_rows)

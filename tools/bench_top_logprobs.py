@@ -20,78 +20,48 @@ the rate at which it reads the rows (`pair_read_GBps`: the rows are cache-reside
 a count of what the mode moves, not a measurement.  Prints one JSON line per (rows, mode).
 
 usage: python tools/bench_top_logprobs.py [--rows 8,64] [--modes plain,top5,top32,patches,both,scores] [--operands fp16|bf16] [--patches 256]"""
-import argparse
-import json
 import os
-import statistics
 import sys
-
-import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from padt_amd import config  # noqa: E402
+import statistics  # noqa: E402
+
+import torch  # noqa: E402
+
+from padt_amd import ops  # noqa: E402
 from padt_amd.generation import GenOptions  # noqa: E402
-from padt_amd.llm import DecodeSession  # noqa: E402
-from padt_amd.weights import _pad_to  # noqa: E402
-from bench_decode_weights import build_weights  # noqa: E402
+from step_bench import StepBench, main, parser  # noqa: E402
 
 MODES = {"plain": (0, False), "top5": (5, False), "top32": (32, False), "patches": (0, True), "both": (5, True), "scores": (0, False)}
 
 
-def set_mode(sess, mode, patches):
-    sess.begin(GenOptions(keep_scores=mode == "scores", top_logprobs=MODES[mode][0], patch_logprobs=MODES[mode][1]), patches)
-
-
 def time_rows(cfg, rows, op16, modes, args, device):
-    W, wbytes = build_weights(cfg, "bf16", op16, device)
-    window = max(args.steps, args.warmup)
-    sess = DecodeSession(cfg, W, rows, _pad_to(args.context + window + 1, 64), rows * args.patches, window + 1, device)
-    sess.proto.copy_(torch.randn(sess.proto.shape, generator=torch.Generator(device=device).manual_seed(2), device=device) * 0.02)
-    sess.vrt_off.copy_(torch.arange(rows + 1, dtype=torch.int32, device=device) * args.patches)      # every sample owns `patches` columns
-    first = torch.randint(0, cfg.vocab_size, (rows,), generator=torch.Generator(device=device).manual_seed(1), device=device)
+    bench = StepBench(cfg, rows, op16, args, device, np_max=rows * args.patches)
+    sess = bench.sess
+    bench.random_prototypes(torch.Generator(device=device).manual_seed(2))
 
-    def reset():
-        """`context` cached tokens per row, step counter at zero: every window replays the same steps (never past s_max / t_max)"""
-        sess.step.zero_()
-        sess.unfinished.fill_(1)
-        sess.cur_tok.copy_(first)
-        sess.slot.fill_(args.context)
-        sess.lens.fill_(args.context)
-        sess.pos3.fill_(args.context)
+    def set_mode(mode):
+        opts = GenOptions(keep_scores=mode == "scores", top_logprobs=MODES[mode][0], patch_logprobs=MODES[mode][1])
+        sess.begin(opts, args.patches)
+        bench.fake_batch(opts, vrt_off=[b * args.patches for b in range(rows + 1)])      # every sample owns `patches` columns
 
-    tokens = {}
-    for mode in modes:                                            # one eager step, the capture, then replays — per mode
-        set_mode(sess, mode, args.patches)
-        reset()
-        sess.run_steps(max(args.warmup, 2))
-        torch.cuda.synchronize()
-        tokens[mode] = sess.tokens[:, : max(args.warmup, 2)].clone()
+    def check(mode, tok):
         if MODES[mode][0]:                                        # greedy: the best candidate of every step is the token the step selected
-            assert torch.equal(sess.top_idx[:, : max(args.warmup, 2), 0].long(), tokens[mode]), f"mode {mode}: entry 0 is not the selected token"
+            assert torch.equal(sess.top_idx[:, : bench.n_chk, 0].long(), tok), f"mode {mode}: entry 0 is not the selected token"
+
+    tokens = bench.capture(modes, set_mode, check)
     for mode in modes[1:]:                                        # the modes select the same tokens: only what is written next to them differs
         assert torch.equal(tokens[mode], tokens[modes[0]]), f"mode {mode} selected other tokens than {modes[0]}"
-    us = {m: [] for m in modes}
-    for _ in range(args.repeats):
-        for mode in modes:
-            set_mode(sess, mode, args.patches)
-            reset()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            sess.run_steps(args.steps)
-            e1.record()
-            torch.cuda.synchronize()
-            us[mode].append(e0.elapsed_time(e1) * 1e3 / args.steps)
+    us = bench.time(modes, set_mode)
     width = cfg.vocab_size + sess.np_max
     row_bytes = rows * width * 4
 
     def pair_alone(mode, n=200):
         """The two launches of padt_topk_logprob_rows_f32 alone, back to back over the session's row buffer as the last step left it (the rows
         are then cache-resident, as they are in the step, where the head has just written them) → us per call: median of 5 windows of n calls"""
-        from padt_amd import ops
-        set_mode(sess, mode, args.patches)
-        reset()
+        set_mode(mode)
+        bench.rewind()
         t = []
         for _ in range(5):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -107,45 +77,17 @@ def time_rows(cfg, rows, op16, modes, args, device):
         return statistics.median(t)
     out = []
     for mode in modes:
-        med = statistics.median(us[mode])
         k, pt = MODES[mode]
         # bytes next to the plain step: the row written by the head and read once by the selection (scores: written, read and filed again)
         extra = 3 * row_bytes if mode == "scores" else (2 * row_bytes + rows * (8 * k + 4 * args.patches * pt) if (k or pt) else 0)
-        out.append({"model": "PaDT_Pro_3B", "mode": mode, "rows": rows, "layers": cfg.num_hidden_layers, "operands": str(op16).split(".")[-1],
-                    "context": args.context, "row_columns": width, "us_per_step": round(med, 1), "us_min": round(min(us[mode]), 1),
-                    "us_max": round(max(us[mode]), 1), "windows": [round(u, 1) for u in us[mode]], "steps_per_window": args.steps,
-                    "weight_bytes": int(wbytes), "extra_bytes_per_step": int(extra)})
+        out.append(bench.record(mode, us[mode], row_columns=width, extra_bytes_per_step=int(extra)))
         if k or pt:                                               # measured: the launch pair alone and the rate at which it reads the rows
             pu = pair_alone(mode)
             out[-1].update(pair_us=round(pu, 2), pair_read_GBps=round(row_bytes / pu / 1e3, 1))
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--rows", default="8,64")
-    ap.add_argument("--modes", default="plain,top5,top32,patches,both,scores")
-    ap.add_argument("--operands", default="fp16", choices=["fp16", "bf16"])
-    ap.add_argument("--context", type=int, default=512, help="cached tokens per row when a window starts")
-    ap.add_argument("--patches", type=int, default=256, help="prototype rows (patch columns) per sample")
-    ap.add_argument("--steps", type=int, default=64, help="graph replays per timed window")
-    ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--repeats", type=int, default=9)
-    args = ap.parse_args()
-    modes = args.modes.split(",")
-    for m in modes:
-        if m not in MODES:
-            raise SystemExit(f"unknown mode '{m}'")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_top_logprobs.py times kernels on an MI355X: no GPU found")
-    device = torch.device("cuda:0")
-    op16 = torch.float16 if args.operands == "fp16" else torch.bfloat16
-    cfg = config.padt_pro_3b()
-    for rows in (int(r) for r in args.rows.split(",")):
-        for res in time_rows(cfg, rows, op16, modes, args, device):
-            print(json.dumps(res), flush=True)
-        torch.cuda.empty_cache()
-
-
 if __name__ == "__main__":
-    main()
+    ap = parser(__doc__, MODES)
+    ap.add_argument("--patches", type=int, default=256, help="prototype rows (patch columns) per sample")
+    main(ap, MODES, time_rows)
