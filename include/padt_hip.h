@@ -558,6 +558,51 @@ int  padt_collect_summary_stop(void* stream, const int* err, const int* unfinish
 int  padt_count_update(void* stream, const long* tokens, long ld_tokens, const int* step, const int* unfinished, const int* vrt_off,
                        const int* grid, const int* radius, void* cnt_text, long ld_cnt, long vocab, void* cnt_patch, void* near,
                        long n_proto, long batch);
+/* generate(beam_width=K) (beam_search.hip): the K best hypotheses of every sample, kept and reordered inside the decode step;
+ * generation.beam_step / beam_backtrace are the specification.  A sample owns K consecutive rows (row = sample * K + beam).
+ * padt_beam_step, in the place of padt_greedy_step, one block per sample.  At t = *step it reads the K rows' entries of top_idx / top_val
+ * [batch * K][t_top][keep] (padt_topk_logprob_rows_f32 with k = keep), adds each live beam's score (fp32), orders the candidates by value
+ * descending, then lower beam, then lower rank, and takes the first `keep`.  A candidate is finishing when its column is an EOS id (eos or
+ * gen_cfg's list) or t == t_last; the first K others become the live rows, the finishing ones among the first K enter the sample's store
+ * of K entries with score value / len_table[t] (the K best stay, older entries first at equal scores).  Written per child row, by one
+ * thread: beam_tok / beam_parent / beam_lp [t_max][batch * K] at t (patch columns as vocab + j, the row's own patch j), live, cur_tok (the
+ * column itself), perm (this step's parent; identity for a done sample); a slot that cannot be filled is dead (score -inf, pad token, its own
+ * parent).  Chores of padt_greedy_step for all K rows: hidden_buf[t][row] = hidden[row], slot / lens / pos3 advance (advance != 0),
+ * unfinished = 0 for the K rows of a done sample, the step counter bumped by a second launch.  *err = 1 for a column outside the row's table.
+ * beam_cfg: 8 int32 in DEVICE memory, packed by ops.beam_cfg_tensor: [0] magic 0x424d3031 [1] K [2] keep [3] early stopping 0 False / 1 True /
+ *   2 "never" [4] t_last = the call's last step [5] 1: the early-stop heuristic divides by len_table[t_last] ("never" with a penalty > 0).
+ * State per sample: live / st_score / st_lp fp32 [batch][K], st_end / st_parent / st_tok / sent int32 [batch][K] (an empty entry: -inf, -1),
+ *   flags int32 [batch][2] = (heuristic not yet satisfied, done).  K <= 8, keep <= 32. */
+int  padt_beam_step(void* stream, const int* top_idx, const void* top_val, long t_top, long keep, long batch, long K, long D, long t_max,
+                    const int* beam_cfg, const void* len_table, const void* gen_cfg, int eos, int pad, long vocab, long n_cols,
+                    const int* vrt_off, void* live, void* st_score, void* st_lp, int* st_end, int* st_parent, int* st_tok, int* sent,
+                    int* flags, int* beam_tok, int* beam_parent, void* beam_lp, int* perm, long* cur_tok, int* unfinished, int* step,
+                    int* slot, int* lens, int* pos3, const void* hidden, void* hidden_buf, int advance, int* err, const void* rep_lp);
+/* generate(beam_width=, output_token_logprobs=True): the log-prob REPORTED for a candidate, in front of padt_beam_step.  One block per row b:
+ * M and S = sum of part_sum x exp(part_val - M) folded from the LSE head's block partials in padt_greedy_step_lp's order, then
+ * out[b][j] (fp32 [rows][keep]) = (rows_f32[b][col] - M) - log S for col = top_idx[b][*step][j]; -inf for col < 0, a -inf score, a row without
+ * candidates.  For the row's arg-max these are padt_greedy_step_lp's bits, for any column padt_forced_step's.  padt_beam_step(rep_lp = out)
+ * records these values in beam_lp / st_lp; the scores it accumulates stay top_val's.  rep_lp null: the recorded values are top_val's. */
+int  padt_beam_cand_lp(void* stream, const void* part_val, const int* part_idx, const void* part_sum, long nblk, long rows,
+                       const void* rows_f32, long ld, long n_cols, const int* top_idx, long t_top, long keep, const int* step, void* out);
+/* The packed KV caches follow the beams, all layers in one launch, in place: for every sample, slots [p0[row], slot[row]) of child row c
+ * get the former bits of row perm[c] of the same sample (row = sample * K + beam; p0 / slot are read at the sample's first row).  images:
+ * n_layers pairs of DEVICE pointers (K image, V^T image) in device memory, each image [batch * K][n_kv_heads][s_max * head_dim] 16-bit
+ * values in padt_decode_attn_rope's packed layout.  Moved by the images' own tiles (K: 16 slots = head_dim * 32 contiguous bytes; V^T: 32
+ * slots = head_dim / 16 segments of 1 KiB): a slot inside a touched tile but outside the range may hold the child's or the parent's former
+ * bits; nothing outside the touched tiles of a permuted sample's rows is written, a sample whose perm is the identity stores nothing.  The
+ * grid covers t_max generated slots; blocks above the live range exit (capture-safe).  head_dim 128, s_max % 32 == 0, K <= 8. */
+int  padt_beam_reorder_kv(void* stream, const void* images, long n_layers, const int* perm, const int* p0, const int* slot, long batch, long K,
+                          long n_kv_heads, long head_dim, long s_max, long t_max);
+/* generation.beam_backtrace on the device, one block per returned hypothesis i = sample * n_best + r (the sample's r-th best store entry):
+ * tokens[i][0..t_max) int64 (pad behind the end; patch tokens vocab + j renumbered to vocab + out_off[i] + j), logprobs[i][0..t_max) (0 behind
+ * the end), scores[i], lengths[i], src_row[i][t] = the beam whose hidden row produced token t (-1 behind the end), and out_hidden
+ * [t_max][batch * n_best][D] = hidden_buf[t][sample * K + src_row[i][t]] for t < lengths[i] (16-byte copies; rows behind the end are not
+ * written).  An empty store entry gives length 0 and score -inf. */
+int  padt_beam_finalize(void* stream, const void* st_score, const void* st_lp, const int* st_end, const int* st_parent, const int* st_tok,
+                        const int* beam_tok, const int* beam_parent, const void* beam_lp, long batch, long K, long n_best, long D, long t_max,
+                        int pad, long vocab, const int* out_off, const void* hidden_buf, void* out_hidden, long* tokens, void* logprobs,
+                        void* scores, int* lengths, int* src_row);
 
 /* ---- caller-side post-processing --------------------------------------------------------------- */
 /* out[o][y][x] = sigmoid(bilinear(masks[o][:src_h[o]][:src_w[o]] → dst_h[o] x dst_w[o], align_corners=False))[y][x] > 0.5,

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpadt_hip.so")
 SOURCES = ["capi.hip", "gemm.hip", "gemm256.hip", "attention.hip", "elementwise.hip", "vrt_head.hip", "decode_step.hip", "sampling.hip", "gen_rules.hip",
-           "topk_rows.hip", "token_automaton.hip", "stop_rules.hip", "count_penalties.hip", "decoder_hp.hip", "resize.hip", "rle.hip"]
+           "topk_rows.hip", "token_automaton.hip", "stop_rules.hip", "count_penalties.hip", "beam_search.hip", "decoder_hp.hip", "resize.hip", "rle.hip"]
 # Translation units written against the 16-bit operand type X of csrc/common.h: compiled a second time with X = fp16 (-DPADT_OP16_F16=1;
 # own namespace, entry points suffixed _f16: include/padt_hip_f16.h) and linked into the same library.
 TWIN_SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "elementwise.hip", "vrt_head.hip"]

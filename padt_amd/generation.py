@@ -4,6 +4,7 @@ generation_config.json resolve to, carried from ``generate_launch`` through the 
 ``StepMode``, the part of it that selects the decode step's kernel sequence (one captured graph per value)."""
 import math
 import numbers
+import struct
 from dataclasses import InitVar, dataclass, fields
 from typing import NamedTuple, Optional
 
@@ -846,6 +847,245 @@ def stop_scan(tokens, sequences, min_tokens, max_tokens, eos_ids):
     return -1, "length", -1
 
 
+# ------------------------------------------------------------------------------------------------ generate(beam_width=, n_best=, beam_length_penalty=, beam_early_stopping=)
+# Beam search: the K best hypotheses of every sample, kept and reordered on the device.  The specification (beam_step / beam_backtrace below are
+# its plain statement; padt_beam_step and padt_beam_finalize are compared against them bit for bit) is HF 5.x's GenerationMixin._beam_search,
+# spelled without its -1e9 arithmetic: an impossible score IS -inf, an empty store entry IS empty.  Two deliberate differences from HF: before
+# step 0 the live scores are [0, -inf, ...] where HF holds [0, -1e9, ...] — the results differ only when beam 0 has fewer than `keep` finite
+# columns at step 0 (HF then continues copies of beam 0 at -1e9; here those slots are dead) — and a step's score is the log-softmax of the
+# PROCESSED row (logit_bias / patch_bias / the EOS decay applied first: the value token_logprobs defines), where HF normalises before its
+# processors.  NOT HF's num_beams / num_return_sequences / length_penalty / early_stopping: those names stay refused exactly as they are.
+BEAM_MAX_WIDTH = ops.BEAM_MAX_WIDTH
+BEAM_EARLY = {False: 0, True: 1, "never": 2}          # the early-stopping code of the device's beam config
+_NEG_INF = -math.inf
+
+
+def check_beam(beam_width=None, n_best=None, beam_length_penalty=None, beam_early_stopping=None, n_eos=1):
+    """generate(beam_width=K, n_best=n, beam_length_penalty=lp, beam_early_stopping=es) → the option's one normal form (K, n, lp, es) with
+    n = 1, lp = 1.0, es = False where not given; None when beam_width is None.  K: an integer >= 1; keep = max(2, 1 + n_eos) * K (HF's
+    beams_to_keep) must fit ops.TOPK_ROWS_MAX_K and K <= BEAM_MAX_WIDTH — above either cap NotImplementedError naming beam_width and the cap;
+    1 <= n <= K; lp a finite float; es one of False / True / "never".  Anything else, or one of the other three without beam_width,
+    ValueError naming the argument."""
+    others = dict(n_best=n_best, beam_length_penalty=beam_length_penalty, beam_early_stopping=beam_early_stopping)
+    if beam_width is None:
+        for name, v in others.items():
+            if v is not None:
+                raise ValueError(f"generate({name}={v!r}) needs beam_width: it is a beam-search option")
+        return None
+    if isinstance(beam_width, bool) or not isinstance(beam_width, numbers.Integral) or int(beam_width) < 1:
+        raise ValueError(f"generate(beam_width={beam_width!r}): an integer >= 1 is required")
+    K = int(beam_width)
+    keep = beam_keep(K, n_eos)
+    if K > BEAM_MAX_WIDTH:
+        raise NotImplementedError(f"generate(beam_width={K}): at most beam_width={BEAM_MAX_WIDTH} on the MI355X path")
+    if keep > ops.TOPK_ROWS_MAX_K:
+        raise NotImplementedError(f"generate(beam_width={K}) with {int(n_eos)} EOS ids keeps {keep} candidates per step; at most "
+                                  f"{ops.TOPK_ROWS_MAX_K} are selected on the device — lower beam_width or shorten the eos_token_id list")
+    n = 1 if n_best is None else n_best
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or not 1 <= int(n) <= K:
+        raise ValueError(f"generate(n_best={n_best!r}): an integer in [1, beam_width={K}] is required")
+    lp = 1.0 if beam_length_penalty is None else beam_length_penalty
+    if isinstance(lp, bool) or not isinstance(lp, numbers.Real) or not math.isfinite(float(lp)):
+        raise ValueError(f"generate(beam_length_penalty={beam_length_penalty!r}): a finite number is required")
+    es = False if beam_early_stopping is None else beam_early_stopping
+    if not (es is False or es is True or es == "never" and isinstance(es, str)):
+        raise ValueError(f"generate(beam_early_stopping={beam_early_stopping!r}): False, True or \"never\" is required")
+    return K, int(n), float(lp), es
+
+
+def check_beam_compatible(opts, processors=False, criteria=False, reference=False, output_scores=False, output_logits=False):
+    """What generate(beam_width=) refuses by name (NotImplementedError): everything that depends on a row's generated HISTORY — that state
+    (seen, hist, counts, automaton state, stop matches) does not follow the beams yet — sampling, and the outputs that describe ONE
+    hypothesis per row.  opts: the call's resolved options (the beam entry aside); the other arguments say what else the call carries."""
+    bad = []
+    if opts.sampling is not None:
+        bad.append("do_sample")
+    if opts.repetition_penalty != 1.0:
+        bad.append("repetition_penalty")
+    if opts.rules is not None:
+        n_gram, static, begin, words = opts.rules
+        bad += [nm for nm, on in (("no_repeat_ngram_size", n_gram), ("bad_words_ids", words), ("suppress_tokens", static),
+                                  ("begin_suppress_tokens", begin)) if on] or ["suppress_tokens"]
+    if opts.automaton is not None:
+        bad.append("token_automaton")
+    if opts.forced:
+        bad.append("forced_tokens")
+    if opts.stop:
+        bad.append("stop_sequences / min_tokens / max_tokens")
+    if opts.counts:
+        bad.append("frequency_penalty / presence_penalty / patch_suppression")
+    if opts.top_logprobs:
+        bad.append("top_logprobs")
+    if opts.patch_logprobs:
+        bad.append("output_patch_logprobs")
+    if output_logits or opts.keep_logits:
+        bad.append("output_logits")
+    if output_scores or (opts.keep_scores and not (output_logits or opts.keep_logits or processors or criteria)):
+        bad.append("output_scores")
+    if processors:
+        bad.append("logits_processor")
+    if criteria:
+        bad.append("stopping_criteria")
+    if reference:
+        bad.append("precision=\"reference\"")
+    if bad:
+        raise NotImplementedError(f"generate(beam_width=...) with {', '.join(bad)} is not implemented on the MI355X path: a row's history state "
+                                  "does not follow the beams yet, and scores / candidates describe one hypothesis per row — drop the argument "
+                                  "or run without beam_width")
+
+
+def check_beam_session(config, batch, K):
+    """What a beam call needs of the model and of a decode session, before anything is launched: the packed KV caches
+    (head_dim 128, at most 16 query heads per kv head — padt_beam_reorder_kv moves their tiles) and batch * K rows within
+    ops.DECODE_ROWS_MAX, what one decode step takes.  NotImplementedError naming beam_width."""
+    if not (int(config.head_dim) == 128 and int(config.num_attention_heads) // int(config.num_key_value_heads) <= 16):
+        raise NotImplementedError("generate(beam_width=...) needs the packed KV caches (head_dim 128: PaDT_Pro_3B / 7B): "
+                                  "padt_beam_reorder_kv moves their tiles")
+    if int(batch) * int(K) > ops.DECODE_ROWS_MAX:
+        raise NotImplementedError(f"generate(beam_width={int(K)}) on {int(batch)} queries needs {int(batch) * int(K)} rows; a decode session takes "
+                                  f"at most {ops.DECODE_ROWS_MAX} — lower beam_width or split the batch")
+
+
+def beam_keep(K, n_eos):
+    """HF's beams_to_keep: the candidates a step keeps per sample, so that K of them remain live when every EOS id was among the best."""
+    return max(2, 1 + int(n_eos)) * int(K)
+
+
+def beam_len_table(length_penalty, t_max) -> torch.Tensor:
+    """The device table of the length penalty: fp32 (t_max,) with entry t = (t + 1) ** length_penalty — the divisor of a hypothesis that ends
+    with its (t + 1)-th token — computed in double with Python's pow and rounded once.  The kernel only ever divides by an entry, so one
+    captured graph serves every penalty.  A power beyond the fp32 range is +inf (or 0), never an exception."""
+    vals = []
+    for t in range(int(t_max)):
+        try:
+            vals.append(float(t + 1) ** float(length_penalty))
+        except OverflowError:
+            vals.append(math.inf)
+    return torch.tensor(vals, dtype=torch.float64).to(torch.float32)
+
+
+def _f32(x):
+    """the double x rounded to fp32 (to nearest even; beyond the range: +-inf), as a Python float"""
+    if math.isfinite(x) and abs(x) <= 3.4028234663852886e38:
+        return struct.unpack("f", struct.pack("f", x))[0]
+    return float(torch.tensor(x, dtype=torch.float64).to(torch.float32))
+
+
+def _f32_add(a, b):
+    """fp32 a + b of two fp32 values: the double sum of two fp32 values rounds to the fp32 sum (no double rounding: 53 >= 2 * 24 + 2)."""
+    return _f32(a + b)
+
+
+def _f32_div(a, b):
+    """fp32 a / b of two fp32 values (the double quotient rounds to the fp32 quotient for the same reason)."""
+    if b == 0.0:
+        return math.nan if a == 0.0 or math.isnan(a) else math.copysign(math.inf, a) * math.copysign(1.0, b)
+    if math.isinf(a) and math.isinf(b):
+        return math.nan
+    return _f32(a / b)
+
+
+def beam_new_state(K):
+    """The state of one sample before step 0: live scores [0, -inf, ...], an empty finished store, the early-stop heuristic not yet
+    satisfied (`open`), not done.  A store entry is (score, end step, parent beam, last token, last log-prob); empty: score -inf, end -1."""
+    K = int(K)
+    return dict(live=[0.0] + [_NEG_INF] * (K - 1), store=[(_NEG_INF, -1, -1, -1, 0.0)] * K, sent=[False] * K, open=True, done=False)
+
+
+def beam_step(state, cand_val, cand_idx, t, keep, eos_ids, len_table, t_last, early=False, pad=0, length_penalty=None, cand_rep=None):
+    """One sample, one step of the beam search → (tok, parent, lp, info): the K child rows' token, parent beam and step log-prob, and
+    info = dict(order=, finishing=, merged=) for tests.  `state` (beam_new_state) is updated in place; a done sample returns pad rows with
+    parent = the slot itself and changes nothing.
+
+    cand_val[p][r] / cand_idx[p][r] (r < keep): live beam p's r-th best (log-prob, column) pair, descending (-inf / -1 once the finite
+    columns run out); t: the step; len_table: beam_len_table's values for the call's penalty; t_last: the call's last step
+    (max_new_tokens - 1); early: False / True / "never".  cand_rep[p][r] (optional): the log-prob REPORTED for the candidate — what the
+    returned lp and the store's last log-prob hold — where it is not cand_val itself: generate() reports the value token_logprobs defines
+    (the greedy step's fold of the head's partials), which differs from the top-k kernel's by a rounding; the values added are cand_val's.
+
+      1. value = fp32(live[p] + cand_val[p][r]); a -inf value is no candidate (never live, never finishing).
+      2. order by value descending, then lower beam, then lower rank; the first `keep` are the step's candidates.
+      3. a candidate is FINISHING when its token is one of eos_ids or t == t_last.
+      4. the first K non-finishing candidates become the live beams (in that order: live scores descend); a slot that cannot be filled is
+         dead: score -inf, pad token, parent = itself.
+      5. the finishing ones among the FIRST K candidates are merged into the finished store with score fp32(value / len_table[t]): store
+         entries and new ones ordered by score descending, an old entry before a new one of equal score, new ones in candidate order; the K
+         best stay.  No merge when early is True and the store is full, nor once the heuristic flag (`open`) is cleared.
+      6. open &= fp32(live[0] / d) > min(store scores), d = len_table[t_last] when early == "never" and length_penalty > 0 (None: read
+         off the table, which then ascends), else len_table[t]; an empty entry counts as -inf (HF: _check_early_stop_heuristic after
+         cur_len += 1).
+      7. done = not (open and not (early is True and store full) and not every candidate finishing)
+         (HF: _beam_search_has_unfinished_sequences; no candidate at all: every one of none is finishing)."""
+    K = len(state["live"])
+    if state["done"]:
+        return [int(pad)] * K, list(range(K)), [0.0] * K, dict(order=[], finishing=[], merged=[])
+    eos = {int(e) for e in eos_ids}
+    cands = []
+    for p in range(K):
+        if state["live"][p] == _NEG_INF:
+            continue
+        for r in range(int(keep)):
+            lp, col = float(cand_val[p][r]), int(cand_idx[p][r])
+            if col < 0 or lp == _NEG_INF or math.isnan(lp):
+                continue
+            v = _f32_add(state["live"][p], lp)
+            if v == _NEG_INF:
+                continue
+            cands.append((-v, p, r, col, lp if cand_rep is None else float(cand_rep[p][r])))
+    cands.sort(key=lambda c: c[:3])
+    cands = cands[: int(keep)]
+    finishing = [c[3] in eos or int(t) >= int(t_last) for c in cands]
+    # 4. the live beams of the next step
+    tok, parent, lps, live = [int(pad)] * K, list(range(K)), [0.0] * K, [_NEG_INF] * K
+    n = 0
+    for c, fin in zip(cands, finishing):
+        if not fin and n < K:
+            tok[n], parent[n], lps[n], live[n] = c[3], c[1], c[4], -c[0]
+            n += 1
+    # 5. the finished store
+    full = all(state["sent"])
+    merged = []
+    if state["open"] and not (early is True and full):
+        div = float(len_table[int(t)])
+        new = [(_f32_div(-c[0], div), int(t), c[1], c[3], c[4]) for c, fin in list(zip(cands, finishing))[:K] if fin]
+        new = [e for e in new if not math.isnan(e[0])]
+        merged = new
+        entries = [(e, s) for e, s in zip(state["store"], state["sent"])] + [(e, True) for e in new]
+        entries.sort(key=lambda es: -es[0][0])                    # stable: old entries first, new ones in candidate order
+        state["store"], state["sent"] = [e for e, _ in entries[:K]], [s for _, s in entries[:K]]
+    state["live"] = live
+    # 6. can a running beam still beat the worst finished one?
+    asc = (len(len_table) > 1 and float(len_table[1]) > float(len_table[0])) if length_penalty is None else float(length_penalty) > 0.0
+    d = float(len_table[int(t_last)]) if (isinstance(early, str) and early == "never" and asc) else float(len_table[int(t)])
+    best = _f32_div(live[0], d)
+    worst = min(e[0] for e in state["store"]) if all(state["sent"]) else _NEG_INF
+    state["open"] = state["open"] and best > worst
+    # 7. is the sample done?
+    state["done"] = not (state["open"] and not (early is True and all(state["sent"])) and not all(finishing))
+    return tok, parent, lps, dict(order=[(c[1], c[2]) for c in cands], finishing=finishing, merged=merged)
+
+
+def beam_backtrace(store, beam_tok, beam_parent, beam_lp, n_best):
+    """The n best store entries of ONE sample, walked back through the steps' records → a list of n hypotheses, each a dict(score=, length=,
+    tokens=, logprobs=, rows=) — rows[t] = (t, beam): where the hidden row that produced token t lives (hidden_buf[t][sample * K + beam]).
+    store: the state's store (best first); beam_tok / beam_parent / beam_lp [t][K]: what beam_step returned per step.  An empty store entry
+    (nothing finished, possible only for a call that produced no candidate at all) gives an empty hypothesis with score -inf."""
+    out = []
+    for score, end, par, tok, lp in list(store)[: int(n_best)]:
+        if end < 0:
+            out.append(dict(score=_NEG_INF, length=0, tokens=[], logprobs=[], rows=[]))
+            continue
+        toks, lps, rows = [0] * (end + 1), [0.0] * (end + 1), [None] * (end + 1)
+        toks[end], lps[end], rows[end] = int(tok), float(lp), (end, int(par))
+        r = int(par)
+        for t in range(end - 1, -1, -1):
+            toks[t], lps[t] = int(beam_tok[t][r]), float(beam_lp[t][r])
+            r = int(beam_parent[t][r])
+            rows[t] = (t, r)
+        out.append(dict(score=float(score), length=end + 1, tokens=toks, logprobs=lps, rows=rows))
+    return out
+
+
 # generate()'s named parameters a generation_config may carry: an explicit argument (not None) wins, as in HF (padt.py:436)
 _GENERATE_CONFIG_NAMED = ("max_new_tokens", "max_length", "do_sample", "repetition_penalty", "eos_token_id", "pad_token_id", "temperature", "top_k",
                           "top_p", "no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens", "min_p", "typical_p",
@@ -938,6 +1178,7 @@ class StepMode(NamedTuple):
     bias: bool = False               # logit_bias / patch_bias / exponential_decay_length_penalty: padt_vrt_head_bias reads the session's bias vector and decay table
     stop: bool = False               # stop_sequences / min_tokens / max_tokens: padt_stop_ban in front of the head, padt_stop_match behind the bookkeeping kernel
     counts: bool = False             # frequency_penalty / presence_penalty / patch_suppression: padt_vrt_head_counts reads the session's count tables, padt_count_update keeps them
+    beam: int = 0                    # generate(beam_width=K): the width; padt_beam_step in the place of padt_greedy_step over top_k = keep candidates per row, then padt_beam_reorder_kv
 
 
 @dataclass(frozen=True)
@@ -978,9 +1219,13 @@ class GenOptions:
     # of the session's arrays) and a batch with the feature never shares one with a batch without.  Init-only attributes like those above.
     count_penalties: InitVar[bool] = False
     patch_suppression: InitVar[bool] = False
+    # generate(beam_width=, n_best=, beam_length_penalty=, beam_early_stopping=) in check_beam's normal form (K, n_best, penalty, early
+    # stopping), or None.  An init-only attribute like those above — part of equality, hash and repr; spelled for a re-run by beam_kwargs().
+    beam: InitVar[Optional[tuple]] = None
 
     def __post_init__(self, forced, automaton, logit_bias, decay, patch_bias, stop_sequences, min_tokens, row_limits, count_penalties,
-                      patch_suppression):
+                      patch_suppression, beam):
+        object.__setattr__(self, "beam", None if beam is None else (int(beam[0]), int(beam[1]), float(beam[2]), beam[3]))
         object.__setattr__(self, "count_penalties", bool(count_penalties))
         object.__setattr__(self, "patch_suppression", bool(patch_suppression))
         object.__setattr__(self, "stop_sequences", None if stop_sequences is None else tuple(tuple(int(i) for i in q) for q in stop_sequences))
@@ -996,7 +1241,7 @@ class GenOptions:
         # every field, whatever is added later, and the init-only attributes
         return tuple(getattr(self, f.name) for f in fields(self)) + (self.forced, self.automaton, self.logit_bias, self.decay, self.patch_bias,
                                                                           self.stop_sequences, self.min_tokens, self.row_limits,
-                                                                          self.count_penalties, self.patch_suppression)
+                                                                          self.count_penalties, self.patch_suppression, self.beam)
 
     def __eq__(self, other):
         return self._key() == other._key() if isinstance(other, GenOptions) else NotImplemented
@@ -1014,7 +1259,7 @@ class GenOptions:
         sq = self.stop_sequences
         args += [f"stop_sequences={sq!r}" if sq is None or sum(len(q) for q in sq) <= 16 else f"stop_sequences=<{len(sq)} sequences, #{hash(sq) & 0xffffffff:08x}>",
                  f"min_tokens={self.min_tokens!r}", f"row_limits={self.row_limits!r}", f"count_penalties={self.count_penalties!r}",
-                 f"patch_suppression={self.patch_suppression!r}"]
+                 f"patch_suppression={self.patch_suppression!r}", f"beam={self.beam!r}"]
         return f"GenOptions({', '.join(args)})"
 
     @property
@@ -1045,6 +1290,11 @@ class GenOptions:
         return self.count_penalties or self.patch_suppression
 
     @property
+    def beam_keep(self) -> int:
+        """The candidates a beam step keeps per sample and asks of every row (HF's beams_to_keep over the call's EOS ids); 0 without beams."""
+        return 0 if self.beam is None else beam_keep(self.beam[0], len(set(self.eos_ids)) or 1)
+
+    @property
     def reads_prompt(self) -> bool:
         """A ban or the repetition penalty is active: the built-in processors see the caller's full (B, L) input_ids."""
         return self.repetition_penalty != 1.0 or self.rules is not None
@@ -1058,9 +1308,10 @@ class GenOptions:
 
     def step_mode(self, processors: bool = False, reference: bool = False) -> StepMode:
         return StepMode(sampling=self.sampling is not None, keep_scores=self.keep_scores, keep_logits=self.keep_logits, rules=self.rules is not None,
-                        token_logprobs=self.token_logprobs, top_k=self.top_logprobs, patches=self.patch_logprobs, processors=bool(processors),
-                        reference=bool(reference), warpers=self.sampling is not None and self.sampling.warpers, forced=self.forced,
-                        automaton=self.automaton is not None, bias=self.score_bias, stop=self.stop, counts=self.counts)
+                        token_logprobs=self.token_logprobs, top_k=self.beam_keep or self.top_logprobs, patches=self.patch_logprobs,
+                        processors=bool(processors), reference=bool(reference), warpers=self.sampling is not None and self.sampling.warpers,
+                        forced=self.forced, automaton=self.automaton is not None, bias=self.score_bias, stop=self.stop, counts=self.counts,
+                        beam=0 if self.beam is None else self.beam[0])
 
     def warper_kwargs(self) -> dict:
         """min_p / typical_p / epsilon_cutoff / eta_cutoff as explicit generate() keywords (with_warpers values), next to generate_kwargs():
@@ -1079,6 +1330,12 @@ class GenOptions:
         generation_config carries either, so off is None.  Per-row min_tokens / max_tokens travel with their batch."""
         sq = self.stop_sequences
         return dict(stop_sequences=None if sq is None else [list(q) for q in sq], min_tokens=self.min_tokens)
+
+    def beam_kwargs(self) -> dict:
+        """beam_width / n_best / beam_length_penalty / beam_early_stopping as explicit generate() keywords, next to generate_kwargs() and the
+        other *_kwargs().  No generation_config carries them, so off is None."""
+        K, n, lp, es = self.beam or (None, None, None, None)
+        return dict(beam_width=K, n_best=n, beam_length_penalty=lp, beam_early_stopping=es)
 
     def generate_kwargs(self) -> dict:
         """Explicit generate() arguments that resolve back to these options under ANY generation_config: what is off is spelled as off (0, [],

@@ -26,7 +26,8 @@ def infer_dataset(model, processor, dataset: Sequence, prepare: Callable, output
                   datasetname: str = "coco", suffix: str = "", rank: int = 0, world: int = 1, max_new_tokens: int = 1024,
                   depth: int = 2, merge: int = 4, schedule=None, repetition_penalty=None, eos_token_id=None,
                   token_automaton=None, logit_bias=None, exponential_decay_length_penalty=None, stop_sequences=None, min_tokens=None,
-                  max_tokens=None, frequency_penalty=None, presence_penalty=None, patch_suppression=None):
+                  max_tokens=None, frequency_penalty=None, presence_penalty=None, patch_suppression=None, beam_width=None, n_best=None,
+                  beam_length_penalty=None, beam_early_stopping=None):
     """repetition_penalty / eos_token_id: None = the checkpoint's generation_config.json (model.generation_config), as HF's
     generate() inside the reference's loop applies it (utils.py:230-236 → padt.py:436).
     token_automaton: generate(token_automaton=) for every batch of the run (e.g. the dataset's category names followed by their VRTs).
@@ -34,7 +35,9 @@ def infer_dataset(model, processor, dataset: Sequence, prepare: Callable, output
     stop_sequences / min_tokens / max_tokens: generate()'s, for every batch of the run (one value each; `prepare` may return per-row
     `min_tokens` / `max_tokens` lists of its batch, which win).
     frequency_penalty / presence_penalty / patch_suppression: generate()'s count edits, for every batch of the run (one value each; `prepare`
-    may return per-row lists of its batch under the same names, which win)."""
+    may return per-row lists of its batch under the same names, which win).
+    beam_width / n_best / beam_length_penalty / beam_early_stopping: generate()'s beam search, for every batch of the run; every sample then
+    writes n_best completions and result sets under its image id, best first."""
     os.makedirs(output_dir, exist_ok=True)
     f_res = os.path.join(output_dir, f"{datasetname}_{rank}_pred_results_{suffix}.json")
     f_comp = os.path.join(output_dir, f"{datasetname}_{rank}_pred_comp_{suffix}.json")
@@ -62,7 +65,8 @@ def infer_dataset(model, processor, dataset: Sequence, prepare: Callable, output
         if idx >= len(dataset):                                   # utils.py:196: ranks past the end skip the work
             continue
         b = prepare(dataset[idx: idx + batch_size])
-        meta.append({"ids": list(b["ids"]), "image_sizes": list(b["image_sizes"])})
+        rep = (n_best or 1) if beam_width is not None else 1      # a beam batch returns n_best rows per sample
+        meta.append({"ids": [i for i in b["ids"] for _ in range(rep)], "image_sizes": [z for z in b["image_sizes"] for _ in range(rep)]})
         extra = {"image_index": b["image_index"]} if b.get("image_index") is not None else {}
         if b.get("prefix") is not None:
             extra["prefix"] = b["prefix"]
@@ -76,7 +80,9 @@ def infer_dataset(model, processor, dataset: Sequence, prepare: Callable, output
         drain(runner.submit(b["input_ids"], b["attention_mask"], b.get("pixel_values"), b.get("image_grid_thw"),
                             max_new_tokens=max_new_tokens, schedule=schedule, repetition_penalty=repetition_penalty,
                             eos_token_id=eos_token_id, token_automaton=token_automaton, logit_bias=logit_bias,
-                            exponential_decay_length_penalty=exponential_decay_length_penalty, stop_sequences=stop_sequences, **extra))
+                            exponential_decay_length_penalty=exponential_decay_length_penalty, stop_sequences=stop_sequences,
+                            beam_width=beam_width, n_best=n_best, beam_length_penalty=beam_length_penalty,
+                            beam_early_stopping=beam_early_stopping, **extra))
         n += len(b["ids"])
     drain(runner.flush())
     return {"samples": n, "results_file": f_res, "completions_file": f_comp}

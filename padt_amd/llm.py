@@ -19,7 +19,7 @@ import torch
 
 from . import ops
 from .config import PaDTConfig
-from .generation import NO_BUDGET, GenOptions, StepMode, decay_table, stop_table
+from .generation import BEAM_EARLY, NO_BUDGET, GenOptions, StepMode, beam_len_table, decay_table, stop_table
 
 I32 = torch.int32
 
@@ -554,6 +554,11 @@ class DecodeSession:
         self.cnt_patch = self.near = None        # ... how often a patch column was generated by its row, and the completed-run VRT tokens around each patch, uint16 [np_max] ...
         self.cpen = None                 # ... each row's f, p and suppression penalty fp32 [3][B] (0: off) ...
         self.cgrid = self.cradius = None         # ... and its merged patch grid (hp, wp) [B][2] and radius [B] (-1: no suppression), int32: what padt_count_update reads
+        self.beam = None                 # mode.beam (generate(beam_width=K)): this generate's ops.BeamState — live scores, finished store, step records — over the buffers below ...
+        for nm in ops.BEAM_STATE_F32 + ops.BEAM_STATE_I32 + ("flags", "beam_tok", "beam_parent", "beam_lp", "perm", "p0", "cfg", "len_table"):
+            setattr(self, "beam_" + nm, None)      # ... flat, allocated on first use, one set for every width
+        self.beam_rep = None             # ... the log-probs a step reports for its candidates (mode.token_logprobs: padt_beam_cand_lp) [B][32] ...
+        self.beam_kv = None              # ... and the device table of the layers' cache image pointers padt_beam_reorder_kv reads, built once
         self.rope_cs = z(B, hd // 2, 2, dt=torch.float32)
         self.n_qkv = (cfg.num_attention_heads + 2 * Hkv) * hd
         self.graphs = {}                 # captured decode-step graph per mode (different kernel sequences and output buffers)
@@ -648,15 +653,16 @@ class DecodeSession:
             self._own("part_sum", self.nblk * B, F32)
             self._own("logprobs", (B, t_max), F32)
         self.top_idx = self.top_val = None
-        if opts.want_rows and self.topk_ws is None:
+        if (opts.want_rows or opts.beam is not None) and self.topk_ws is None:
             nbytes = ops.topk_rows_workspace(self.cfg.vocab_size + self.np_max, ops.TOPK_ROWS_MAX_K, B)
             self.topk_ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        if opts.top_logprobs:
+        k_top = opts.top_logprobs or opts.beam_keep              # a beam step reads its rows' `keep` best candidates from the same pair
+        if k_top:
             if self.top_flat is None:
                 n = B * t_max * ops.TOPK_ROWS_MAX_K
                 self.top_flat = (torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=F32))
-            n = B * t_max * opts.top_logprobs
-            self.top_idx, self.top_val = (f[:n].view(B, t_max, opts.top_logprobs) for f in self.top_flat)
+            n = B * t_max * k_top
+            self.top_idx, self.top_val = (f[:n].view(B, t_max, k_top) for f in self.top_flat)
             self.top_idx.fill_(-1)
             self.top_val.fill_(float("-inf"))
         if opts.patch_logprobs:
@@ -702,6 +708,22 @@ class DecodeSession:
         if opts.rules is not None:
             self.rules.copy_(ops.gen_rules_tensor(key=opts.rules).to(dev, non_blocking=True))
             self.hist_len.zero_()                                # rows no batch of the group fills: an empty prompt
+        self.beam = None
+        if opts.beam is not None:
+            # live scores [0, -inf, ...], empty stores, every sample open; the length table and the config in device memory, so that one
+            # captured graph per width (and candidate count) serves every penalty, early-stopping mode and max_new_tokens
+            K, _, penalty, early = opts.beam
+            if not self.cache_packed:
+                raise NotImplementedError("generate(beam_width=...) needs the packed KV caches (head_dim 128): padt_beam_reorder_kv moves their tiles")
+            if B % K:
+                raise ValueError(f"generate(beam_width={K}): the session holds {B} rows, not a multiple of the width")
+            self.beam = ops.BeamState(B // K, K, t_max, dev, own=lambda nm, n, dt: self._own("beam_" + nm, n, dt, reset=False))
+            self.beam.len_table.copy_(beam_len_table(penalty, t_max).to(dev, non_blocking=True))
+            self.beam.cfg.copy_(ops.beam_cfg_tensor(K, opts.beam_keep, BEAM_EARLY[early], T - 1, early == "never" and penalty > 0.0).to(dev, non_blocking=True))
+            if opts.token_logprobs:
+                self._own("beam_rep", B * ops.TOPK_ROWS_MAX_K, F32, reset=False)
+            if self.beam_kv is None:
+                self.beam_kv = ops.beam_kv_table(self.kc, self.vtc)
 
     def add_batch(self, opts: GenOptions, row0: int, proto_row0: int, vrt_off, lens, next_pos, prompt_ids=None, forced=None, stop=None,
                   counts=None, count_grids=None, patch_bias=None):
@@ -735,6 +757,8 @@ class DecodeSession:
         if opts.rules is not None:
             self.hist[rows, : ids_full.shape[1]].copy_(ids_full)  # int64 → int32 (ids are table rows)
             self.hist_len[rows].fill_(ids_full.shape[1])
+        if opts.beam is not None:                              # where the rows' generated slots begin: what padt_beam_reorder_kv moves
+            self.beam.p0[rows].copy_(lens_t.to(dev, non_blocking=True))
         if forced is not None:
             # this batch's rows of the session's table, in session numbering like the prompt history; the steps past n stay free (-1: begin())
             self.forced[rows, : forced.shape[1]].copy_(shift(forced).to(dev, non_blocking=True))
@@ -873,7 +897,22 @@ class DecodeSession:
             ops.topk_logprob_rows(lg, cfg.vocab_size + self.np_max, self.unfinished, self.step, self.topk_ws, self.B, top_idx=self.top_idx,
                                   top_val=self.top_val, vrt_off=self.vrt_off if m.patches else None, vocab=cfg.vocab_size,
                                   patch_lp=self.patch_lp if m.patches else None)
-        if fc is not None:
+        if m.beam:
+            # the K rows of a sample are its beams: their `keep` best candidates of this step are merged, the next live beams and the finished
+            # hypotheses selected (generation.beam_step), and the caches of every layer follow the beams' parents
+            bs = self.beam
+            rep_lp = None
+            if psum is not None:
+                # the log-probs REPORTED for the candidates are the values token_logprobs defines: the greedy step's fold of the LSE head's
+                # partials, so a hypothesis' token_logprobs are the bits the greedy call and score_completions report; the scores add the top-k's
+                rep_lp = ops.beam_cand_lp(self.part_val, self.part_idx, psum, nblk, lg, cfg.vocab_size + self.np_max, self.top_idx, self.step,
+                                          self.beam_rep[: self.B * m.top_k].view(self.B, m.top_k))
+            ops.beam_step(bs, self.top_idx, self.top_val, hn, self.hidden_buf, self.unfinished, self.cur_tok, self.step, self.slot, self.lens,
+                          self.pos3, self.vrt_off, cfg.eos_token_id, cfg.pad_token_id, cfg.vocab_size, cfg.vocab_size + self.np_max,
+                          advance=advance, gen_cfg=self.gen_cfg, err=self.err, rep_lp=rep_lp)
+            ops.beam_reorder_kv(self.beam_kv, bs.perm, bs.p0, self.slot, bs.B, bs.K, cfg.num_key_value_heads, cfg.head_dim, self.s_max,
+                                self.t_max, rows=self.B)
+        elif fc is not None:
             ops.forced_step(self.part_val, self.part_idx, nblk, hn, self.hidden_buf, self.unfinished, self.tokens,
                             self.cur_tok, self.step, self.slot, self.lens, self.pos3, cfg.eos_token_id, cfg.pad_token_id, fc,
                             cfg.vocab_size + self.np_max, advance=advance, gen_cfg=self.gen_cfg, seen=self.seen, part_sum=psum, logprobs=lp_out,

@@ -21,7 +21,7 @@ import torch
 from . import _lib, ops
 from .config import PaDTConfig
 from .decoder import PaDTDecoder
-from .generation import (_GENERATE_CONFIG_NAMED, _GENERATE_CONFIG_OWN, check_decay_length_penalty, check_forced_tokens, check_generate_kwargs,  # noqa: F401
+from .generation import (_GENERATE_CONFIG_NAMED, _GENERATE_CONFIG_OWN, check_beam, check_beam_compatible, check_beam_session, check_decay_length_penalty, check_forced_tokens, check_generate_kwargs,  # noqa: F401
                          check_count_penalties, check_logit_bias, check_max_tokens, check_patch_suppression, check_min_tokens, check_patch_bias, check_stop_sequences, check_token_automaton, check_top_logprobs, completion_logprobs, forced_tokens_active, generation_config_fields, resolve_options, with_warpers,
                          WARPER_NAMES)
 from .llm import (LanguageModel, PromptPrefix, check_shared_destinations, plan_prefix_build, plan_prompt, plan_prompt_prefix,
@@ -422,6 +422,29 @@ class PaDTForConditionalGeneration:
         ``generation_config=``.  Works with ``precision="reference"`` (the same head).  The options carry only WHETHER each mechanism is
         on: batches with different values share a decode group (each writes its own rows), a batch with the feature and one without do
         not; one captured graph serves every value; without the three the call is what it was: same kernels, same step mode.
+        Keywords ``beam_width=K`` / ``n_best=n`` / ``beam_length_penalty=1.0`` / ``beam_early_stopping=False``: beam search — the n best
+        completions of every query with their sequence scores, the hypotheses kept and reordered ON THE DEVICE inside the captured step
+        (generation.beam_step / beam_backtrace are the specification: HF 5.x's ``_beam_search`` rule, spelled without its ``-1e9``
+        arithmetic).  The call is expanded on the host to B * K rows (each input row K times, ``image_index`` / ``prefix`` composed with the
+        repeat), so the ViT runs once per image and the prompt rows once per query; a beam step then selects every row's
+        ``keep = max(2, 1 + #eos) * K`` best candidates (``padt_topk_logprob_rows_f32``), ``padt_beam_step`` merges them per query — live
+        beams, the finished store of K entries scored ``sum of log-probs / length ** beam_length_penalty``, HF's early-stopping heuristic
+        for ``beam_early_stopping`` False / True / ``"never"`` — and ``padt_beam_reorder_kv`` makes the packed KV caches follow the beams.
+        A step's score is the log-softmax of the PROCESSED row (``schedule``, ``logit_bias`` / ``patch_bias`` / the EOS decay applied first:
+        the value ``token_logprobs`` defines; HF normalises before its processors).  Returned: B * n rows, row ``b * n + r`` query b's r-th
+        best, shaped like a plain call on the inputs repeated n times — ``sequences`` trimmed to the longest returned hypothesis (pad behind
+        a shorter one), per-row VRT ranges and ``past_*`` entries to match, so ``parseVRTintoCompletion`` + ``vl_decode`` work unchanged
+        with ``image_grid_thw`` repeated — plus ``sequences_scores`` (B * n,), ``sequence_lengths`` (B * n,) and, when asked,
+        ``token_logprobs``.  K: an integer in [1, 8] with keep <= 32 and B * K <= 128 rows (``NotImplementedError`` naming ``beam_width`` beyond), 1 <= n <= K,
+        a finite penalty, else ``ValueError`` naming the argument; one of the other three without ``beam_width``: ``ValueError``.  Refused by
+        name together with ``beam_width`` (``NotImplementedError``): ``do_sample``, ``repetition_penalty != 1``, the four bans,
+        ``token_automaton``, ``forced_tokens``, ``stop_sequences`` / ``min_tokens`` / ``max_tokens``, the count penalties,
+        ``top_logprobs``, ``output_patch_logprobs``, ``output_scores``, ``output_logits``, ``logits_processor`` / ``stopping_criteria``,
+        ``precision="reference"`` and a model without the packed caches (head_dim != 128) — the state that depends on a row's generated
+        history does not follow the beams yet.  A beam batch is always its own decode group; one captured graph per width (and candidate
+        count) serves every penalty, early-stopping mode and ``max_new_tokens``.  They are NOT HF's ``num_beams`` /
+        ``num_return_sequences`` / ``length_penalty`` / ``early_stopping``, which stay refused by name; without ``beam_width`` the call
+        is what it was: same kernels, same step mode, same output object.
         """
         if synced_gpus:
             raise NotImplementedError("generate(synced_gpus=True) is the ZeRO-3 / FSDP lock-step loop (padt.py:445,670): every rank holds a full "
@@ -435,6 +458,7 @@ class PaDTForConditionalGeneration:
         stop_sequences, min_tokens, max_tokens = (kwargs.pop(k, None) for k in ("stop_sequences", "min_tokens", "max_tokens"))      # ... and how a row ends
         frequency_penalty, presence_penalty, patch_suppression = (kwargs.pop(k, None) for k in ("frequency_penalty", "presence_penalty", "patch_suppression"))      # ... and the count edits
         prefix = kwargs.pop("prefix", None)                           # ... and the handle of encode_prefix
+        beam = {k: kwargs.pop(k, None) for k in ("beam_width", "n_best", "beam_length_penalty", "beam_early_stopping")}      # ... and beam search
         if generation_config is not None:
             named = dict(max_new_tokens=max_new_tokens, max_length=max_length, do_sample=do_sample, repetition_penalty=repetition_penalty,
                          eos_token_id=eos_token_id, pad_token_id=pad_token_id, temperature=temperature, top_k=top_k, top_p=top_p,
@@ -492,6 +516,14 @@ class PaDTForConditionalGeneration:
                                                   patch_suppression=patch_suppression))
         if prefix is not None:
             hooks = dict(hooks or {}, prefix=prefix)
+        if any(v is not None for v in beam.values()):
+            check_beam(**beam)                                        # one of the other three without beam_width: ValueError
+            for name, on in (("output_scores", output_scores), ("output_logits", output_logits), ("logits_processor", processors is not None),
+                             ("stopping_criteria", criteria is not None)):
+                if on:
+                    raise NotImplementedError(f"generate(beam_width=...) with {name} is not implemented on the MI355X path: scores and host "
+                                              "callbacks describe one hypothesis per row — drop the argument or run without beam_width")
+            hooks = dict(hooks or {}, beam=beam)
         if output_logits:
             pen = self.generation_config.repetition_penalty if repetition_penalty is None else repetition_penalty
             if float(pen) != 1.0 or schedule is not None or processors is not None:
@@ -543,6 +575,9 @@ class PaDTForConditionalGeneration:
         entries: off); the sequences and a one-value ``min_tokens`` are part of the options, per-row lists are per-batch data.
         ``hooks=dict(counts=dict(frequency_penalty=..., presence_penalty=..., patch_suppression=...))``: generate()'s three arguments of that
         name (None entries: off); the values are per-batch data, the options only say which of the two mechanisms is on.
+        ``hooks=dict(beam=dict(beam_width=..., n_best=..., beam_length_penalty=..., beam_early_stopping=...))``: generate()'s four
+        arguments of that name; part of the options.  The batch is expanded to B * beam_width rows here and is its own decode group: with
+        ``group`` given the call returns None, and the group it starts takes no second batch.
         """
         # a call's min_p / typical_p / epsilon_cutoff / eta_cutoff arrive as hooks["warpers"] (this method's parameter list is frozen) and are put
         # in front of the generation config's; what is left of `hooks` is the caller's processors / criteria, or nothing
@@ -594,6 +629,10 @@ class PaDTForConditionalGeneration:
             if fpen is not None or supp is not None:                  # all off: the call without the arguments
                 counts = dict(frequency_penalty=fpen, presence_penalty=ppen, patch_suppression=supp)
             hooks = {k: v for k, v in hooks.items() if k != "counts"} or None
+        beam_args = None
+        if hooks is not None and "beam" in hooks:
+            beam_args = hooks["beam"] or {}
+            hooks = {k: v for k, v in hooks.items() if k != "beam"} or None
         decay = check_decay_length_penalty(decay, max_new_tokens)
         if decay is not None and decay[1] == 1.0:
             decay = None                                          # a[t] = 1 ** k - 1 = 0 at every step: the call without the argument
@@ -634,15 +673,47 @@ class PaDTForConditionalGeneration:
             if keep_logits and opts.sampling is None:
                 raise NotImplementedError("generate(output_logits=True) with a logits processor active (frequency_penalty, presence_penalty or "
                                           "patch_suppression): only the processed rows are kept on this path — ask for output_scores=True")
+        beam_orig = None
+        beam = check_beam(n_eos=len(set(opts.eos_ids)), **beam_args) if beam_args is not None else None
+        if beam is not None:
+            # what depends on a row's generated history does not follow the beams (yet): refused by name, before anything is launched
+            check_beam_compatible(opts, processors=bool(hooks and hooks.get("processors")), criteria=bool(hooks and hooks.get("criteria")),
+                                  reference=getattr(self, "precision", "default") == "reference")
+            check_beam_session(self.config, input_ids.shape[0], beam[0])      # the packed caches; B * K rows within what a session takes
+            if group is not None:
+                return None                                       # a beam batch is always its own decode group
+            opts = dataclasses.replace(opts, beam=beam)
+            # the call expanded to B * K rows: every input row K times in place, image_index / prefix composed with the repeat — the existing
+            # sharing then runs the ViT once per image and the common prompt rows once (llm.plan_prompt_shared / plan_prompt_prefix)
+            K, B0 = beam[0], input_ids.shape[0]
+            beam_orig = dict(input_ids=input_ids, attention_mask=attention_mask, image_index=image_index, patch_bias=patch_bias)
+            if image_index is None and (prefix is None or len(prefix.ids) == B0):
+                image_index = list(range(B0))
+            if image_index is not None:
+                image_index = [int(i) for i in image_index for _ in range(K)]
+            input_ids = input_ids.repeat_interleave(K, dim=0)
+            V = self.config.vocab_size
+            if bool((input_ids >= V).any()):
+                # VRT ids of the prompt rows are numbered within the caller's batch; every expanded row owns a range of its own
+                g = (prefix.grid if prefix is not None else image_grid_thw).detach().cpu().long().tolist()
+                idx0 = list(range(B0)) if beam_orig["image_index"] is None else [int(i) for i in beam_orig["image_index"]]
+                n_m = [g[u][0] * g[u][1] * g[u][2] // self.config.merge_unit for u in idx0]
+                shift = [sum(n_m[:b]) * (K - 1) + c * n_m[b] for b in range(B0) for c in range(K)]      # the row's new offset minus its old one
+                shift = torch.tensor(shift, dtype=input_ids.dtype, device=input_ids.device)[:, None]
+                input_ids = torch.where(input_ids >= V, input_ids + shift, input_ids)
+            attention_mask = None if attention_mask is None else attention_mask.repeat_interleave(K, dim=0)
+            patch_bias = None if patch_bias is None else [pb for pb in patch_bias for _ in range(K)]
+            n_slots = 1
         return owner._launch(opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, max_new_tokens=max_new_tokens,
                              schedule=schedule, hooks=hooks, sync_every=sync_every, use_graph=use_graph, lane=lane, decode_stream=decode_stream,
                              group=group, n_slots=n_slots, vit_stream=vit_stream, inputs_ready=inputs_ready, forced=forced, automaton=automaton,
-                             patch_bias=patch_bias, stop=stop, counts=counts, prefix=prefix)
+                             patch_bias=patch_bias, stop=stop, counts=counts, prefix=prefix, beam_orig=beam_orig)
 
     def _launch(self, opts, input_ids, attention_mask, pixel_values, image_grid_thw, image_index, *, max_new_tokens, schedule, hooks, sync_every,
                 use_graph, lane, decode_stream, group, n_slots, vit_stream, inputs_ready, forced=None, automaton=None, patch_bias=None, stop=None,
-                counts=None, prefix=None):
-        """generate_launch on the group's owner, with the call's options resolved (generation.GenOptions)."""
+                counts=None, prefix=None, beam_orig=None):
+        """generate_launch on the group's owner, with the call's options resolved (generation.GenOptions).  beam_orig: a beam call's inputs
+        before their expansion to B * K rows (what a re-run on the bf16 twin is given)."""
         self._batches_seen += 1
         if prefix is None and (pixel_values is None or image_grid_thw is None):
             raise ValueError("pixel_values and image_grid_thw are required (text-only input crashes in the reference too, "
@@ -770,7 +841,8 @@ class PaDTForConditionalGeneration:
             ops.gather_rows(hn_all, plan.last_idx, out=sess.hn_first[rows])
         group["subs"].append(dict(plan=plan, low=low, high=high, pe=pe, proto=proto, hn_all=hn_all, input_ids=input_ids,
                                   n_proto=n_proto, row0=row0, proto_row0=proto_row0, nf=nf, p_max=p_max, forced=forced, automaton=automaton,
-                                  patch_bias=patch_bias, stop=stop, counts=counts, prefix=prefix,
+                                  patch_bias=patch_bias, stop=stop, counts=counts, prefix=prefix, beam_orig=beam_orig,
+                                  row_grids=(grid if image_index is None else grid[torch.as_tensor([int(i) for i in image_index], dtype=torch.long)]).tolist(),
                                   inputs=(attention_mask, pixel_values, image_grid_thw, image_index)))       # what a re-run on the bf16 twin needs
         group["proto_rows"] = proto_row0 + n_proto
         if len(group["subs"]) == group["n_slots"]:
@@ -922,6 +994,9 @@ class PaDTForConditionalGeneration:
             if nf_batch[k_sub] != 0 or any(nf_rows[row0: row0 + B]):
                 outs.append(self._non_finite_batch(group, sub, output_hidden_states, return_dict_in_generate, output_scores, output_logits))
                 continue
+            if opts.beam is not None:
+                outs.append(self._collect_beams(group, sub, output_hidden_states, return_dict_in_generate))
+                continue
             # the reference stops right after the step in which the last sequence finished (padt.py:756-757); any id of the EOS list finishes a row
             fe = fin_step[row0: row0 + B] if opts.stop else first_eos[row0: row0 + B]
             n_steps = max(fe) + 1 if all(f >= 0 for f in fe) else done_steps
@@ -965,6 +1040,41 @@ class PaDTForConditionalGeneration:
             outs.append(out if return_dict_in_generate else sequences)
         return outs if all_batches else outs[0]
 
+    def _collect_beams(self, group, sub, output_hidden_states, return_dict_in_generate):
+        """The output object of a beam batch: B * n_best rows, row b * n_best + r query b's r-th best hypothesis, shaped like a plain call on
+        the inputs repeated n_best times.  padt_beam_finalize walks the parents back on the device (tokens, log-probs, scores, lengths, the
+        hidden rows gathered into StepHiddenStates' layout); the host selects the first n_best of every query's K identical prompt rows."""
+        cfg, dev, sess, plan = self.config, self.device, group["sess"], sub["plan"]
+        K, n_best = group["opts"].beam[0], group["opts"].beam[1]
+        B, V = group["B"] // K, cfg.vocab_size
+        sel = [b * K + r for b in range(B) for r in range(n_best)]                  # the expanded rows that stand for the returned ones
+        n_patch = [plan.vrt_off[i + 1] - plan.vrt_off[i] for i in sel]
+        off = [0]
+        for n in n_patch:
+            off.append(off[-1] + n)
+        off_dev = torch.tensor(off, dtype=torch.int32).to(dev)
+        fin = ops.beam_finalize(sess.beam, n_best, sess.hidden_buf, off_dev, cfg.pad_token_id, V)
+        lengths = fin["lengths"].cpu().tolist()
+        n_steps = max(lengths)
+        sel_dev = torch.tensor(sel, dtype=torch.long, device=dev)
+        sequences = ops.assemble_sequences(sub["input_ids"].to(dev)[sel_dev].contiguous(), fin["tokens"], n_steps, V, 0)
+        # the selected rows of everything that is packed per expanded row: prompt hidden rows, prototypes, patch-level rows
+        ranges = lambda offs: torch.cat([torch.arange(offs[i], offs[i + 1], dtype=torch.long) for i in sel]).to(dev)
+        cu, patch_off = [0], [0]
+        for l, g in zip(plan.lens, sub["row_grids"]):
+            cu.append(cu[-1] + l)
+            patch_off.append(patch_off[-1] + int(g[0]) * int(g[1]) * int(g[2]))
+        hidden = StepHiddenStates(fin["hidden"][:n_steps], n_steps, sub["hn_all"][ranges(cu)], [plan.lens[i] for i in sel], plan.L_pad)
+        prows = ranges(patch_off)
+        out = CustomGenerateDecoderOnlyOutput(
+            sequences=sequences, scores=None, logits=None, attentions=None, hidden_states=hidden if output_hidden_states else None,
+            past_key_values=sess, token_logprobs=fin["logprobs"][:, :n_steps].clone() if group["opts"].token_logprobs else None,
+            top_token_ids=None, top_logprobs=None, patch_logprobs=None, past_image_embeds=sub["proto"][ranges(plan.vrt_off)],
+            past_logit_mask=ops.logit_mask(off_dev, V, V + off[-1], 0, len(sel)), past_high_res_image_embeds=sub["high"][prows],
+            past_visual_pe=tuple(t[prows] for t in sub["pe"]), sequences_scores=fin["scores"],
+            sequence_lengths=fin["lengths"].to(torch.int64))
+        return out if return_dict_in_generate else sequences
+
     def _non_finite_batch(self, group, sub, output_hidden_states, return_dict_in_generate, output_scores, output_logits):
         """A batch whose range guard fired: inf / NaN reached its ViT output, prototypes or hidden rows.  With fp16 operands that is an
         overflow of an un-normalised 16-bit tensor (65504); operands="auto" answers it with the SAME batch on the bf16 instantiation."""
@@ -987,7 +1097,7 @@ class PaDTForConditionalGeneration:
         am, pix, grid, image_index = sub["inputs"]
         # the group's options spelled as explicit arguments (an "off" is 0 / [], never the default), and what this collect was asked to return
         kw = dict(group["opts"].generate_kwargs(), **group["opts"].warper_kwargs(), **group["opts"].bias_kwargs(), **group["opts"].stop_kwargs(),
-                  output_scores=output_scores, output_logits=output_logits)
+                  **group["opts"].beam_kwargs(), output_scores=output_scores, output_logits=output_logits)
         if sub.get("stop") is not None:                           # the batch's own per-row lists: the options only say that there are some
             kw.update({k: v for k, v in sub["stop"].items() if v is not None})
         if sub.get("counts") is not None:                         # the batch's own per-row values: the options only say which mechanism is on
@@ -1002,7 +1112,13 @@ class PaDTForConditionalGeneration:
             kw.update(patch_bias=sub["patch_bias"])               # the batch's tensors: the options only say that there are some
         if sub.get("prefix") is not None:
             kw.update(prefix=sub["prefix"])                       # the caller's handle: the twin reads its bf16 build (made once, _prefix_for)
-        return fb.generate(input_ids=sub["input_ids"], attention_mask=am, pixel_values=pix, image_grid_thw=grid, max_new_tokens=group["T_max"],
+        ids = sub["input_ids"]
+        if sub.get("beam_orig") is not None:                      # a beam batch is re-run from the rows the caller gave, not from their expansion
+            bo = sub["beam_orig"]
+            ids, am, image_index = bo["input_ids"], bo["attention_mask"], bo["image_index"]
+            if bo["patch_bias"] is not None:
+                kw.update(patch_bias=bo["patch_bias"])
+        return fb.generate(input_ids=ids, attention_mask=am, pixel_values=pix, image_grid_thw=grid, max_new_tokens=group["T_max"],
                            schedule=group["schedule"], sync_every=group["sync_every"], use_graph=group["use_graph"], lane=("fb", group["lane"]),
                            output_hidden_states=output_hidden_states, return_dict_in_generate=return_dict_in_generate, image_index=image_index, **kw)
 

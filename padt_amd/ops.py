@@ -1277,6 +1277,139 @@ def collect_summary_stop(err, unfinished, nf_rows, nf_batch, n_batch, tokens, do
     return out
 
 
+DECODE_ROWS_MAX = 128           # rows of one decode step: what padt_gemm_packed_* and the fragment-packed activation buffers take
+BEAM_MAX_WIDTH = 8              # generate(beam_width=): the widest beam padt_beam_step / padt_beam_reorder_kv keep in registers
+BEAM_CFG_MAGIC = 0x424d3031
+BEAM_CFG_INTS = 8
+BEAM_STATE_F32 = ("live", "st_score", "st_lp")                               # per sample [B][K]
+BEAM_STATE_I32 = ("st_end", "st_parent", "st_tok", "sent")                   # per sample [B][K]
+
+
+def beam_cfg_tensor(K, keep, early, t_last, never_max) -> torch.Tensor:
+    """The packed beam config padt_beam_step reads (BEAM_CFG_INTS int32, CPU; layout in include/padt_hip.h): early — 0 False, 1 True,
+    2 "never"; t_last — the call's last step; never_max — the early-stop heuristic divides by the length table's entry of t_last."""
+    return torch.tensor([BEAM_CFG_MAGIC, int(K), int(keep), int(early), int(t_last), 1 if never_max else 0, 0, 0], dtype=torch.int32)
+
+
+class BeamState:
+    """The device state of a beam search over B samples of K beams and t_max steps (padt_beam_step's arrays, by the header's names): the
+    live scores and the finished store [B][K], flags [B][2], the steps' records beam_tok / beam_parent / beam_lp [t_max][B * K], perm and p0
+    [B * K], the config and the length table.  reset() puts it before step 0: live = [0, -inf, ...], an empty store, every sample open."""
+
+    def __init__(self, B, K, t_max, device, own=None):
+        """own(name, numel, dtype) → a flat zeroed device tensor that stays at its address (a session's allocator: every array but `flags`
+        has a size that does not depend on K, and `flags` is asked for at 2 * B * K, so one set of buffers serves every width)."""
+        self.B, self.K, self.t_max = int(B), int(K), int(t_max)
+        R = self.B * self.K
+        own = own or (lambda name, n, dt: torch.zeros(n, device=device, dtype=dt))
+
+        def z(name, shape, dt, n=None):
+            numel = 1
+            for d in shape:
+                numel *= d
+            return own(name, numel if n is None else n, dt)[:numel].view(shape)
+        for n in BEAM_STATE_F32:
+            setattr(self, n, z(n, (self.B, self.K), torch.float32))
+        for n in BEAM_STATE_I32:
+            setattr(self, n, z(n, (self.B, self.K), torch.int32))
+        self.flags = z("flags", (self.B, 2), torch.int32, n=2 * R)
+        self.beam_tok, self.beam_parent = (z(n, (self.t_max, R), torch.int32) for n in ("beam_tok", "beam_parent"))
+        self.beam_lp = z("beam_lp", (self.t_max, R), torch.float32)
+        self.perm, self.p0 = z("perm", (R,), torch.int32), z("p0", (R,), torch.int32)
+        self.cfg = z("cfg", (BEAM_CFG_INTS,), torch.int32)
+        self.len_table = z("len_table", (self.t_max,), torch.float32)
+        self.len_table.fill_(1.0)
+        self.reset()
+
+    def reset(self):
+        self.live.fill_(float("-inf"))
+        self.live[:, 0] = 0.0
+        self.st_score.fill_(float("-inf"))
+        for t in (self.st_lp, self.st_tok, self.sent, self.beam_tok, self.beam_parent, self.beam_lp, self.p0):
+            t.zero_()
+        self.st_end.fill_(-1)
+        self.st_parent.fill_(-1)
+        self.st_tok.fill_(-1)
+        self.flags[:, 0] = 1
+        self.flags[:, 1] = 0
+        self.perm.copy_(torch.arange(self.B * self.K, device=self.perm.device, dtype=torch.int32) % self.K)
+
+
+def beam_step(st, top_idx, top_val, hidden, hidden_buf, unfinished, cur_tok, step, slot, lens, pos3, vrt_off, eos, pad, vocab, n_cols,
+              advance=True, gen_cfg=None, err=None, rep_lp=None):
+    """One beam-search step of every sample of `st` (a BeamState), in the place of greedy_step (padt_beam_step): reads the rows' entries of
+    top_idx / top_val (B * K, t_top, keep) at the device step counter, updates the state, files the step's records and does greedy_step's
+    chores for the B * K rows (hidden rows, slot / lens / pos3, unfinished of a done sample's rows, the step counter).  rep_lp (fp32
+    (B * K, keep), beam_cand_lp's): the log-probs recorded for the candidates instead of top_val's; the scores add top_val's either way."""
+    R, D = hidden.shape
+    assert R == st.B * st.K and hidden.is_contiguous() and hidden_buf.is_contiguous() and hidden_buf.shape == (st.t_max, R, D), "beam_step: rows"
+    assert top_idx.dtype == torch.int32 and top_val.dtype == torch.float32 and top_idx.is_contiguous() and top_val.is_contiguous()
+    assert top_idx.dim() == 3 and top_idx.shape == top_val.shape and top_idx.shape[0] == R
+    _chk_i32(step, n=1)
+    _chk_i32(unfinished, slot, lens, n=R)
+    _chk_i32(vrt_off, n=R + 1)
+    assert pos3.dtype == torch.int32 and pos3.is_contiguous() and pos3.shape == (3, R) and cur_tok.dtype == torch.int64 and cur_tok.numel() == R
+    _lib.check(_lib.load().padt_beam_step(
+        _stream(), _p(top_idx), _p(top_val), top_idx.shape[1], top_idx.shape[2], st.B, st.K, D, st.t_max, _p(st.cfg), _p(st.len_table), _p(gen_cfg),
+        int(eos), int(pad), int(vocab), int(n_cols), _p(vrt_off), _p(st.live), _p(st.st_score), _p(st.st_lp), _p(st.st_end), _p(st.st_parent),
+        _p(st.st_tok), _p(st.sent), _p(st.flags), _p(st.beam_tok), _p(st.beam_parent), _p(st.beam_lp), _p(st.perm), _p(cur_tok), _p(unfinished),
+        _p(step), _p(slot), _p(lens), _p(pos3), _p(hidden), _p(hidden_buf), 1 if advance else 0, _p(err), _p(rep_lp)), "padt_beam_step")
+
+
+def beam_cand_lp(part_val, part_idx, part_sum, nblk, rows, n_cols, top_idx, step, out):
+    """out[b, j] = log_softmax(rows[b])[top_idx[b, *step, j]] as padt_greedy_step_lp / padt_forced_step compute it from the LSE head's block
+    partials (padt_beam_cand_lp): what a beam step records as a candidate's token log-prob.  rows fp32 (R, >= n_cols), out fp32 (R, keep)."""
+    R, keep = top_idx.shape[0], top_idx.shape[2]
+    assert rows.dtype == torch.float32 and rows.is_cuda and rows.dim() == 2 and rows.stride(1) == 1 and rows.shape[0] >= R
+    assert part_val.dtype == torch.float32 and part_sum.dtype == torch.float32 and part_idx.dtype == torch.int32
+    assert part_val.numel() >= nblk * R and part_sum.numel() >= nblk * R and part_idx.numel() >= nblk * R
+    assert top_idx.dtype == torch.int32 and top_idx.is_contiguous() and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= R * keep
+    _lib.check(_lib.load().padt_beam_cand_lp(_stream(), _p(part_val), _p(part_idx), _p(part_sum), int(nblk), R, _p(rows), rows.stride(0), int(n_cols),
+                                             _p(top_idx), top_idx.shape[1], keep, _p(step), _p(out)), "padt_beam_cand_lp")
+    return out
+
+
+
+def beam_kv_table(k_images, vt_images) -> torch.Tensor:
+    """The device table of cache image pointers beam_reorder_kv reads: int64 (layers, 2) = (K image, V^T image) of every layer.  The images
+    must stay allocated while the table is in use (a session builds it once over its own caches)."""
+    assert len(k_images) == len(vt_images) and len(k_images) > 0
+    for k, v in zip(k_images, vt_images):
+        assert k.is_cuda and v.is_cuda and k.is_contiguous() and v.is_contiguous() and k.element_size() == 2 and v.element_size() == 2
+        assert k.dim() == 4 and k.shape[:2] == v.shape[:2] and k.shape[2] == v.shape[3] and k.shape[3] == v.shape[2], "beam_kv_table: (B, Hkv, S, D) / (B, Hkv, D, S)"
+        assert k.shape == k_images[0].shape
+    return torch.tensor([[k.data_ptr(), v.data_ptr()] for k, v in zip(k_images, vt_images)], dtype=torch.int64).to(k_images[0].device)
+
+
+def beam_reorder_kv(table, perm, p0, slot, B, K, n_kv_heads, head_dim, s_max, t_max, rows=None):
+    """The packed KV caches of every layer follow the beams (padt_beam_reorder_kv): slots [p0, slot) of row sample * K + c get the former
+    bits of row sample * K + perm[c], in place, for the images `table` (beam_kv_table) names.  rows: the images' row count (checked against
+    B * K when given)."""
+    assert table.dtype == torch.int64 and table.is_cuda and table.is_contiguous() and table.dim() == 2 and table.shape[1] == 2
+    _chk_i32(perm, p0, slot, n=int(B) * int(K))
+    assert rows is None or int(rows) == int(B) * int(K), "beam_reorder_kv: the images hold B * K rows"
+    _lib.check(_lib.load().padt_beam_reorder_kv(_stream(), _p(table), table.shape[0], _p(perm), _p(p0), _p(slot), int(B), int(K), int(n_kv_heads),
+                                                int(head_dim), int(s_max), int(t_max)), "padt_beam_reorder_kv")
+
+
+def beam_finalize(st, n_best, hidden_buf, out_off, pad, vocab):
+    """generation.beam_backtrace on the device (padt_beam_finalize) → dict(tokens (B * n_best, t_max) int64, logprobs (same) fp32, scores
+    (B * n_best,) fp32, lengths int32, src_row (B * n_best, t_max) int32, hidden (t_max, B * n_best, D) — zero behind a hypothesis's end).
+    out_off: int32 (B * n_best,) — the patch offset of every returned row in the returned batch's VRT numbering."""
+    n, dev = st.B * int(n_best), hidden_buf.device
+    D = hidden_buf.shape[2]
+    assert hidden_buf.is_contiguous() and hidden_buf.shape[:2] == (st.t_max, st.B * st.K)
+    _chk_i32(out_off, n=n)
+    out = dict(tokens=torch.empty((n, st.t_max), device=dev, dtype=torch.int64), logprobs=torch.empty((n, st.t_max), device=dev, dtype=torch.float32),
+               scores=torch.empty(n, device=dev, dtype=torch.float32), lengths=torch.empty(n, device=dev, dtype=torch.int32),
+               src_row=torch.empty((n, st.t_max), device=dev, dtype=torch.int32), hidden=torch.zeros((st.t_max, n, D), device=dev, dtype=hidden_buf.dtype))
+    _lib.check(_lib.load().padt_beam_finalize(
+        _stream(), _p(st.st_score), _p(st.st_lp), _p(st.st_end), _p(st.st_parent), _p(st.st_tok), _p(st.beam_tok), _p(st.beam_parent), _p(st.beam_lp),
+        st.B, st.K, int(n_best), D, st.t_max, int(pad), int(vocab), _p(out_off), _p(hidden_buf), _p(out["hidden"]), _p(out["tokens"]),
+        _p(out["logprobs"]), _p(out["scores"]), _p(out["lengths"]), _p(out["src_row"])), "padt_beam_finalize")
+    return out
+
+
 def assemble_sequences(input_ids, tokens, n_steps, vocab, proto_row0):
     """→ (B, L + n_steps) int64: [input_ids | tokens[:, :n_steps]] with session-global VRT ids shifted back by proto_row0 (padt.py:751)."""
     assert input_ids.dtype == torch.int64 and input_ids.stride(1) == 1 and tokens.dtype == torch.int64 and tokens.stride(1) == 1

@@ -22,7 +22,8 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
               schedule: Optional[Sequence] = None, need_thinking_mask=None, image_index=None, do_sample=False, min_p=None, typical_p=None,
               epsilon_cutoff=None, eta_cutoff=None, forced_tokens=None, token_automaton=None, logit_bias=None, patch_bias=None,
               exponential_decay_length_penalty=None, stop_sequences=None, min_tokens=None, max_tokens=None, frequency_penalty=None,
-              presence_penalty=None, patch_suppression=None, prefix=None, **gen_kw):
+              presence_penalty=None, patch_suppression=None, prefix=None, beam_width=None, n_best=None, beam_length_penalty=None,
+              beam_early_stopping=None, **gen_kw):
     """→ (decoded dict of vl_decode, completions, labels, vrts).  ``input_ids`` carries LOCAL VRT ids (as a processor
     emits them) and is updated in place exactly like the reference's callers do.
     ``image_index``: sample b asks about image image_index[b] of the N <= B images given (generate(image_index=)); everything per sample
@@ -37,7 +38,10 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
     sample over its own patches; (start, factor)).
     ``stop_sequences`` / ``min_tokens`` / ``max_tokens``: generate()'s — how a row ends; the decoded dict then carries ``finish_reason`` /
     ``stop_index`` / ``finish_step``.
-    ``frequency_penalty`` / ``presence_penalty`` / ``patch_suppression``: generate()'s count edits (a value, or one per sample)."""
+    ``frequency_penalty`` / ``presence_penalty`` / ``patch_suppression``: generate()'s count edits (a value, or one per sample).
+    ``beam_width`` / ``n_best`` / ``beam_length_penalty`` / ``beam_early_stopping``: generate()'s beam search; everything returned then has
+    B * n_best entries (entry b * n_best + r: sample b's r-th best hypothesis) and the decoded dict carries ``sequences_scores`` /
+    ``sequence_lengths``."""
     B = input_ids.shape[0]
     grid_in = image_grid_thw
     if prefix is not None:                                        # the handle's grids stand in for the caller's (generate() refuses both)
@@ -53,8 +57,11 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
                          epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, forced_tokens=forced_tokens, token_automaton=token_automaton,
                          logit_bias=logit_bias, patch_bias=patch_bias, exponential_decay_length_penalty=exponential_decay_length_penalty,
                          stop_sequences=stop_sequences, min_tokens=min_tokens, max_tokens=max_tokens, frequency_penalty=frequency_penalty,
-                         presence_penalty=presence_penalty, patch_suppression=patch_suppression, **gen_kw)
+                         presence_penalty=presence_penalty, patch_suppression=patch_suppression, beam_width=beam_width, n_best=n_best,
+                         beam_length_penalty=beam_length_penalty, beam_early_stopping=beam_early_stopping, **gen_kw)
     L = input_ids.shape[1]
+    if beam_width is not None:                                    # B * n_best rows, shaped like a plain call on the inputs repeated n_best times
+        image_grid_thw, need_thinking_mask, B = beam_rows(n_best or 1, image_grid_thw, need_thinking_mask, B)
     seq_local = processor.assign_to_local_vrt_id(out["sequences"].cpu(), image_grid_thw.cpu())
     completion_ids = seq_local[:, L:]
     mask = need_thinking_mask if need_thinking_mask is not None else torch.Tensor([False] * B)
@@ -65,10 +72,20 @@ def rec_batch(model, processor, input_ids, attention_mask, pixel_values, image_g
     for name in ("top_token_ids", "top_logprobs", "patch_logprobs"):      # generate(top_logprobs=k, output_patch_logprobs=True), likewise
         if out[name] is not None:
             decoded[name] = out[name]
-    for name in ("finish_reason", "stop_index", "finish_step"):           # generate(stop_sequences=, min_tokens=, max_tokens=)
+    for name in ("finish_reason", "stop_index", "finish_step",            # generate(stop_sequences=, min_tokens=, max_tokens=)
+                 "sequences_scores", "sequence_lengths"):                 # generate(beam_width=)
         if name in out:
             decoded[name] = out[name]
     return decoded, completions, labels, vrts
+
+
+def beam_rows(n_best, image_grid_thw, need_thinking_mask, B):
+    """What is per sample on the host side of a generate(beam_width=, n_best=) call, repeated n_best times in place → (grids, mask, rows)."""
+    n = int(n_best)
+    mask = need_thinking_mask
+    if mask is not None:
+        mask = torch.as_tensor(mask).repeat_interleave(n, dim=0)
+    return torch.as_tensor(image_grid_thw).repeat_interleave(n, dim=0), mask, B * n
 
 
 class PipelinedRunner:
@@ -126,7 +143,8 @@ class PipelinedRunner:
                bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, image_index=None, do_sample=False, min_p=None,
                typical_p=None, epsilon_cutoff=None, eta_cutoff=None, forced_tokens=None, token_automaton=None, logit_bias=None, patch_bias=None,
                exponential_decay_length_penalty=None, stop_sequences=None, min_tokens=None, max_tokens=None, frequency_penalty=None,
-               presence_penalty=None, patch_suppression=None, prefix=None, **sampling):
+               presence_penalty=None, patch_suppression=None, prefix=None, beam_width=None, n_best=None, beam_length_penalty=None,
+               beam_early_stopping=None, **sampling):
         """image_index: see generate(); the batch's results are those of the expanded batch.
         prefix: generate(prefix=) — pixel_values / image_grid_thw are then None and the grids are the handle's; the batch's ViT stream is idle.
         do_sample (default: greedy) with min_p / typical_p / epsilon_cutoff / eta_cutoff and, through **sampling, temperature / top_k / top_p /
@@ -141,7 +159,9 @@ class PipelinedRunner:
         "finish_step".  Batches share a decode group only when stop_sequences and a one-value min_tokens are equal and both or neither carry
         per-row lists (each batch its own min_tokens / max_tokens rows).
         frequency_penalty / presence_penalty / patch_suppression: generate()'s count edits.  Batches share a decode group whatever their
-        values are (each batch writes its own rows), as long as the same of the two mechanisms — token counts, patch suppression — are on."""
+        values are (each batch writes its own rows), as long as the same of the two mechanisms — token counts, patch suppression — are on.
+        beam_width / n_best / beam_length_penalty / beam_early_stopping: generate()'s beam search.  A beam batch is always its own decode
+        group, whatever `merge` is; its results have B * n_best entries and the decoded dict carries "sequences_scores" / "sequence_lengths"."""
         done = []
         bid = self.n_batches
         self.n_batches += 1
@@ -166,6 +186,11 @@ class PipelinedRunner:
             hooks["stop"] = dict(stop_sequences=stop_sequences, min_tokens=min_tokens, max_tokens=max_tokens)
         if frequency_penalty is not None or presence_penalty is not None or patch_suppression is not None:
             hooks["counts"] = dict(frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, patch_suppression=patch_suppression)
+        beam = dict(beam_width=beam_width, n_best=n_best, beam_length_penalty=beam_length_penalty, beam_early_stopping=beam_early_stopping)
+        if any(v is not None for v in beam.values()):
+            hooks["beam"] = beam
+            if self.cur is not None and self.cur["ctx"] is not None:
+                self._close_cur()                                 # a beam batch never joins a group that holds a batch
         for attempt in range(2):
             if self.cur is None:
                 while len(self.pending) > self.depth - 1:         # the lane about to be reused must have been collected
@@ -204,10 +229,14 @@ class PipelinedRunner:
             raise RuntimeError("batch rejected by an empty decode group")
         self._mark(bid, "prefill_end", pre)
         g["ctx"] = ctx
-        g["meta"].append((input_ids.shape, image_grid_thw, need_thinking_mask))
+        shape = tuple(input_ids.shape)
+        if beam_width is not None:
+            image_grid_thw, need_thinking_mask, rows = beam_rows(n_best or 1, image_grid_thw, need_thinking_mask, shape[0])
+            shape = (rows, shape[1])
+        g["meta"].append((shape, image_grid_thw, need_thinking_mask))
         g.setdefault("keep", []).append((ids, attention_mask, pixel_values))
         g["bids"].append(bid)
-        if len(g["meta"]) == self.merge:
+        if len(g["meta"]) == self.merge or beam_width is not None:       # ... and takes no second one
             self._close_cur()
         while len(self.pending) >= self.depth:
             done += self._finish_oldest()
@@ -232,7 +261,8 @@ class PipelinedRunner:
                 for name in ("top_token_ids", "top_logprobs", "patch_logprobs"):      # submit(top_logprobs=k, output_patch_logprobs=True)
                     if out[name] is not None:
                         decoded[name] = out[name]
-                for name in ("finish_reason", "stop_index", "finish_step"):           # submit(stop_sequences=, min_tokens=, max_tokens=)
+                for name in ("finish_reason", "stop_index", "finish_step",            # submit(stop_sequences=, min_tokens=, max_tokens=)
+                             "sequences_scores", "sequence_lengths"):                 # submit(beam_width=)
                     if name in out:
                         decoded[name] = out[name]
                 res.append((decoded, completions, labels, vrts))
